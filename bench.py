@@ -81,8 +81,15 @@ def parse():
                     help="records of the text-in -> text-out leg (`rb [--gpus N] liftover` on the PAF text of the same workload, first byte "
                          "read to last byte written; 1e6 = the headline size, 14.7 GB in / 19 GB out in /dev/shm -- cut to 1e5 when the "
                          "host lacks the memory); 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64): a fixed, seeded sample of the "
+                         "hit rows, the clipped CIGAR ops of those rows, a sample of the normalised records, and the counts and digest of the "
+                         "whole output; rank 0's shard when --gpus > 1")
     ap.add_argument("--launch-dry-run", action="store_true", help=argparse.SUPPRESS)  # tests: ranks report their environment and exit
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def launch_ranks(args):
@@ -278,6 +285,63 @@ class SmiSampler:
             return {"samples": n, **{k_: [v[0], v[1]] for k_, v in sorted(out.items())}} if n else {"samples": 0}
         except Exception as e:
             return {"error": f"{type(e).__name__}: {e}"}
+
+
+DUMP_SEED = 0x5EED_D0E5  # which hit rows and records --dump-outputs samples: fixed, so that two builds write the same rows
+DUMP_ROWS = 8192         # hit rows in the sample (and the clipped CIGARs of those rows)
+DUMP_RECORDS = 8192      # normalised records in the sample
+DUMP_CLIP_OPS = 4 << 20  # at most this many clipped ops (32 MB as float64): the whole dump stays far below 64 MB
+
+
+def dump_outputs(out_dir, torch, dev, d_rows, n_hits, d_out, d_norm, n_rec, n_ok, n_out_ops, digest):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files in out_dir.  The outputs are far larger than a
+    dump should be (1e7+ hit rows, 1e9+ clipped ops), so rows and records are a sample drawn with a fixed seed; `summary` carries the
+    counts and the digest of the whole output (rb_dev_digest_rows over every row and clipped op).  Fields that only say how the result
+    was reached are left out (out_off: where the clip landed in the arena; RB_HIT_GENERIC: which kernel resolved it), and the value
+    fields of a row or record whose status is not RB_ST_OK are written as 0 (they carry no result).  Every value is an integer below
+    2^53, exact in float64."""
+    import rustybam_amd
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+
+    def save(name, a):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = int(a.nbytes)
+
+    rng = np.random.default_rng(DUMP_SEED)
+    ridx = np.sort(rng.choice(n_hits, size=min(n_hits, DUMP_ROWS), replace=False)) if n_hits else np.zeros(0, np.int64)
+    rows = d_rows[: n_hits * 64].view(n_hits, 64)[torch.from_numpy(ridx).to(dev)].cpu().numpy().view(rustybam_amd.HIT_DT).reshape(-1)
+    ok = rows["status"] == 0
+    save("hit_rec", rows["rec"])
+    save("hit_win", rows["win"])
+    save("hit_status", rows["status"])
+    save("hit_flags", (rows["flags"] & ~np.uint16(rustybam_amd.HIT_GENERIC)) * ok)
+    for key in ("out_n", "t_st", "t_en", "q_st", "q_en", "nmatch", "aln_len"):
+        save("hit_" + key, rows[key] * ok)
+    # the clipped CIGARs of the sampled rows (packed len << 4 | op; a RB_HIT_DESCRIPTOR row: its 4-word descriptor), row after row in
+    # sample order; clip_off[i] .. clip_off[i + 1] is row i's
+    n_keep = np.where(rows["flags"] & rustybam_amd.HIT_DESCRIPTOR, 4, rows["out_n"]).astype(np.int64) * ok
+    clip_off = np.zeros(len(rows) + 1, np.int64)
+    clip_off[1:] = np.minimum(np.cumsum(n_keep), DUMP_CLIP_OPS)
+    sel = np.concatenate([np.arange(o, o + n, dtype=np.int64) for o, n in zip(rows["out_off"].astype(np.int64), n_keep)]) if len(rows) else np.zeros(0, np.int64)
+    sel = sel[:DUMP_CLIP_OPS]
+    if len(sel) and not (0 <= sel.min() and sel.max() < d_out.numel()):  # (checked here: never an out-of-range gather on the device)
+        raise RuntimeError(f"--dump-outputs: a clipped CIGAR lies outside the output arena ({sel.min()} .. {sel.max()}, {d_out.numel()} ops)")
+    save("clip_off", clip_off)
+    save("clip_ops", d_out[torch.from_numpy(sel).to(dev)].cpu().numpy().view(np.uint32))
+    # the records as the step normalised them (remove_trailing_indels + check_integrity; an output of the fused step)
+    nidx = np.sort(rng.choice(n_rec, size=min(n_rec, DUMP_RECORDS), replace=False)) if n_rec else np.zeros(0, np.int64)
+    norm = d_norm[: n_rec * 64].view(n_rec, 64)[torch.from_numpy(nidx).to(dev)].cpu().numpy().view(rustybam_amd.NORM_DT).reshape(-1)
+    nok = norm["status"] == 0
+    save("norm_rec", nidx)
+    save("norm_status", norm["status"])
+    save("norm_flags", (norm["flags"] & np.uint32(7)) * nok)  # RB_F_REGULAR | RB_F_STRIPPED | RB_F_HAS_M: the bits a caller sees
+    for key in ("t_st", "t_en", "q_st", "q_en", "first_op", "n_ops", "lead_ops", "trail_ops", "nmatch", "aln_len"):
+        save("norm_" + key, norm[key] * nok)
+    save("summary", [n_hits, n_ok, n_out_ops, digest >> 32, digest & 0xFFFFFFFF])  # the digest as two 32-bit halves (exact in float64)
+    return {"dir": out_dir, "files": len(written), "bytes": sum(written.values()), "sample_rows": int(len(rows)), "sample_records": int(len(norm)),
+            "clip_ops": int(len(sel))}
 
 
 def under_profiler():
@@ -695,6 +759,9 @@ def main():
     out_n = rows_t[:, 3].to(torch.int64)
     n_ok = int((status == 0).sum().item())
     n_out_ops = int((out_n * (status == 0)).sum().item())
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (outside the timed region; before anything below launches the step again or reuses its buffers)
+        dumped = dump_outputs(args.dump_outputs, torch, dev, d_rows, n_hits, d_out, d_norm, n_rec, n_ok, n_out_ops, digest)
     algo_bytes = wl.algorithmic_bytes(total_ops, n_rec, n_hits, n_out_ops)
     # (break-paf is priced with the same single-pass formula although this build walks the ops twice:
     #  collect pieces, clip; its rate is taken over the whole step, not one kernel)
@@ -796,6 +863,8 @@ def main():
     }
     if e2e:
         result.update(e2e)
+    if dumped:
+        result["dump_outputs"] = dumped
 
     # ---- CPU baseline + sample parity (rank 0, N = 1 only) ----
     if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.descriptors and args.op == "liftover" and not irregular and args.irregular_frac == 0:

@@ -14,9 +14,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RB = os.path.join(ROOT, "rustybam_amd", "rb")
 
 
-def rb(*args, env=None):
+def rb_run(*args, env=None):
     assert os.path.exists(RB), "rustybam_amd/rb missing: run __graft_entry__.build()"
-    r = subprocess.run([RB, *map(str, args)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=None if env is None else {**os.environ, **env})
+    return subprocess.run([RB, *map(str, args)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=None if env is None else {**os.environ, **env})
+
+
+def rb(*args, env=None):
+    r = rb_run(*args, env=env)
     return r.returncode, r.stdout
 
 
@@ -483,14 +487,15 @@ def test_gpus_flag_gathers_the_single_gpu_bytes(golden, args, n, tmp_path):
     srcs = [f"{golden}/asm_small.paf"] + ([] if ".gz" in args[-1] else [_shuffled(golden, tmp_path, 7), _shuffled(golden, tmp_path, 8)])
     for src in srcs:
         a = [x.format(paf=src, bed=f"{golden}/asm_small.bed", qbed=_qbed(golden, tmp_path)) for x in args]
-        rc1, out1 = rb(*a)
-        rcn, outn = rb("--gpus", n, *a, env={"RB_GPUS_SAME_DEVICE": "1"})
-        assert (rc1, rcn) == (0, 0)
+        one = rb_run(*a)
+        many = rb_run("--gpus", n, *a, env={"RB_GPUS_SAME_DEVICE": "1"})
+        assert (one.returncode, many.returncode) == (0, 0), (a, n, one.stderr[-1000:], many.stderr[-2000:])
+        out1, outn = one.stdout, many.stdout
         assert len(out1) > 1000, a
         assert outn == out1, (a, n)
         with open(tmp_path / "out.paf", "wb") as f:
             r = subprocess.run([RB, "--gpus", str(n), *a], stdout=f, stderr=subprocess.PIPE, env={**os.environ, "RB_GPUS_SAME_DEVICE": "1"})
-        assert r.returncode == 0 and open(tmp_path / "out.paf", "rb").read() == out1, (a, n, "file")
+        assert r.returncode == 0 and open(tmp_path / "out.paf", "rb").read() == out1, (a, n, "file", r.stderr[-2000:])
 
 
 def test_gpus_flag_interleaved_contigs_vs_oracle(golden, oracle, tmp_path):

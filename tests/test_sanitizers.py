@@ -70,8 +70,21 @@ def rb_san():
     if not (_toolchain_has(["-fsanitize=address,undefined"], "g++") and _toolchain_has(["-fsanitize=thread"], "g++")):
         pytest.skip("this toolchain has no libasan / libubsan / libtsan: nothing to run rb under")
     subprocess.check_call(["make", "-s", "-j2", "-C", CSRC, "sanitizers"])  # (a build error here is a regression, not a skip)
-    return {"asan": os.path.join(ROOT, "rustybam_amd", "rb_asan"), "tsan": os.path.join(ROOT, "rustybam_amd", "rb_tsan"),
-            "plain": os.path.join(ROOT, "rustybam_amd", "rb")}
+    return {"asan": [os.path.join(ROOT, "rustybam_amd", "rb_asan")], "tsan": _no_aslr() + [os.path.join(ROOT, "rustybam_amd", "rb_tsan")],
+            "plain": [os.path.join(ROOT, "rustybam_amd", "rb")]}
+
+
+def _no_aslr():
+    """ThreadSanitizer (gcc's) knows a fixed layout of the address space: on a kernel that randomises addresses with more bits than that
+    layout allows for, the binary lands outside it and TSan stops at start-up ("FATAL: ThreadSanitizer: unexpected memory mapping")
+    before it has run anything.  The TSan build therefore runs with address randomisation off for that process alone (`setarch -R`,
+    what newer TSan runtimes do by themselves), where this box lets a process ask for that."""
+    import platform
+    import shutil
+    cmd = ["setarch", platform.machine(), "-R"]
+    if shutil.which("setarch") and subprocess.run(cmd + ["true"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL).returncode == 0:
+        return cmd
+    return []
 
 
 def _shuffled(tmp_path, seed):
@@ -87,22 +100,22 @@ def _shuffled(tmp_path, seed):
 def test_rb_gather_and_line_splitter_under_sanitizers(rb_san, tmp_path, san):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1", TSAN_OPTIONS="report_signal_unsafe=0")
     paf = _shuffled(tmp_path, 5)
-    want = subprocess.run([rb_san["plain"], "regroup", paf], stdout=subprocess.PIPE).stdout
+    want = subprocess.run([*rb_san["plain"], "regroup", paf], stdout=subprocess.PIPE).stdout
     assert want.count(b"\n") > 200
     for flags in ([], ["-q"], ["-l"]):
-        one = subprocess.run([rb_san["plain"], "regroup", *flags, paf], stdout=subprocess.PIPE).stdout
+        one = subprocess.run([*rb_san["plain"], "regroup", *flags, paf], stdout=subprocess.PIPE).stdout
         for n in (1, 3):
             pre = ["--gpus", str(n)] if n > 1 else []
-            r = subprocess.run([rb_san[san], *pre, "regroup", *flags, paf], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+            r = subprocess.run([*rb_san[san], *pre, "regroup", *flags, paf], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
             _clean(r.stderr, f"{san} regroup {flags} n={n}")
             assert r.returncode == 0 and r.stdout == one, (san, flags, n, r.stderr[-400:])
             out = tmp_path / f"o_{san}_{n}.paf"
             with open(out, "wb") as f:  # (a regular file: workers pwrite at assigned offsets)
-                r = subprocess.run([rb_san[san], *pre, "regroup", *flags, paf], stdout=f, stderr=subprocess.PIPE, env=env)
+                r = subprocess.run([*rb_san[san], *pre, "regroup", *flags, paf], stdout=f, stderr=subprocess.PIPE, env=env)
             _clean(r.stderr, f"{san} regroup to a file {flags} n={n}")
             assert r.returncode == 0 and open(out, "rb").read() == one
     # the whole fixture (2 MB of CIGAR text) through the threaded line splitter
     full = os.path.join(GOLDEN, "asm_small.paf")
-    r = subprocess.run([rb_san[san], "--gpus", "2", "regroup", full], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+    r = subprocess.run([*rb_san[san], "--gpus", "2", "regroup", full], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
     _clean(r.stderr, f"{san} regroup of the fixture")
-    assert r.returncode == 0 and r.stdout == subprocess.run([rb_san["plain"], "regroup", full], stdout=subprocess.PIPE).stdout
+    assert r.returncode == 0 and r.stdout == subprocess.run([*rb_san["plain"], "regroup", full], stdout=subprocess.PIPE).stdout
