@@ -105,9 +105,9 @@ enum { RB_BSEARCH_MODERN = 0 /* rustc >= 1.82 (and < 1.52) */, RB_BSEARCH_LEGACY
         * norm row ends up with status != RB_ST_OK carry that status. */
        RB_LIFT_FUSED_SCAN = 64,
        /* RB_BREAK_ONE_WALK (rb_dev_break): the clip kernel finds the long indels itself while it streams a record (no separate pass
-        * that collects the pieces first: the ops are read once).  The caller must look at counters->redo_two_walk afterwards: set,
-        * the batch holds something this path does not take (an irregular record, a boundary the fast path cannot
-        * resolve), the results are incomplete and the call is to be repeated without this flag (rb_host_break does). */
+        * that collects the pieces first: the ops are read once).  The records this path does not take (irregular CIGARs, records
+        * its verification hands back, boundaries only the generic kernel resolves) are declined one by one inside the same call:
+        * their pieces are found in a pass of their own and the generic kernel clips them.  The results are complete either way. */
        RB_BREAK_ONE_WALK = 128,
        /* RB_LIFT_OP_STARTS (rb_dev_liftover, rb_dev_break; not with RB_LIFT_FUSED_SCAN or RB_LIFT_DESCRIPTORS): the batch is one that trim-paf has cut IN PLACE
         * (rb_dev_overlap_split with RB_TRIM_IN_PLACE + rb_dev_apply_pairs): batch->op_off[r] is where record r starts and says nothing
@@ -184,8 +184,7 @@ typedef struct rb_counters { /* device-written job summary, 64 bytes */
                                     without debug_skip: phase[3] = tiles of short records the call ran (0: none), phase[4] = records of
                                     those tiles that the tile kernel handed back to the per-record kernel (informational) */
     uint32_t brk_scratch_short;  /* RB_BREAK_ONE_WALK only: != 0: a scratch-row cursor ran out before the rows did; n_hits then asks for more */
-    uint32_t redo_two_walk;      /* RB_BREAK_ONE_WALK only: != 0: the batch holds what the one-walk path does not take (irregular
-                                    records, boundaries only the generic kernel resolves): results incomplete, call again without the flag */
+    uint32_t redo_two_walk;      /* always 0: kept for the layout (RB_BREAK_ONE_WALK declines records one by one inside the call) */
 } rb_counters;
 
 /* per-record outcome of rb_dev_parse_cigars */

@@ -22,144 +22,14 @@
 #include "../../include/rustybam_amd.h"
 #include "rb_lift.h" // rb_lift_params (the device helpers in it are unused here)
 #include "rb_trim.h" // rb_trim_params
+#include "rb_launch.h" // the other kernels' parameter blocks and launchers
 
-// ---- kernel-side parameter blocks (must match the .hip files) ----------------------------------
-struct rb_scan_params {
-    uint64_t n_rec;
-    const uint32_t *ops;
-    const uint64_t *op_off;
-    const uint64_t *t_st, *t_en, *q_st, *q_en;
-    const uint8_t *strand;
-    rb_reduce_row *reduce_rows;
-    rb_norm_row *norm_rows;
-    const uint32_t *list;
-    const uint64_t *n_list;
-};
-struct rb_break_params {
-    uint64_t n_rec;
-    const uint32_t *ops;
-    const uint64_t *op_off;
-    const rb_norm_row *norm;
-    const uint32_t *sched;
-    uint64_t *hit_off; // indexed by record (break-paf order is record order)
-    uint64_t *x_st, *x_en;
-    uint64_t rows_cap;
-    uint32_t max_size;
-    int fill;
-    int redo_only;
-    void *tmp;
-    uint64_t *tmp_off;
-    unsigned long long *tmp_cursor;
-    uint32_t n_arena;
-    uint64_t arena_cap;
-    const uint32_t *list;
-    const unsigned long long *n_list;
-};
-// (rb_trim_params: rb_trim.h)
-struct rb_swap_params {
-    uint64_t n_rec;
-    const uint32_t *ops;
-    const uint64_t *op_off;
-    const uint8_t *strand;
-    uint32_t *out_ops;
-};
-
-extern "C" hipError_t rb_launch_scan_records(const rb_scan_params *p, hipStream_t stream);
-extern "C" hipError_t rb_launch_scan_rows(const rb_scan_params *p, void *long_buf, hipStream_t stream);
 #ifndef RB_SCAN_ROWS_MEAN_MAX
 #define RB_SCAN_ROWS_MEAN_MAX 1536 // ops per record, batch mean, up to which rb_dev_scan_records takes the row form (k_records.hip)
 #endif
-extern "C" hipError_t rb_launch_peek_norm(const rb_scan_params *p, hipStream_t stream);
-extern "C" hipError_t rb_launch_count_and_scan(const rb_lift_params *p, uint64_t *block_sums, bool do_count, hipStream_t stream);
-struct rb_parse_params {
-    uint64_t n_rec;
-    const uint8_t *text;
-    const uint64_t *text_off;
-    const uint64_t *text_end;
-    uint64_t *op_off;
-    uint32_t *ops;
-    uint64_t ops_cap;
-    uint8_t *status;
-};
-struct rb_format_params {
-    uint64_t n_items;
-    const uint32_t *ops;
-    const uint32_t *ops_alt;
-    const uint64_t *first;
-    const uint32_t *count;
-    const uint32_t *first_len;
-    const uint32_t *last_len;
-    uint64_t *text_off;
-    uint8_t *text;
-    uint64_t text_cap;
-    int plain_ops;
-};
-extern "C" hipError_t rb_launch_parse_cigars(const rb_parse_params *p, bool fill, hipStream_t stream);
-extern "C" hipError_t rb_launch_format_cigars(const rb_format_params *p, bool fill, hipStream_t stream);
-extern "C" hipError_t rb_launch_exclusive_scan(uint64_t *v, uint64_t n, uint64_t *block_sums, uint64_t *total_out, hipStream_t stream);
-extern "C" hipError_t rb_launch_make_jobs(const rb_lift_params *p, hipStream_t stream);
-extern "C" hipError_t rb_launch_liftover_stream(const rb_lift_params *p, hipStream_t stream);
-extern "C" hipError_t rb_launch_liftover_tail(const rb_lift_params *p, hipStream_t stream);
-extern "C" hipError_t rb_launch_liftover_tiles(const rb_lift_params *p, hipStream_t stream);       // k_tile.hip
-extern "C" hipError_t rb_launch_liftover_stream_list(const rb_lift_params *p, hipStream_t stream);
-extern "C" uint32_t rb_tile_max_ops(void);
-extern "C" uint32_t rb_tile_max_records(void);
 #ifndef RB_SHORT_MAX_DEFAULT
 #define RB_SHORT_MAX_DEFAULT 2048 // records of up to this many ops go through the tile kernel (profiles/r05_reclen_summary.md)
 #endif
-extern "C" hipError_t rb_launch_break_gather(const rb_lift_params *p, hipStream_t stream);
-extern "C" hipError_t rb_launch_break_declined(const rb_lift_params *p, hipStream_t stream);
-extern "C" hipError_t rb_launch_break_list_declined(const rb_lift_params *p, hipStream_t stream);
-extern "C" size_t rb_scan_block_sums_count(uint64_t n_rec);
-extern "C" hipError_t rb_launch_break_pieces(const rb_break_params *p, hipStream_t stream);
-extern "C" hipError_t rb_launch_break_place(const rb_break_params *p, hipStream_t stream);
-extern "C" hipError_t rb_launch_swap(const rb_swap_params *p, hipStream_t stream);
-extern "C" hipError_t rb_launch_overlap_split(const rb_trim_params *p, hipStream_t stream);
-extern "C" size_t rb_trim_scratch_bytes(uint32_t blocks);
-extern "C" hipError_t rb_launch_synth(uint64_t seed, uint64_t first_record, uint64_t n_rec, const uint64_t *op_off, uint32_t *ops, hipStream_t stream);
-
-struct rb_nf_params {
-    uint64_t n_reads;
-    const uint32_t *ops;
-    const uint64_t *op_off;
-    const uint8_t *seq;
-    const uint64_t *seq_off;
-    const uint32_t *l_seq;
-    const int32_t *tid;
-    const int64_t *pos;
-    const uint32_t *flag;
-    uint64_t n_regions;
-    const int32_t *rg_tid;
-    const uint64_t *rg_st, *rg_en, *out_off;
-    uint32_t *counts;
-    uint32_t *read_status;
-    rb_nucfreq_counters *counters;
-    uint64_t *end_key;
-    void *hd;
-    uint64_t *tile_off;
-    uint64_t *blk;
-    uint64_t *tile_lo, *tile_hi;
-    uint64_t max_tiles;
-    uint64_t *drop_off;
-    uint64_t *drop_bits;
-    uint64_t drop_words;
-    uint32_t *deep_list;
-    uint32_t flags;
-    void *tdesc;
-    uint32_t *wide_list;
-};
-extern "C" hipError_t rb_launch_nucfreq(const rb_nf_params *p, hipStream_t stream);
-struct rb_compact_params {
-    uint64_t n_rows;
-    rb_hit_row *rows;
-    const uint32_t *src;
-    uint64_t *off;
-    uint32_t *dst;
-    int fill;
-};
-extern "C" hipError_t rb_launch_compact_clips(const rb_compact_params *p, hipStream_t stream);
-extern "C" size_t rb_nf_tile_positions(void);
-extern "C" size_t rb_nf_scan_blocks(uint64_t n);
 
 #define RB_MAX_ARENA 256
 
@@ -378,8 +248,7 @@ static int rb_free_vmm(void *p, int device, hipError_t *err) {
     // copies, which do not go through the compute units' translation caches, read and wrote the new pages).  Addresses are not
     // scarce (a batch of 75 GB takes 2^-11 of the 47-bit range); memory is what is returned, chunk by chunk, above.
     g_va_live -= it->second.bytes;
-    if (getenv("RB_ALLOC_FREE_VA")) note(hipMemAddressFree(p, it->second.bytes)); // (the probe's switch)
-    else g_va_retired += it->second.bytes;
+    g_va_retired += it->second.bytes;
     g_vmm.erase(it);
     if (first != hipSuccess) (void)hipGetLastError();
     *err = first;
@@ -467,8 +336,8 @@ extern "C" int rb_dev_alloc(rb_ctx *ctx, size_t bytes, void **dev_ptr) {
         }
     const char *mode = getenv("RB_ALLOC_MODE");
     // (round 4: from 256 MB up, not 1 GB -- the row arena of the headline batch, 1.02e9 bytes, fell just short of the old threshold and sat
-    //  in plain hipMalloc memory beside a chunked batch; RB_ALLOC_CHUNK_MIN_MB moves the threshold for experiments)
-    static const size_t chunk_min = (size_t)(getenv("RB_ALLOC_CHUNK_MIN_MB") ? atol(getenv("RB_ALLOC_CHUNK_MIN_MB")) : 256) << 20;
+    //  in plain hipMalloc memory beside a chunked batch)
+    const size_t chunk_min = (size_t)256 << 20;
     const bool chunks = mode ? (!strcmp(mode, "scatter") || !strcmp(mode, "chunks")) : want >= chunk_min;
     if (want >= ((size_t)64 << 20) && chunks) {
         void *q = rb_alloc_vmm(ctx->device, want, mode && !strcmp(mode, "scatter"));
@@ -700,9 +569,8 @@ extern "C" int rb_dev_scan_records(rb_ctx *ctx, const rb_batch_view *b, rb_reduc
     p.list = nullptr;
     p.n_list = nullptr;
     // a batch of short records (config 4's shape: a few hundred ops each) goes through the row form, four records per wavefront, and
-    // only what that lists through the wave-per-record kernel; RB_SCAN_ROWS=0 (diagnostics): the wave-per-record kernel for everything
-    static const bool rows_off = getenv("RB_SCAN_ROWS") && atoi(getenv("RB_SCAN_ROWS")) == 0;
-    if (!rows_off && b->n_rec >= 64 && b->n_ops / b->n_rec <= RB_SCAN_ROWS_MEAN_MAX) {
+    // only what that lists through the wave-per-record kernel
+    if (b->n_rec >= 64 && b->n_ops / b->n_rec <= RB_SCAN_ROWS_MEAN_MAX) {
         if (ctx->scan_list_cap < b->n_rec) { // (grows with the largest batch seen: four bytes per record)
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             if (ctx->scan_list) hipFree(ctx->scan_list);
@@ -849,22 +717,6 @@ extern "C" int rb_plan_create(rb_ctx *ctx, uint64_t n_rec, const uint64_t *op_of
             a.swap(b);
         }
         sched = a;
-        // RB_SCHED=chunk:<N> (experiments): records in MEMORY order by chunks of N, longest first inside a chunk.  The waves that run at
-        // the same time then work on neighbouring records -- a few hundred MB of the ops array and of each output slot -- instead of
-        // on records scattered over all of them, and the four waves of a workgroup still get records of one length.
-        if (const char *e = getenv("RB_SCHED")) {
-            uint64_t N = 0;
-            if (!strncmp(e, "chunk:", 6)) N = strtoull(e + 6, nullptr, 10);
-            else if (!strcmp(e, "memory")) N = 1;
-            if (N >= 1) {
-                std::iota(sched.begin(), sched.end(), 0u);
-                if (N > 1)
-                    for (uint64_t c0 = 0; c0 < n_rec; c0 += N) {
-                        const uint64_t c1 = std::min<uint64_t>(n_rec, c0 + N);
-                        std::stable_sort(sched.begin() + c0, sched.begin() + c1, [&](uint32_t x, uint32_t y) { return key[x] > key[y]; });
-                    }
-            }
-        }
     }
     // windows grouped by contig, BED order kept inside a contig
     std::vector<uint64_t> cw_off(n_contig + 1, 0), g_st(n_win), g_en(n_win), o_st(n_win), o_en(n_win);
@@ -898,12 +750,12 @@ extern "C" int rb_plan_create(rb_ctx *ctx, uint64_t n_rec, const uint64_t *op_of
         }
     }
     // tiles of short records (k_tile.hip): rb_plan_tiles_host below.  RB_TILE=0 switches the tile kernel off, RB_SHORT_MAX=<ops> moves the
-    // line between the two kernels (experiments; RB_SCHED -- a schedule that is not sorted by length -- switches it off as well).
+    // line between the two kernels (experiments).
     std::vector<uint32_t> tiles;
     pl->stream_end = (uint32_t)n_rec;
     {
         const char *e = getenv("RB_TILE");
-        const bool on = !(e && !strcmp(e, "0")) && !getenv("RB_SCHED");
+        const bool on = !(e && !strcmp(e, "0"));
         uint64_t short_max = RB_SHORT_MAX_DEFAULT;
         if (const char *m = getenv("RB_SHORT_MAX")) short_max = strtoull(m, nullptr, 10);
         if (on && n_rec) {
@@ -998,11 +850,7 @@ extern "C" size_t rb_plan_diag_stamps_offset(const rb_plan *plan, uint64_t rows_
 
 // ops per output slot: the batch's op index space, 32 ops (one 128-byte line) of room per record (records that share a line in the
 // input must not share one in the output), a multiple of 32
-static uint64_t slot_pad() { // (experiment, RB_SLOT_PAD=<ops>: where slot 1 lies relative to slot 0 below the 2 MB of a physical chunk)
-    static const uint64_t v = [] { const char *e = getenv("RB_SLOT_PAD"); return e ? (uint64_t)strtoull(e, nullptr, 10) & ~(uint64_t)31 : 0ull; }();
-    return v;
-}
-static uint64_t slot_stride_of(uint64_t n_ops, uint64_t n_rec) { return ((n_ops + 31) & ~(uint64_t)31) + 32 * n_rec + 64 + slot_pad(); }
+static uint64_t slot_stride_of(uint64_t n_ops, uint64_t n_rec) { return ((n_ops + 31) & ~(uint64_t)31) + 32 * n_rec + 64; }
 extern "C" uint64_t rb_plan_out_capacity(const rb_plan *plan, int for_break) {
     if (!plan) return 0;
     const uint64_t slots = for_break ? std::min<uint32_t>(2u, RB_MS) : std::min<uint32_t>(plan->depth, RB_MS);
@@ -1086,7 +934,7 @@ static int lift_common(rb_ctx *ctx, const rb_plan *plan, const rb_batch_view *b,
     p.pend_list = (uint32_t *)(ws + w.pend_list);
     p.pend_count = (unsigned long long *)(ws + w.pend_count);
     // short records go through the tile kernel (k_tile.hip); the diagnostics builds keep every record on the per-record kernel
-    const bool use_tiles = plan->n_tiles != 0 && ((policy >> 8) & 0xFFF) == 0 && !getenv("RB_DEBUG_NO_TILES");
+    const bool use_tiles = plan->n_tiles != 0 && ((policy >> 8) & 0xFFF) == 0;
     p.tile_first = use_tiles ? plan->tiles : nullptr;
     p.n_tiles = use_tiles ? plan->n_tiles : 0;
     p.fb_list = (uint32_t *)(ws + w.fb_list);
@@ -1185,7 +1033,7 @@ static int lift_common(rb_ctx *ctx, const rb_plan *plan, const rb_batch_view *b,
         bp.max_size = max_size;
         // one walk of the ops: count the pieces of every record and keep their windows (tmp[]), scan the counts, move the
         // windows to their rows; a second walk only for records with more pieces than the collect pass keeps
-        bp.tmp = ws + w.bp_tmp;
+        bp.tmp = (uint2 *)(ws + w.bp_tmp);
         bp.tmp_off = (uint64_t *)(ws + w.bp_off);
         bp.tmp_cursor = (unsigned long long *)(ws + w.bp_cur);
         bp.n_arena = pick_arenas(b->n_rec);
@@ -1308,38 +1156,6 @@ extern "C" int rb_dev_overlap_split(rb_ctx *ctx, const rb_batch_view *b, const r
     return RB_OK;
 }
 
-struct rb_apply_params {
-    uint64_t n_pairs;
-    const uint32_t *left, *right;
-    const rb_pair_row *rows;
-    uint64_t *op_off;
-    rb_norm_row *norm;
-};
-struct rb_gather_params {
-    uint64_t n_rec;
-    const uint32_t *ops;
-    const uint64_t *op_off;
-    const rb_norm_row *norm;
-    uint64_t *new_off;
-    uint32_t *new_ops;
-    int fill;
-};
-struct rb_tsel_params {
-    uint64_t n_groups;
-    const uint32_t *order;
-    const uint64_t *grp_off;
-    const rb_norm_row *norm;
-    uint8_t *contained;
-    uint64_t *slot;
-    uint64_t *has;
-    uint32_t *cand;
-    uint64_t out_base;
-    uint32_t *left, *right;
-    uint64_t *pair_out_off;
-    rb_trim_pass *pass;
-};
-extern "C" hipError_t rb_launch_trim_select(const rb_tsel_params *p, uint64_t *block_sums, hipStream_t stream);
-extern "C" hipError_t rb_launch_trim_check(const rb_pair_row *rows, uint64_t n_pairs, rb_trim_pass *pass, hipStream_t stream);
 // scratch of rb_dev_trim_select: [slot (n_groups + 2) u64][has (n_groups + 2) u64][cand 2 n_groups u32][block sums of the scans]
 extern "C" size_t rb_trim_select_scratch_bytes(uint64_t n_groups) {
     return 2 * (((n_groups + 2) * 8 + 255) & ~(size_t)255) + ((2 * n_groups * 4 + 255) & ~(size_t)255) + (rb_scan_block_sums_count(n_groups) + 4) * 8 + 256;
@@ -1370,8 +1186,6 @@ extern "C" int rb_dev_trim_check(rb_ctx *ctx, uint64_t n_pairs, const rb_pair_ro
     HIPCHK(ctx, rb_launch_trim_check(rows, n_pairs, pass, ctx->stream));
     return RB_OK;
 }
-extern "C" hipError_t rb_launch_apply_pairs(const rb_apply_params *p, hipStream_t stream);
-extern "C" hipError_t rb_launch_gather_records(const rb_gather_params *p, hipStream_t stream);
 extern "C" int rb_dev_apply_pairs(rb_ctx *ctx, uint64_t n_pairs, const uint32_t *left, const uint32_t *right, const rb_pair_row *rows,
                                   uint64_t *op_off, rb_norm_row *norm_rows) {
     if (!ctx || (n_pairs && (!left || !right || !rows || !op_off || !norm_rows))) return RB_E_INVALID;
@@ -1544,6 +1358,49 @@ static void rb_lap(const char *what, double &t) {
     if (on) fprintf(stderr, "[rb timing]     %-24s %.3f s\n", what, n - t);
     t = n;
 }
+// Plan, workspace, rows and clips for one liftover / break-paf call on a device-resident batch: the clip kernels are run again with
+// larger outputs while the counters say they overflowed (at most 6 attempts).  The rows and clips of the last attempt go with the batch
+// (*d_rows, *d_out); the plan and the workspace are freed here.
+static int lift_sized(rb_ctx *ctx, DevBatch &b, const uint64_t *op_off, const uint32_t *contig, uint64_t n_win, const uint32_t *w_contig,
+                      const uint64_t *w_st, const uint64_t *w_en, const rb_norm_row *d_norm, bool is_break, uint32_t max_size, int policy,
+                      rb_hit_row **d_rows, uint32_t **d_out, rb_counters *hc, double &tl) {
+    memset(hc, 0, sizeof *hc);
+    rb_plan *plan = nullptr;
+    int rc = rb_plan_create(ctx, b.v.n_rec, op_off, contig, n_win, w_contig, w_st, w_en, &plan);
+    if (rc) return rc;
+    rb_lap("plan", tl);
+    rb_counters *d_cnt = nullptr;
+    rc = b.alloc(1, &d_cnt);
+    const bool desc = (policy & RB_LIFT_DESCRIPTORS) != 0;
+    uint64_t rows_cap = 16 * b.v.n_rec + n_win + 1024; // a first guess; the counters say what is needed if it is short
+    uint64_t out_cap = (desc ? b.v.n_ops / 4 : rb_plan_out_capacity(plan, is_break ? 1 : 0)) + 16 * rows_cap + 4096;
+    void *ws = nullptr;
+    rb_hit_row *rows = nullptr;
+    uint32_t *out = nullptr;
+    for (int attempt = 0; !rc && attempt < 6; attempt++) {
+        for (void *q : {ws, (void *)rows, (void *)out})
+            if (q) (void)rb_dev_free(ctx, q);
+        ws = nullptr, rows = nullptr, out = nullptr;
+        rc = rb_dev_alloc(ctx, rb_plan_workspace_bytes(plan, rows_cap), &ws);
+        if (!rc) rc = rb_dev_alloc(ctx, (rows_cap + 1) * sizeof(rb_hit_row), (void **)&rows);
+        if (!rc) rc = rb_dev_alloc(ctx, (out_cap + 4) * 4, (void **)&out);
+        if (!rc)
+            rc = is_break ? rb_dev_break(ctx, plan, &b.v, d_norm, max_size, policy | (desc ? 0 : RB_BREAK_ONE_WALK), ws, rows, rows_cap, out, out_cap, d_cnt)
+                          : rb_dev_liftover(ctx, plan, &b.v, d_norm, policy, ws, rows, rows_cap, out, out_cap, d_cnt);
+        if (!rc) rc = rb_dev_download(ctx, hc, d_cnt, sizeof *hc);
+        if (rc || !hc->overflow) break;
+        rows_cap = std::max<uint64_t>(rows_cap, hc->n_hits + 16);
+        out_cap = std::max<uint64_t>(out_cap * 2, hc->out_ops_needed + hc->out_ops_needed / 4 + 4096 + 4 * rows_cap);
+    }
+    if (!rc && hc->overflow) rc = RB_E_CAPACITY;
+    if (ws) (void)rb_dev_free(ctx, ws);
+    rb_plan_destroy(plan);
+    for (void *q : {(void *)rows, (void *)out})
+        if (q) b.owned.push_back(q);
+    *d_rows = rows, *d_out = out;
+    rb_lap("alloc + kernels", tl);
+    return rc;
+}
 static int host_lift(rb_ctx *ctx, bool is_break, uint32_t max_size, uint64_t n_rec, const uint32_t *ops, const uint64_t *op_off,
                      const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand,
                      const uint32_t *contig, uint64_t n_win, const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en,
@@ -1572,53 +1429,10 @@ static int host_lift(rb_ctx *ctx, bool is_break, uint32_t max_size, uint64_t n_r
         if (norm_out && (rc = rb_dev_download(ctx, norm_out, d_norm, n_rec * sizeof(rb_norm_row)))) return rc;
         rb_lap("scan_records + norm D2H", tl);
     }
-    rb_plan *plan = nullptr;
-    if ((rc = rb_plan_create(ctx, n_rec, op_off, contig, n_win, w_contig, w_st, w_en, &plan))) return rc;
-    rb_lap("plan", tl);
-    rb_counters *d_cnt = nullptr;
-    if ((rc = b.alloc(1, &d_cnt))) {
-        rb_plan_destroy(plan);
-        return rc;
-    }
-    const uint64_t n_ops = n_rec ? op_off[n_rec] : 0;
-    uint64_t rows_cap = 16 * n_rec + n_win + 1024; // a first guess; the counters say what is needed if it is short
-    uint64_t out_cap = ((policy & RB_LIFT_DESCRIPTORS) ? n_ops / 4 : rb_plan_out_capacity(plan, is_break ? 1 : 0)) + 16 * rows_cap + 4096;
     rb_counters hc;
-    memset(&hc, 0, sizeof hc);
-    void *ws = nullptr;
     rb_hit_row *d_rows = nullptr;
     uint32_t *d_out = nullptr;
-    bool one_walk = is_break && !(policy & RB_LIFT_DESCRIPTORS) && !getenv("RB_BREAK_TWO_WALK"); // (the env: diagnostics)
-    for (int attempt = 0; attempt < 6; attempt++) {
-        if (ws) (void)rb_dev_free(ctx, ws);
-        if (d_rows) (void)rb_dev_free(ctx, d_rows);
-        if (d_out) (void)rb_dev_free(ctx, d_out);
-        ws = nullptr;
-        d_rows = nullptr;
-        d_out = nullptr;
-        rc = rb_dev_alloc(ctx, rb_plan_workspace_bytes(plan, rows_cap), &ws);
-        if (!rc) rc = rb_dev_alloc(ctx, (rows_cap + 1) * sizeof(rb_hit_row), (void **)&d_rows);
-        if (!rc) rc = rb_dev_alloc(ctx, (out_cap + 4) * 4, (void **)&d_out);
-        if (rc) break;
-        rc = is_break ? rb_dev_break(ctx, plan, &b.v, d_norm, max_size, policy | (one_walk ? RB_BREAK_ONE_WALK : 0), ws, d_rows, rows_cap, d_out,
-                                     out_cap, d_cnt)
-                      : rb_dev_liftover(ctx, plan, &b.v, d_norm, policy, ws, d_rows, rows_cap, d_out, out_cap, d_cnt);
-        if (rc) break;
-        rc = rb_dev_download(ctx, &hc, d_cnt, sizeof hc);
-        if (rc) break;
-        if (one_walk && hc.redo_two_walk) { // something the one-walk path does not take: the same buffers, the two-walk path
-            one_walk = false;
-            attempt--;
-            rc = RB_E_CAPACITY;
-            continue;
-        }
-        if (!hc.overflow) break;
-        rows_cap = std::max<uint64_t>(rows_cap, hc.n_hits + 16);
-        out_cap = std::max<uint64_t>(out_cap * 2, hc.out_ops_needed + hc.out_ops_needed / 4 + 4096 + 4 * rows_cap);
-        rc = RB_E_CAPACITY;
-    }
-    if (!rc && hc.overflow) rc = RB_E_CAPACITY;
-    rb_lap("alloc + kernels", tl);
+    rc = lift_sized(ctx, b, op_off, contig, n_win, w_contig, w_st, w_en, d_norm, is_break, max_size, policy, &d_rows, &d_out, &hc, tl);
     if (!rc && fused && norm_out) rc = rb_dev_download(ctx, norm_out, d_norm, n_rec * sizeof(rb_norm_row));
     if (!rc) {
         // the clips packed side by side in row order ON THE DEVICE (the slots of out_ops are as large as the batch: only the clips
@@ -1653,10 +1467,6 @@ static int host_lift(rb_ctx *ctx, bool is_break, uint32_t max_size, uint64_t n_r
         if (counters) *counters = hc;
         rb_lap("D2H + compact", tl);
     }
-    if (ws) (void)rb_dev_free(ctx, ws);
-    if (d_rows) (void)rb_dev_free(ctx, d_rows);
-    if (d_out) (void)rb_dev_free(ctx, d_out);
-    rb_plan_destroy(plan);
     if (rc) {
         free(*rows);
         free(*out_ops);
@@ -1839,50 +1649,11 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
     if (reduce_out && (rc = rb_dev_download(ctx, reduce_out, d_red, n_rec * sizeof(rb_reduce_row)))) return rc;
     rb_lap("scan_records + rows D2H", tl);
     if (scan_only) return RB_OK;
-    rb_plan *plan = nullptr;
-    if ((rc = rb_plan_create(ctx, n_rec, op_off.data(), contig, n_win, w_contig, w_st, w_en, &plan))) return rc;
-    rb_counters *d_cnt = nullptr;
-    if ((rc = b.alloc(1, &d_cnt))) {
-        rb_plan_destroy(plan);
-        return rc;
-    }
-    policy |= RB_LIFT_DESCRIPTORS;
-    uint64_t rows_cap = 16 * n_rec + n_win + 1024;
-    uint64_t out_cap = b.v.n_ops / 4 + 16 * rows_cap + 4096;
     rb_counters hc;
-    memset(&hc, 0, sizeof hc);
-    void *ws = nullptr;
     rb_hit_row *d_rows = nullptr;
     uint32_t *d_out = nullptr;
-    bool one_walk = is_break && !(policy & RB_LIFT_DESCRIPTORS) && !getenv("RB_BREAK_TWO_WALK"); // (the env: diagnostics)
-    for (int attempt = 0; attempt < 6; attempt++) {
-        if (ws) (void)rb_dev_free(ctx, ws);
-        if (d_rows) (void)rb_dev_free(ctx, d_rows);
-        if (d_out) (void)rb_dev_free(ctx, d_out);
-        ws = nullptr, d_rows = nullptr, d_out = nullptr;
-        rc = rb_dev_alloc(ctx, rb_plan_workspace_bytes(plan, rows_cap), &ws);
-        if (!rc) rc = rb_dev_alloc(ctx, (rows_cap + 1) * sizeof(rb_hit_row), (void **)&d_rows);
-        if (!rc) rc = rb_dev_alloc(ctx, (out_cap + 4) * 4, (void **)&d_out);
-        if (rc) break;
-        rc = is_break ? rb_dev_break(ctx, plan, &b.v, d_norm, max_size, policy | (one_walk ? RB_BREAK_ONE_WALK : 0), ws, d_rows, rows_cap, d_out,
-                                     out_cap, d_cnt)
-                      : rb_dev_liftover(ctx, plan, &b.v, d_norm, policy, ws, d_rows, rows_cap, d_out, out_cap, d_cnt);
-        if (rc) break;
-        rc = rb_dev_download(ctx, &hc, d_cnt, sizeof hc);
-        if (rc) break;
-        if (one_walk && hc.redo_two_walk) { // something the one-walk path does not take: the same buffers, the two-walk path
-            one_walk = false;
-            attempt--;
-            rc = RB_E_CAPACITY;
-            continue;
-        }
-        if (!hc.overflow) break;
-        rows_cap = std::max<uint64_t>(rows_cap, hc.n_hits + 16);
-        out_cap = std::max<uint64_t>(out_cap * 2, hc.out_ops_needed + hc.out_ops_needed / 4 + 4096 + 4 * rows_cap);
-        rc = RB_E_CAPACITY;
-    }
-    if (!rc && hc.overflow) rc = RB_E_CAPACITY;
-    rb_lap("plan + clip kernels", tl);
+    rc = lift_sized(ctx, b, op_off.data(), contig, n_win, w_contig, w_st, w_en, d_norm, is_break, max_size, policy | RB_LIFT_DESCRIPTORS,
+                    &d_rows, &d_out, &hc, tl);
     // ---- rows to the host, clip items back to the device, text out ----
     const uint64_t nr = hc.n_hits;
     std::vector<uint32_t> desc;
@@ -1936,21 +1707,6 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
             else rb_advise_huge(*row_text, (size_t)bytes);
         }
         if (!rc && bytes) rc = rb_dev_download(ctx, *row_text, d_rtext, (size_t)bytes);
-        if (!rc && bytes && getenv("RB_DEBUG_TEXT_CHECK")) { // diagnostics: CIGAR text holds no NUL byte
-            const uint8_t *z = (const uint8_t *)memchr(*row_text, 0, (size_t)bytes);
-            if (z) {
-                const uint64_t at = (uint64_t)(z - *row_text);
-                uint64_t row = 0;
-                while (row + 1 < nr && (*row_text_off)[row + 1] <= at) row++;
-                fprintf(stderr, "[rb text check] NUL at byte %llu of %llu (mod 32 MB: %llu, mod 16: %llu), row %llu of %llu, row text [%llu, %llu), item first %llu count %u\n",
-                        (unsigned long long)at, (unsigned long long)bytes, (unsigned long long)(at % RB_PIN_CHUNK), (unsigned long long)(at & 15),
-                        (unsigned long long)row, (unsigned long long)nr, (unsigned long long)(*row_text_off)[row], (unsigned long long)(*row_text_off)[row + 1],
-                        (unsigned long long)0, 0u);
-                std::vector<uint8_t> again((size_t)bytes);
-                (void)hipMemcpy(again.data(), d_rtext, (size_t)bytes, hipMemcpyDeviceToHost);
-                fprintf(stderr, "[rb text check] plain hipMemcpy of the same buffer: byte is %u (device %s)\n", again[(size_t)at], again[(size_t)at] ? "has the text: the staged download lost it" : "holds the NUL too: the kernel did not write it");
-            }
-        }
         rb_lap("format cigars + text D2H", tl);
     }
     if (!rc) {
@@ -1962,10 +1718,6 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
         free(*row_text);
         *rows = nullptr, *row_text_off = nullptr, *row_text = nullptr;
     }
-    if (ws) (void)rb_dev_free(ctx, ws);
-    if (d_rows) (void)rb_dev_free(ctx, d_rows);
-    if (d_out) (void)rb_dev_free(ctx, d_out);
-    rb_plan_destroy(plan);
     return rc;
 }
 
@@ -2096,16 +1848,6 @@ extern "C" int rb_dev_synth_fill_ops(rb_ctx *ctx, uint64_t seed, uint64_t first_
 }
 
 // ---- verification aid: digest of rows + clipped cigars ----------------------------------------------
-struct rb_digest_params {
-    const uint32_t *ops;
-    const uint64_t *op_off;
-    const rb_hit_row *rows;
-    uint64_t n_rows;
-    const uint32_t *out_ops;
-    uint64_t row_base, rec_base;
-    unsigned long long *digest;
-};
-extern "C" hipError_t rb_launch_digest_rows(const rb_digest_params *p, hipStream_t stream);
 extern "C" int rb_dev_digest_rows(rb_ctx *ctx, const rb_batch_view *batch, const rb_hit_row *rows, uint64_t n_rows, const uint32_t *out_ops,
                                   uint64_t row_base, uint64_t rec_base, uint64_t *digest) {
     if (!ctx || !batch || !digest || (n_rows && (!rows || !out_ops))) return RB_E_INVALID;
@@ -2123,7 +1865,6 @@ extern "C" int rb_dev_digest_rows(rb_ctx *ctx, const rb_batch_view *batch, const
 }
 
 // ---- the box: what this GPU moves at the clip kernel's memory mix, and the clock it holds meanwhile (diagnostics for bench.py) ----
-extern "C" hipError_t rb_launch_box_probe(const void *src, void *d0, void *d1, uint64_t n_stretch, uint32_t *stamps, int scatter, hipStream_t stream);
 extern "C" int rb_dev_box_probe(rb_ctx *ctx, const void *src, uint64_t src_bytes, void *dst0, void *dst1, int reps, int scatter, double *ms_out, double *mhz_out) {
     if (!ctx || !src || !dst0 || !dst1 || !ms_out || reps < 1) return RB_E_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2312,14 +2053,13 @@ extern "C" int rb_dev_nucfreq(rb_ctx *ctx, const rb_reads_view *reads, uint64_t 
     p.n_regions = n_regions;
     p.rg_tid = rg_tid, p.rg_st = rg_st, p.rg_en = rg_en, p.out_off = out_off;
     p.counts = counts, p.read_status = read_status, p.counters = counters;
-    p.end_key = (uint64_t *)(w + L.end_key), p.hd = (void *)(w + L.rd_end), p.tile_off = (uint64_t *)(w + L.tile_off);
+    p.end_key = (uint64_t *)(w + L.end_key), p.hd = (nf_read *)(w + L.rd_end), p.tile_off = (uint64_t *)(w + L.tile_off);
     p.blk = (uint64_t *)(w + L.blk), p.tile_lo = (uint64_t *)(w + L.tile_lo), p.tile_hi = (uint64_t *)(w + L.tile_hi);
     p.max_tiles = L.max_tiles;
     p.drop_off = (uint64_t *)(w + L.drop_off), p.deep_list = (uint32_t *)(w + L.deep_list);
     p.drop_bits = (uint64_t *)(w + L.drop_pool) + 1, p.drop_words = L.drop_words;
-    static const bool all_atomic = getenv("RB_DEBUG_NF_ATOMIC") != nullptr; // (diagnostic: every tile through the LDS-atomic kernel)
-    p.flags = all_atomic ? 1u : 0u;
-    p.tdesc = (void *)(w + L.tdesc);
+    p.flags = 0;
+    p.tdesc = (nf_tdesc *)(w + L.tdesc);
     p.wide_list = (uint32_t *)(w + L.wide_list);
     HIPCHK(ctx, rb_fill_async(p.drop_bits - 1, 0, 8, ctx->stream));
     HIPCHK(ctx, rb_fill_async(p.deep_list + n_regions, 0, 8, ctx->stream)); // (how many deep regions; can the cap be reached at all)

@@ -24,9 +24,7 @@
 //                       the previous clip of their slot, and clips of windows that are not sorted, are listed and
 //                       copied by rb_k_copy_clips into the arenas behind the slots.
 //   rb_k_liftover_generic_wave  one wavefront per hit the streaming kernel declines: three passes over the record's
-//                       ops (boundaries, merge of adjacent runs through LDS, emission); rb_k_liftover_generic, the
-//                       serial one-thread-per-hit form, stays as the diagnostic reference (RB_DEBUG_GENERIC_SERIAL).
-//                       They take every case the streaming kernel declines
+//                       ops (boundaries, merge of adjacent runs through LDS, emission).  It takes every case the streaming kernel declines
 //                       (irregular CIGARs: N/S/H/P, zero lengths, adjacent ops of one type that must
 //                       merge (paf.rs:602-620); the legacy binary-search policy when the duplicate
 //                       choice matters; look-aheads / look-backs longer than RB_WALK_MAX ops).
@@ -34,6 +32,7 @@
 // Roofline: HBM.  Algorithmic bytes: 4 B per input op + 48 B per record + 88 B per hit + 4 B per
 // emitted op.  No MFMA: integer / index work only.
 #include "rb_lift.h"
+#include "rb_launch.h"
 #include <type_traits>
 #include <algorithm>
 
@@ -1315,7 +1314,7 @@ __global__ __launch_bounds__(256) void rb_k_copy_clips(rb_lift_params p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// generic kernel: one thread per hit, serial, fully general (unit semantics evaluated in op space)
+// generic hit, one thread, serial, fully general (unit semantics evaluated in op space): what the wave kernel below hands unsorted arrays to
 // ------------------------------------------------------------------------------------------------
 struct rb_gwalk {
     const uint32_t *ops;
@@ -1386,7 +1385,7 @@ __device__ bool rb_bsearch_units(const uint32_t *ops, uint32_t n, uint64_t t_st,
     return false;
 }
 
-// one hit, one thread, serial (the general case of the general case: also what the wave kernel below hands unsorted arrays to)
+// one hit, one thread, serial (the general case of the general case)
 __device__ void rb_generic_serial_hit(const rb_lift_params &p, const uint64_t g) {
     for (int once = 0; once < 1; once++) {
         const uint64_t hrow = p.gen_list[g];
@@ -1608,10 +1607,6 @@ __device__ void rb_generic_serial_hit(const rb_lift_params &p, const uint64_t g)
         }
         *row = w;
     }
-}
-__global__ __launch_bounds__(256) void rb_k_liftover_generic(rb_lift_params p) { // (diagnostics: RB_DEBUG_GENERIC_SERIAL)
-    const uint64_t n_gen = p.counters->n_generic;
-    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n_gen; g += (uint64_t)gridDim.x * blockDim.x) rb_generic_serial_hit(p, g);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2225,7 +2220,6 @@ extern "C" hipError_t rb_launch_break_declined(const rb_lift_params *p, hipStrea
     hipLaunchKernelGGL(rb_k_finish, dim3(1), dim3(64), 0, stream, *p);
     return hipGetLastError();
 }
-extern "C" hipError_t rb_launch_exclusive_scan(uint64_t *v, uint64_t n, uint64_t *block_sums, uint64_t *total_out, hipStream_t stream);
 extern "C" hipError_t rb_launch_count_and_scan(const rb_lift_params *p, uint64_t *block_sums, bool do_count, hipStream_t stream) {
     if (p->n_rec == 0) return hipSuccess;
     if (do_count) {
@@ -2252,29 +2246,22 @@ extern "C" hipError_t rb_launch_make_jobs(const rb_lift_params *p, hipStream_t s
 extern "C" hipError_t rb_launch_liftover_stream(const rb_lift_params *p, hipStream_t stream) {
     if (p->n_rec == 0 || p->wave_end <= p->wave0) return hipSuccess;
     const unsigned blocks = (unsigned)(((uint64_t)(p->wave_end - p->wave0) + 3) / 4);
-    // diagnostics: RB_DEBUG_DYN_LDS=<bytes> adds unused dynamic LDS to lower the occupancy
-    static const unsigned dyn = getenv("RB_DEBUG_DYN_LDS") ? (unsigned)atoi(getenv("RB_DEBUG_DYN_LDS")) : 0u;
     if (p->debug_skip) { // diagnostics only (bench.py --debug-skip, the box block's clock stamps)
         if (!p->brk_mode) {
-            hipLaunchKernelGGL(rb_k_liftover_stream_diag, dim3(blocks), dim3(256), dyn, stream, *p);
+            hipLaunchKernelGGL(rb_k_liftover_stream_diag, dim3(blocks), dim3(256), 0, stream, *p);
             return hipGetLastError();
         }
     }
-    if (p->brk_mode) hipLaunchKernelGGL(rb_k_liftover_stream_brk, dim3(blocks), dim3(256), dyn, stream, *p);
-    else hipLaunchKernelGGL(rb_k_liftover_stream, dim3(blocks), dim3(256), dyn, stream, *p);
+    if (p->brk_mode) hipLaunchKernelGGL(rb_k_liftover_stream_brk, dim3(blocks), dim3(256), 0, stream, *p);
+    else hipLaunchKernelGGL(rb_k_liftover_stream, dim3(blocks), dim3(256), 0, stream, *p);
     return hipGetLastError();
 }
 extern "C" hipError_t rb_launch_liftover_tail(const rb_lift_params *p, hipStream_t stream) {
     if (p->n_rec == 0) return hipSuccess;
     hipLaunchKernelGGL(rb_k_copy_clips, dim3(2048), dim3(256), 0, stream, *p);
-    static const bool serial_generic = getenv("RB_DEBUG_GENERIC_SERIAL") != nullptr; // diagnostics: one thread per hit, as in round 1
-    if (serial_generic) {
-        hipLaunchKernelGGL(rb_k_liftover_generic, dim3(1024), dim3(256), 0, stream, *p);
-    } else {
-        if (p->gen_cp) hipLaunchKernelGGL(rb_k_generic_checkpoints, dim3(2048), dim3(256), 0, stream, *p);
-        hipLaunchKernelGGL(rb_k_generic_jobs, dim3(1024), dim3(256), 0, stream, *p);
-        hipLaunchKernelGGL(rb_k_liftover_generic_wave, dim3(2048), dim3(256), 0, stream, *p);
-    }
+    if (p->gen_cp) hipLaunchKernelGGL(rb_k_generic_checkpoints, dim3(2048), dim3(256), 0, stream, *p);
+    hipLaunchKernelGGL(rb_k_generic_jobs, dim3(1024), dim3(256), 0, stream, *p);
+    hipLaunchKernelGGL(rb_k_liftover_generic_wave, dim3(2048), dim3(256), 0, stream, *p);
     hipLaunchKernelGGL(rb_k_finish, dim3(1), dim3(64), 0, stream, *p);
     return hipGetLastError();
 }

@@ -1,5 +1,6 @@
 // k_misc.hip -- break-paf piece enumeration, invert (swap), synthetic workload fill (gfx950).
 #include "rb_device.h"
+#include "rb_launch.h"
 #include <algorithm>
 #include "synth.h"
 
@@ -13,28 +14,6 @@
 // One wavefront per record, streaming; a prefix-sum (ref offsets, piece ordinals) and a prefix-max
 // (pre) per 256-op step.  Run twice: count, then fill after the exclusive scan of the counts.
 // ------------------------------------------------------------------------------------------------
-struct rb_break_params {
-    uint64_t n_rec;
-    const uint32_t *ops;
-    const uint64_t *op_off;
-    const rb_norm_row *norm;
-    const uint32_t *sched;
-    uint64_t *hit_off;
-    uint64_t *x_st, *x_en;
-    uint64_t rows_cap;
-    uint32_t max_size;
-    int fill; // 0: count pieces; 1: write the windows of every record (or, with redo_only, of the records the collect pass gave up on);
-              // 2 (collect): count AND keep the windows, in LDS while the record streams, then in tmp[] at a slot from tmp_cursor
-    int redo_only;
-    uint2 *tmp;                    // [rows_cap] (start, end) of a piece relative to the record's t_st
-    uint64_t *tmp_off;             // [n_rec] where the record's pieces sit in tmp[]; ~0 = not kept (more than RB_BP_CAP pieces, or no room)
-    unsigned long long *tmp_cursor; // one bump cursor per arena, 128 bytes apart (a single cursor would serialise every record at one L2 line)
-    uint32_t n_arena;
-    uint64_t arena_cap;             // slots of tmp[] per arena
-    // list mode (break-paf in one walk: the records its clip kernel declined): wave w takes record list[w], w < *n_list
-    const uint32_t *list;
-    const unsigned long long *n_list;
-};
 #define RB_BP_CAP 512 // pieces of one record kept in LDS by the collect pass
 
 __device__ __forceinline__ uint32_t rb_umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
@@ -264,13 +243,6 @@ extern "C" hipError_t rb_launch_break_place(const rb_break_params *p, hipStream_
 // ------------------------------------------------------------------------------------------------
 // invert: cigar_swap_target_query (paf.rs:1050-1065): I <-> D, reversed when the strand is '-'
 // ------------------------------------------------------------------------------------------------
-struct rb_swap_params {
-    uint64_t n_rec;
-    const uint32_t *ops;
-    const uint64_t *op_off;
-    const uint8_t *strand;
-    uint32_t *out_ops;
-};
 __global__ __launch_bounds__(256) void rb_k_swap(rb_swap_params p) {
     const uint64_t wave = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (wave >= p.n_rec) return;
@@ -317,15 +289,6 @@ extern "C" hipError_t rb_launch_synth(uint64_t seed, uint64_t first_record, uint
 // verification aid: order-sensitive digest of hit rows and the clipped CIGARs they point at
 // (include/rustybam_amd.h, rb_dev_digest_rows).  One wavefront per row.
 // ------------------------------------------------------------------------------------------------
-struct rb_digest_params {
-    const uint32_t *ops;     // the batch's packed ops (descriptor rows are expanded through them)
-    const uint64_t *op_off;
-    const rb_hit_row *rows;
-    uint64_t n_rows;
-    const uint32_t *out_ops;
-    uint64_t row_base, rec_base;
-    unsigned long long *digest;
-};
 __global__ __launch_bounds__(256) void rb_k_digest_rows(rb_digest_params p) {
     __shared__ unsigned long long part[4];
     const uint32_t wib = threadIdx.x >> 6;
@@ -395,14 +358,6 @@ extern "C" hipError_t rb_launch_digest_rows(const rb_digest_params *p, hipStream
 
 // ---- clips of a finished clip call, packed side by side in row order (host-buffer callers: the slots of out_ops mirror the input's op
 //      positions and are as large as the batch; what goes over PCIe is the clips alone) ----------------------------------------------
-struct rb_compact_params {
-    uint64_t n_rows;
-    rb_hit_row *rows;
-    const uint32_t *src; // out_ops of the clip call
-    uint64_t *off;       // [n_rows + 1] words per row, then their exclusive prefix
-    uint32_t *dst;
-    int fill;
-};
 __device__ __forceinline__ uint64_t rb_row_words(const rb_hit_row &h) {
     return h.status != RB_ST_OK ? 0ull : ((h.flags & RB_HIT_DESCRIPTOR) ? 4ull : (uint64_t)h.out_n);
 }

@@ -26,6 +26,7 @@
 // HBM traffic: each read's packed bases once per tile it overlaps (4 bits / base), its CIGAR likewise, 16 B written per
 // position.  Bound: HBM (the counters never leave LDS).
 #include "rb_device.h"
+#include "rb_launch.h"
 #include <algorithm>
 
 #ifndef NF_TILE
@@ -39,40 +40,6 @@
 #define NF_WAVES (NF_THREADS / 64)
 #define NF_LANE_OPS 4u // reads with at most this many ops are walked by one lane each where a tile is crowded
 #define NF_PLP_MASK (0x4u | 0x100u | 0x200u | 0x400u) // htslib BAM_DEF_MASK: UNMAP | SECONDARY | QCFAIL | DUP
-
-struct rb_nf_params {
-    uint64_t n_reads;
-    const uint32_t *ops;
-    const uint64_t *op_off;
-    const uint8_t *seq;
-    const uint64_t *seq_off;
-    const uint32_t *l_seq;
-    const int32_t *tid;
-    const int64_t *pos;
-    const uint32_t *flag;
-    uint64_t n_regions;
-    const int32_t *rg_tid;
-    const uint64_t *rg_st, *rg_en, *out_off;
-    uint32_t *counts;
-    uint32_t *read_status;
-    rb_nucfreq_counters *counters;
-    // workspace
-    uint64_t *end_key;  // [n_reads] tid << 32 | end, then its inclusive prefix maximum
-    struct nf_read *hd; // [n_reads] what the tile kernel needs of a read, in one 48-byte record
-    uint64_t *tile_off; // [n_regions + 1] exclusive prefix of tiles per region
-    uint64_t *blk;      // block partials of the scans
-    uint64_t *tile_lo, *tile_hi; // [max_tiles] reads that can overlap the tile
-    uint64_t max_tiles;
-    // htslib's cap on buffered reads (rb_k_nf_admit): per region the bit offset of its dropped-read bitmap in drop_bits (~0: none)
-    uint64_t *drop_off;   // [n_regions]
-    uint64_t *drop_bits;  // pool of drop_words 64-bit words; drop_bits[-1] is the pool's cursor
-    uint64_t drop_words;
-    uint32_t *deep_list;  // [n_regions + 1] regions whose fetch holds more reads than the cap; [n_regions] = how many
-    uint32_t flags;       // bit 0: 16-bit counters for every tile (diagnostic)
-    struct nf_tdesc *tdesc; // [max_tiles] what a workgroup needs to know about a tile, in one 64-byte record (rb_k_nf_tile_desc)
-    uint32_t *wide_list;    // [max_tiles + 2] the tiles of the two builds that walk lists (rb_k_nf_tile_desc): [0] = how many of kind 2, then which,
-                            // upwards from [1]; [max_tiles + 1] = how many of kind 0, then which, downwards from [max_tiles]
-};
 
 // one read as the tile kernel sees it: a single 48-byte record (one scalar load) instead of eight arrays
 struct __attribute__((aligned(16))) nf_read {
@@ -1057,9 +1024,6 @@ __global__ __launch_bounds__(NF_THREADS) __attribute__((amdgpu_waves_per_eu(D8 ?
 
 extern "C" size_t rb_nf_tile_positions(void) { return NF_TILE; }
 extern "C" size_t rb_nf_scan_blocks(uint64_t n) { return (size_t)((n + NF_SCAN_PER_BLOCK - 1) / NF_SCAN_PER_BLOCK); }
-
-extern "C" hipError_t rb_launch_exclusive_scan(uint64_t *v, uint64_t n, uint64_t *block_sums, uint64_t *total_out, hipStream_t stream);
-extern "C" hipError_t rb_fill_async(void *dst, int value, size_t bytes, hipStream_t stream);
 
 extern "C" hipError_t rb_launch_nucfreq(const rb_nf_params *pp, hipStream_t stream) {
     const rb_nf_params p = *pp;

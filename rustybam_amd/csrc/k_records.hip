@@ -10,21 +10,9 @@
 //                    check_integrity().unwrap() outcome at :782.
 // Roofline: HBM read, 4 B per op + 48 B header per record; 128 B of rows written per record.
 #include "rb_device.h"
+#include "rb_launch.h"
 #include <algorithm>
 #include <type_traits>
-
-struct rb_scan_params {
-    uint64_t n_rec;
-    const uint32_t *ops;
-    const uint64_t *op_off;
-    const uint64_t *t_st, *t_en, *q_st, *q_en;
-    const uint8_t *strand;
-    rb_reduce_row *reduce_rows;
-    rb_norm_row *norm_rows;
-    // list mode (fused liftover): only the records list[0 .. *n_list) are scanned
-    const uint32_t *list;
-    const uint64_t *n_list;
-};
 
 // remove_trailing_indels (paf.rs:656-783) needs only the runs of I/D ops at the two ends of a record: how many ops go,
 // how many reference / query bases they hold, and the shifted coordinates (with the quirks at :668-701 and the strand

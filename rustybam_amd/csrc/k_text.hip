@@ -19,34 +19,11 @@
 // Roofline: HBM (byte work, no MFMA).  Algorithmic bytes: parse = text bytes read twice + 4 B per op written;
 // format = 4 B per op read twice + text bytes written.
 #include "rb_device.h"
+#include "rb_launch.h"
 
 #ifndef RB_PARSE_STOP
 #define RB_PARSE_STOP 0 // diagnostics (timing only): 1 = the fill pass of the parser stops behind the values of a step, 2 = behind the ops in LDS
 #endif
-
-struct rb_parse_params {
-    uint64_t n_rec;
-    const uint8_t *text;      // all CIGAR strings, any layout
-    const uint64_t *text_off; // [n_rec + 1] record r's string is text[text_off[r] .. text_end[r])
-    const uint64_t *text_end; // [n_rec] (NULL: strings are back to back, end = text_off[r + 1])
-    uint64_t *op_off;         // [n_rec + 1] counts (count pass) / offsets (fill pass)
-    uint32_t *ops;
-    uint64_t ops_cap;
-    uint8_t *status;          // [n_rec] RB_TEXT_*
-};
-struct rb_format_params {
-    uint64_t n_items;
-    const uint32_t *ops;
-    const uint32_t *ops_alt;   // second source: items whose first[] has bit 63 set index this array (NULL if unused)
-    const uint64_t *first;     // [n_items] index of the item's first op in ops[] (bit 63: in ops_alt[])
-    const uint32_t *count;     // [n_items] ops in the item (0 = empty text)
-    const uint32_t *first_len; // [n_items] or NULL: != 0 replaces the length of the first op
-    const uint32_t *last_len;  // [n_items] or NULL: != 0 replaces the length of the last op; a one-op item with both keeps first + last - len
-    uint64_t *text_off;        // [n_items + 1] counts / offsets
-    uint8_t *text;
-    uint64_t text_cap;
-    int plain_ops;             // != 0: the items of ops[] hold no continuation words (a batch the device parsed: rb_k_parse_cigars makes none)
-};
 
 // op character -> code (MIDNSHP=X -> 0..8), 255 = not an op.  Branch-free: the nine characters lie in '=' (61) .. 'X' (88),
 // so the code is a nibble of a packed table indexed by c - 61 (15 = not an op).

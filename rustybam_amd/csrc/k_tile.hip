@@ -27,6 +27,7 @@
 // Results are those of the per-record kernel (same rows, same clips; only out_off differs: a tile's clips lie in the slot lines of
 // its FIRST record, 32 ra + position).  Roofline: HBM; algorithmic bytes as for rb_k_liftover_stream.
 #include "rb_lift.h"
+#include "rb_launch.h"
 #include <type_traits>
 
 #ifndef RBT_OPS

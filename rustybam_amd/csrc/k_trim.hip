@@ -10,6 +10,7 @@
 // independent (one pair per query name and pass, paf.rs:264-284); the pass/recursion driver stays on the
 // host.  Fully general (all op codes, both binary-search policies).
 #include "rb_trim.h"
+#include "rb_launch.h"
 #include <algorithm>
 
 
@@ -1012,46 +1013,37 @@ __global__ __launch_bounds__(64) void rb_k_overlap_split_wave_pending(rb_trim_pa
         __builtin_amdgcn_wave_barrier();
     }
 }
-extern "C" hipError_t rb_launch_overlap_split_quad(const rb_trim_params *p, int t, bool from_list, hipStream_t stream); // k_trim4.hip
 extern "C" size_t rb_trim_scratch_bytes(uint32_t blocks) { return (size_t)blocks * RB_TW_SLAB_WORDS(RB_TW_CAP3) * 4u; }
 extern "C" hipError_t rb_launch_overlap_split(const rb_trim_params *p, hipStream_t stream) {
     if (p->n_pairs == 0) return hipSuccess;
     rb_trim_params q = *p;
-    static const bool serial_only = getenv("RB_DEBUG_TRIM_SERIAL") != nullptr; // diagnostics: the general kernel for every pair
-    if (!serial_only) {
-        q.only_pending = 0;
-        // first attempt: four pairs per wavefront (k_trim4.hip); what it lists goes to the wave-per-pair kernel.  Without a list (its
-        // allocation failed) the wave-per-pair kernel looks at every pair, as it did before round 6.
-        static const char *quad_env = getenv("RB_TRIM_QUAD"); // diagnostics: 0 = off, 4 / 8 = ops per lane of the first attempt's regions
-        const int quad_t = quad_env ? atoi(quad_env) : 4;
-        if (q.pend_list && quad_t) {
-            hipError_t e = rb_launch_overlap_split_quad(&q, quad_t, false, stream);
-            if (e != hipSuccess) return e;
-            q.only_pending = 2;
-            if (quad_t < 8) { // the pairs whose overlap does not fit 64 ops of a record's end: 128
-                e = rb_launch_overlap_split_quad(&q, 8, true, stream);
-                if (e != hipSuccess) return e;
-            }
-            const unsigned g0 = (unsigned)(p->n_pairs < 8192 ? p->n_pairs : 8192);
-            hipLaunchKernelGGL(rb_k_overlap_split_wave_pending<RB_TW_CAP>, dim3(g0), dim3(64), 0, stream, q);
-        } else {
-            hipLaunchKernelGGL(rb_k_overlap_split_wave<RB_TW_CAP>, dim3((unsigned)p->n_pairs), dim3(64), 0, stream, q);
-        }
-        q.only_pending = 2; // (the attempts behind the first walk its list; what they decline is listed already)
-        const unsigned g1 = (unsigned)(p->n_pairs < 8192 ? p->n_pairs : 8192);
-        hipLaunchKernelGGL(rb_k_overlap_split_wave_pending<RB_TW_CAP1>, dim3(g1), dim3(64), 0, stream, q);
-        const unsigned g2 = (unsigned)(p->n_pairs < 2048 ? p->n_pairs : 2048);
-        hipLaunchKernelGGL(rb_k_overlap_split_wave_pending<RB_TW_CAP2>, dim3(g2), dim3(64), 0, stream, q);
-        if (q.scratch && q.scratch_blocks) {
-            const unsigned g3 = (unsigned)(p->n_pairs < q.scratch_blocks ? p->n_pairs : q.scratch_blocks);
-            hipLaunchKernelGGL(rb_k_overlap_split_wave_scratch<RB_TW_CAP3>, dim3(g3), dim3(64), 0, stream, q);
-        }
+    q.only_pending = 0;
+    // first attempt: four pairs per wavefront (k_trim4.hip); what it lists goes to the wave-per-pair kernel.  Without a list (its
+    // allocation failed) the wave-per-pair kernel looks at every pair, as it did before round 6.
+    if (q.pend_list) {
+        hipError_t e = rb_launch_overlap_split_quad(&q, 4, false, stream);
+        if (e != hipSuccess) return e;
+        q.only_pending = 2;
+        e = rb_launch_overlap_split_quad(&q, 8, true, stream); // the pairs whose overlap does not fit 64 ops of a record's end: 128
+        if (e != hipSuccess) return e;
+        const unsigned g0 = (unsigned)(p->n_pairs < 8192 ? p->n_pairs : 8192);
+        hipLaunchKernelGGL(rb_k_overlap_split_wave_pending<RB_TW_CAP>, dim3(g0), dim3(64), 0, stream, q);
+    } else {
+        hipLaunchKernelGGL(rb_k_overlap_split_wave<RB_TW_CAP>, dim3((unsigned)p->n_pairs), dim3(64), 0, stream, q);
     }
-    q.only_pending = serial_only ? 0 : 1;
-    if (serial_only) q.pend_list = nullptr;
+    q.only_pending = 2; // (the attempts behind the first walk its list; what they decline is listed already)
+    const unsigned g1 = (unsigned)(p->n_pairs < 8192 ? p->n_pairs : 8192);
+    hipLaunchKernelGGL(rb_k_overlap_split_wave_pending<RB_TW_CAP1>, dim3(g1), dim3(64), 0, stream, q);
+    const unsigned g2 = (unsigned)(p->n_pairs < 2048 ? p->n_pairs : 2048);
+    hipLaunchKernelGGL(rb_k_overlap_split_wave_pending<RB_TW_CAP2>, dim3(g2), dim3(64), 0, stream, q);
+    if (q.scratch && q.scratch_blocks) {
+        const unsigned g3 = (unsigned)(p->n_pairs < q.scratch_blocks ? p->n_pairs : q.scratch_blocks);
+        hipLaunchKernelGGL(rb_k_overlap_split_wave_scratch<RB_TW_CAP3>, dim3(g3), dim3(64), 0, stream, q);
+    }
+    q.only_pending = 1;
     static const bool no_serial = getenv("RB_DEBUG_TRIM_NO_SERIAL") != nullptr; // diagnostics: leave what the wave kernels declined as it is
     if (no_serial) return hipGetLastError();
-    const uint64_t sblocks = (q.only_pending && q.pend_list) ? std::min<uint64_t>((p->n_pairs + 63) / 64, 256) : (p->n_pairs + 63) / 64;
+    const uint64_t sblocks = q.pend_list ? std::min<uint64_t>((p->n_pairs + 63) / 64, 256) : (p->n_pairs + 63) / 64;
     hipLaunchKernelGGL(rb_k_overlap_split, dim3((unsigned)sblocks), dim3(64), 0, stream, q);
     return hipGetLastError();
 }
@@ -1060,13 +1052,6 @@ extern "C" hipError_t rb_launch_overlap_split(const rb_trim_params *p, hipStream
 // between two passes of trim-paf: the clipped records of a pass become the batch's current records (include/rustybam_amd.h,
 // rb_dev_apply_pairs), and the current records gathered into a dense batch again (rb_dev_gather_records)
 // ------------------------------------------------------------------------------------------------
-struct rb_apply_params {
-    uint64_t n_pairs;
-    const uint32_t *left, *right;
-    const rb_pair_row *rows;
-    uint64_t *op_off;
-    rb_norm_row *norm;
-};
 __global__ __launch_bounds__(256) void rb_k_apply_pairs(rb_apply_params p) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t k = t >> 1;
@@ -1089,15 +1074,6 @@ extern "C" hipError_t rb_launch_apply_pairs(const rb_apply_params *p, hipStream_
     return hipGetLastError();
 }
 
-struct rb_gather_params {
-    uint64_t n_rec;
-    const uint32_t *ops;
-    const uint64_t *op_off;
-    const rb_norm_row *norm;
-    uint64_t *new_off; // [n_rec + 1]: counts (fill == 0) then their exclusive prefix
-    uint32_t *new_ops;
-    int fill;
-};
 __global__ __launch_bounds__(256) void rb_k_gather_records(rb_gather_params p) {
     if (!p.fill) { // the kept length of every record
         const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1128,20 +1104,6 @@ extern "C" hipError_t rb_launch_gather_records(const rb_gather_params *p, hipStr
 // RB_TS_BIG records by the whole wave, one after the other), an exclusive scan that gives the chosen pairs dense slots and their
 // places in the ops arena, rb_k_trim_place.  The host keeps only the recursion loop (:286-288) and reads 64 bytes per pass.
 // ------------------------------------------------------------------------------------------------
-struct rb_tsel_params {
-    uint64_t n_groups;
-    const uint32_t *order;     // [n_rec] records stably sorted by query name
-    const uint64_t *grp_off;   // [n_groups + 1] group g = order[grp_off[g] .. grp_off[g + 1])
-    const rb_norm_row *norm;   // current coordinates / lengths of every record
-    uint8_t *contained;        // [n_rec] by record: the flags of THIS pass (paf.rs:224: reset at every level)
-    uint64_t *slot;            // [n_groups + 1] ops(left) + ops(right) of the group's pair (0: none); scanned in place: where its clips go
-    uint64_t *has;             // [n_groups + 1] 1 for a group with a pair, else 0; scanned in place: the pair's dense slot
-    uint32_t *cand;            // [2 n_groups] the chosen (left, right) records of each group
-    uint64_t out_base;
-    uint32_t *left, *right;    // dense outputs
-    uint64_t *pair_out_off;
-    rb_trim_pass *pass;
-};
 #define RB_TS_BIG 48u
 
 struct rb_tsel_best {
@@ -1294,20 +1256,13 @@ __global__ __launch_bounds__(256) void rb_k_trim_check(const rb_pair_row *rows, 
     const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n_pairs && rows[k].status != RB_ST_OK) atomicMax(&pass->bad_status, rows[k].status);
 }
-extern "C" hipError_t rb_launch_exclusive_scan(uint64_t *v, uint64_t n, uint64_t *block_sums, uint64_t *total_out, hipStream_t stream);
-extern "C" hipError_t rb_fill_async(void *dst, int value, size_t bytes, hipStream_t stream);
 extern "C" hipError_t rb_launch_trim_select(const rb_tsel_params *p, uint64_t *block_sums, hipStream_t stream) {
     hipError_t e = rb_fill_async(p->pass, 0, sizeof(rb_trim_pass), stream); // (the library's own fill kernel: capi.hip says why)
     if (e != hipSuccess) return e;
     if (p->n_groups == 0) return hipSuccess;
     const unsigned blocks = (unsigned)((p->n_groups + 255) / 256);
-    static const bool rows_off = getenv("RB_TRIM_SELECT_ROWS") && atoi(getenv("RB_TRIM_SELECT_ROWS")) == 0; // diagnostics: the thread-per-group form for every group
-    if (rows_off) {
-        hipLaunchKernelGGL(rb_k_trim_select<false>, dim3(blocks), dim3(256), 0, stream, *p);
-    } else {
-        hipLaunchKernelGGL(rb_k_trim_select_rows, dim3((unsigned)((p->n_groups + 15) / 16)), dim3(256), 0, stream, *p);
-        hipLaunchKernelGGL(rb_k_trim_select<true>, dim3(blocks), dim3(256), 0, stream, *p);
-    }
+    hipLaunchKernelGGL(rb_k_trim_select_rows, dim3((unsigned)((p->n_groups + 15) / 16)), dim3(256), 0, stream, *p);
+    hipLaunchKernelGGL(rb_k_trim_select<true>, dim3(blocks), dim3(256), 0, stream, *p);
     e = rb_launch_exclusive_scan(p->slot, p->n_groups, block_sums, nullptr, stream);
     if (e != hipSuccess) return e;
     e = rb_launch_exclusive_scan(p->has, p->n_groups, block_sums, nullptr, stream);

@@ -18,6 +18,7 @@
 // policy, region too small, a walk that leaves the region, a non-query run of T ops) is listed in pend_list and done by the kernels
 // behind it: the wave-per-pair kernel with its larger regions, then the serial one.
 #include "rb_trim.h"
+#include "rb_launch.h"
 
 // ---- a record's region in LDS -----------------------------------------------------------------------------------------------------
 template <int T>
