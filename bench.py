@@ -18,8 +18,13 @@ here touches the GPU.  Records shard by contiguous range, no data-path collectiv
 canonical (gathered) order; with --scaling strong it must be the same for N = 1, 2, 4, 8.
 
 Prints ONE JSON line on rank 0: metric CIGAR-ops/s (whole job), plus `roofline` for the streaming
-kernel (HIP events on the launch stream) and `cpu_baseline` (the oracle, a faithful per-base port of
-the reference, timed on this host's cores on a bounded sample of the same workload).
+kernel (HIP events on the launch stream of the timed steps).  A plain run does only what that line
+needs: set-up (the batch, the sizing calls, the output arena and the ops array placed by measurement),
+warm-up, the timed steps, the output digest, --dump-outputs.  `--full` adds what takes runs or
+processes of its own: the end-to-end leg (`e2e`), the kernel on the buffers as first allocated
+(`roofline.unplaced`), `cpu_baseline` (the oracle, a faithful per-base port of the reference, timed on
+this host's cores on a bounded sample of the same workload, and the op-space port) with the parity
+checks against it, and the `box` block.
 """
 import argparse
 import json
@@ -56,11 +61,15 @@ def parse():
                     help="where the records lie on the target: config 3 = uniform; config 2 = overlap (every record overlaps the window); "
                          "`--workload config2 --placement uniform` is SURVEY 8(d)'s second imbalance case: about 0.8 %% of the records overlap "
                          "the window, every record is still walked (liftover.rs:119-121)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the end-to-end leg, the kernel on the buffers as "
+                         "first allocated (roofline.unplaced), the CPU baselines with the parity checks, and the `box` block.  Off: set up, "
+                         "warm up, time the steps, write --dump-outputs, print the line")
     ap.add_argument("--no-box", action="store_true", help="skip the `box` block (memory-mix probe, in-kernel clock, tail of the launch)")
     ap.add_argument("--box-smi", action="store_true",
                     help="the `box` block also asks rocm-smi (two child processes, started before this one touches the GPU; never under a profiler)")
     ap.add_argument("--legacy", action="store_true", help="RB_BSEARCH_LEGACY (rustc 1.52 .. 1.81 binary search): duplicates resolved by probe replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines, the parity checks and the end-to-end leg")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--early-exit", action="store_true", help="allow the kernel to stop a record early (off: full walk)")
     ap.add_argument("--unfused", action="store_true", help="run rb_dev_scan_records as its own pass inside the step instead of the fused scan")
@@ -80,7 +89,7 @@ def parse():
     ap.add_argument("--e2e-records", type=int, default=1_000_000,
                     help="records of the text-in -> text-out leg (`rb [--gpus N] liftover` on the PAF text of the same workload, first byte "
                          "read to last byte written; 1e6 = the headline size, 14.7 GB in / 19 GB out in /dev/shm -- cut to 1e5 when the "
-                         "host lacks the memory); 0 = skip")
+                         "host lacks the memory); 0 = skip; only with --full")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64): a fixed, seeded sample of the "
                          "hit rows, the clipped CIGAR ops of those rows, a sample of the normalised records, and the counts and digest of the "
@@ -377,10 +386,10 @@ def main():
                           "port": os.environ.get("MASTER_PORT"), "ipc_legacy": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY")}), flush=True)
         return
     e2e = None
-    want_smi = rank == 0 and args.box_smi and not args.no_box and not profiled
+    want_smi = rank == 0 and args.full and args.box_smi and not args.no_box and not profiled
     smi = smi_facts() if want_smi else None
     sampler = SmiSampler() if want_smi else None  # (a child process, started before this one touches the GPU)
-    if rank == 0 and args.e2e_records > 0 and args.workload == "config3" and args.op == "liftover" and not args.no_cpu_baseline and not profiled:
+    if rank == 0 and args.full and args.e2e_records > 0 and args.workload == "config3" and args.op == "liftover" and not args.no_cpu_baseline and not profiled:
         # (child processes, before this one initialises the GPU; with N ranks: `rb --gpus N` on the same file while the other ranks
         #  wait for rank 0 at the rendezvous)
         e2e = e2e_leg(args.e2e_records, args.windows, world)
@@ -460,6 +469,46 @@ def main():
             except Exception as e:  # (torch could not take the library's memory for a tensor of this device: its own allocator then)
                 alloc_note.append(f"{type(e).__name__}: {e}")
         return torch.empty(n, dtype=dtype, device=dev), None
+
+    class _Raw:  # (an address as a tensor of bytes: a placement candidate carved out of a larger buffer)
+        def __init__(self, ptr, nbytes):
+            self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 3}
+
+    spare = []  # buffers that lost a placement (DevBufs), kept: the ops array's candidates are carved out of them
+
+    def place(n, dtype, score, pieces=()):
+        """-> (tensor, owner, {"launch_ms": [...], "kept": i}): rb_dev_alloc_placed_by's search, run here -- up to --placement-tries
+        candidates of n elements, score(address) = the step on each, the first of the fastest kept.  `pieces` ((address, owner): a
+        buffer that is there already, or memory that lost a placement before) are tried first, then new buffers, each only while twice
+        its size and 8 GB stay free (the library's rule).  The library gives the losers back at once (1.5 s per 40 GB on the headline
+        batch); here they go to `spare`, and the process's exit returns them."""
+        if not lib_alloc or alloc_note:
+            return (*big(n, dtype), None)
+        nbytes = max(n * torch.empty(0, dtype=dtype).element_size(), 256)
+        cands, ms = [], []
+        for i in range(args.placement_tries):
+            if i < len(pieces):
+                cands.append(pieces[i])
+            else:
+                if i > 0 and torch.cuda.mem_get_info(dev)[0] < 2 * nbytes + (8 << 30):
+                    break
+                try:
+                    b_ = capi_mod.DevBuf(eng, torch, n, dtype, device=dev)
+                except Exception as e:
+                    if i > 0:
+                        break
+                    alloc_note.append(f"{type(e).__name__}: {e}")  # (as big(): torch's own allocator then)
+                    return torch.empty(n, dtype=dtype, device=dev), None, None
+                cands.append((b_.ptr, b_))
+            ms.append(float(score(cands[-1][0])))
+        best = int(np.argmin(ms))
+        for ptr_, o_ in cands:
+            if o_ is not cands[best][1] and all(o_ is not s_ for s_ in spare):
+                spare.append(o_)
+        ptr, owner = cands[best]
+        whole = ptr == owner.ptr and owner.n * owner.item == nbytes and owner.dtype == dtype
+        t_ = owner.t if whole else torch.as_tensor(_Raw(ptr, nbytes), device=dev).view(dtype)
+        return t_, owner, {"launch_ms": [round(x, 4) for x in ms], "kept": best}
 
     d_ops, own_ops = big(total_ops + 64, torch.int32)
     eng.dev_synth_fill_ops(seed, first, n_rec, d_off.data_ptr(), d_ops.data_ptr())
@@ -568,18 +617,21 @@ def main():
     placement_ms = 0.0
     unplaced_ms = None  # the clip kernel (HIP events) on the buffers as rb_dev_alloc first returned them: what a caller that places nothing gets
     if args.placement_tries > 1 and own_out is not None:
-        run_op(d_ws, d_rows, d_out)
-        torch.cuda.synchronize()
-        eng.set_timing(True)
-        for _ in range(5):
+        if args.full:
             run_op(d_ws, d_rows, d_out)
-        torch.cuda.synchronize()
-        u_ = eng.get_timing()[-5:]
-        eng.set_timing(False)
-        unplaced_ms = float(np.mean(u_)) if len(u_) else None
+            torch.cuda.synchronize()
+            eng.set_timing(True)
+            for _ in range(5):
+                run_op(d_ws, d_rows, d_out)
+            torch.cuda.synchronize()
+            u_ = eng.get_timing()[-5:]
+            eng.set_timing(False)
+            unplaced_ms = float(np.mean(u_)) if len(u_) else None
         tp = time.perf_counter()
-        del d_out
-        own_out.free()
+        sized = [(own_out.ptr, own_out)]  # (the sizing calls' arena: what rb_dev_alloc returned first, the search's first candidate)
+        if args.placement_by != "launch":
+            del d_out
+            own_out.free()
 
         def launch_score(ptr):
             # the clip kernels' own time on the candidate (HIP events inside the library, three launches), the measure the line reports --
@@ -596,15 +648,22 @@ def main():
             eng.set_timing(False)
             return float(np.mean(ev_)) if len(ev_) == 3 else wall
 
-        d_out, own_out = big(out_cap + 64, torch.int32, placed=args.placement_tries, score=launch_score if args.placement_by == "launch" else None)
+        if args.placement_by == "launch":
+            d_out, own_out, pl_ = place(out_cap + 64, torch.int32, launch_score, sized)
+            if own_out is not None:
+                own_out.placement = pl_
+        else:
+            d_out, own_out = big(out_cap + 64, torch.int32, placed=args.placement_tries)
         # ... and the INPUT: with the arena fixed, the same launch reading its ops from other pages differs by up to 8 % as well (9.23 /
         # 9.38 / 10.02 ms, profiles/r04_alloc_summary.md).  Candidates of the ops array, each filled with a copy of the ops and measured by
-        # the step itself; rows and workspace do not care where they lie (9.42 - 9.48 ms).
+        # the step itself; rows and workspace do not care where they lie (9.42 - 9.48 ms).  The candidates are carved out of the arena's
+        # losers, first one piece of each, then a second one of each: pages the arena's search drew but did not keep, as the new
+        # allocations that used to follow their release got (no allocation, nothing given back)
         if args.placement_by == "launch" and own_ops is not None:
-            class _Raw:  # (a candidate's address as a tensor, for the copy)
-                def __init__(self, ptr, nbytes):
-                    self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 3}
             ops_bytes = (total_ops + 64) * 4
+            stride = (ops_bytes + (2 << 20) - 1) >> 21 << 21  # (each piece starts on a 2 MB chunk, as a buffer of its own would)
+            pieces = [(s_.ptr + k * stride, s_) for k in range(max([s_.n * s_.item // stride for s_ in spare] + [0]))
+                      for s_ in spare if k * stride + ops_bytes <= s_.n * s_.item]
             views = {}
 
             def ops_score(ptr):
@@ -617,19 +676,21 @@ def main():
                 finally:
                     nonlocal_view[0] = None
             incumbent_ms = launch_score(d_out)  # (the ops array as it lies: a candidate like the others -- the pages the arena's losers gave back may be the slow ones)
-            new_ops, new_own = big(total_ops + 64, torch.int32, placed=args.placement_tries, score=ops_score)
-            if new_own is not None and new_own.placement:
-                ops_placement = dict(new_own.placement, incumbent_ms=round(incumbent_ms, 4))
-                if min(new_own.placement["launch_ms"]) < incumbent_ms:
+            new_ops, new_own, pl_ = place(total_ops + 64, torch.int32, ops_score, pieces)
+            if new_own is not None:
+                ops_placement = dict(pl_, incumbent_ms=round(incumbent_ms, 4))
+                if min(pl_["launch_ms"]) < incumbent_ms:
                     old_t, old_own = d_ops, own_ops
                     d_ops, own_ops = new_ops, new_own
                     view = views[d_ops.data_ptr()]
                     del old_t
-                    old_own.free()
+                    spare.append(old_own)
+                    spare[:] = [s_ for s_ in spare if s_ is not own_ops]  # (the ops array now lives in it)
                 else:
                     ops_placement["kept"] = "incumbent"
                     del new_ops
-                    new_own.free()
+                    if all(new_own is not s_ for s_ in spare):
+                        spare.append(new_own)
         run_op(d_ws, d_rows, d_out)
         torch.cuda.synchronize()
         placement_ms = (time.perf_counter() - tp) * 1e3
@@ -660,6 +721,10 @@ def main():
     elapsed = time.perf_counter() - t0
     kern_ms = eng.get_timing()
     eng.set_timing(False)
+    if args.full or os.environ.get("RB_BENCH_PLACEMENTS"):  # (what runs from here on wants device memory: the placement's losers go back)
+        for s_ in spare:
+            s_.free()
+        spare.clear()
     if os.environ.get("RB_BENCH_PLACEMENTS") and rank == 0 and args.op == "liftover":
         # experiment: the same launch with the output arena in OTHER physical pages of this process (earlier arenas stay allocated), and
         # the probe's write side alone on each: is the time of a launch a property of where its output lies?
@@ -867,7 +932,7 @@ def main():
         result["dump_outputs"] = dumped
 
     # ---- CPU baseline + sample parity (rank 0, N = 1 only) ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.descriptors and args.op == "liftover" and not irregular and args.irregular_frac == 0:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.descriptors and args.op == "liftover" and not irregular and args.irregular_frac == 0:
         from oracle import pyoracle  # checker / baseline only; never on the product path
         from rustybam_amd import capi
         threads = os.cpu_count() or 1
@@ -1003,7 +1068,7 @@ def main():
     #      of back-to-back launches; the same run leaves the time each wave was done, hence how long the launch ran on after 95 % of
     #      them had retired.  (b) the library's memory-mix probe on these very buffers: the kernel's bytes in its access shape without
     #      its instructions -- a box that is slow at moving bytes shows here, a box that holds a lower clock shows in (a).
-    if rank == 0 and not args.no_box and args.op == "liftover" and not args.descriptors and not irregular:
+    if rank == 0 and args.full and not args.no_box and args.op == "liftover" and not args.descriptors and not irregular:
         box = {"smi_before_start": smi}
         try:
             dpol = policy | ((128 | 256) << 8)
@@ -1079,7 +1144,8 @@ def main():
     if rank == 0:
         print(json.dumps(result))
     d_ops = d_ws = d_rows = d_out = rows_t = None
-    [o.free() for o in (own_ops, own_ws, own_rows, own_out) if o]
+    if args.full:  # (a plain run leaves its buffers, and the placement's losers, to the process's exit: it returns them at once)
+        [o.free() for o in (own_ops, own_ws, own_rows, own_out) if o]
     eng.plan_destroy(plan)
     if use_dist:
         dist.destroy_process_group()

@@ -53,6 +53,18 @@ def test_defaults_place_the_arena_by_the_step_itself(monkeypatch):
     assert a.placement_tries == 1 and a.placement_by == "sweep"
 
 
+def test_full_is_off_by_default(monkeypatch):
+    """a plain `python bench.py` does what its headline needs; `--full` adds the end-to-end leg, roofline.unplaced, the CPU baselines
+    with their parity checks and the `box` block"""
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full is True
+
+
 def test_an_ended_rank_leaves_nothing_in_shared_memory():
     """bench.py's end-to-end leg keeps its files in /dev/shm (memory).  launch_ranks ends the other ranks with SIGTERM when one fails: the
     leg's directory must go with the process -- and a directory an earlier run left after being killed outright is taken away too."""

@@ -49,6 +49,24 @@ def test_strong_scaling_digest_is_the_same_for_every_gpu_count():
         assert many["job_hits"] == one["job_hits"] and many["output_digest"] == one["output_digest"], n
 
 
+def test_plain_run_leaves_the_extras_to_full():
+    """a plain run prints the headline line without what takes runs or processes of its own; --full adds them, on the same output"""
+    def run(extra):
+        args = ["--records", "20000", "--steps", "2", "--warmup", "1"] + extra
+        env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    extras = ("e2e", "e2e_paf_records_per_s", "cpu_baseline", "parity_sample", "parity_full", "box")
+    plain = run([])
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and not any(k in plain for k in extras)
+    assert plain["roofline"]["unplaced"] is None and plain["config"]["out_arena_placement"]["launch_ms"]
+    full = run(["--full", "--e2e-records", "20000", "--cpu-seconds", "1"])
+    assert all(k in full for k in extras), sorted(full)
+    assert full["parity_sample"].startswith("ok") and full["parity_full"].startswith("ok") and full["roofline"]["unplaced"]["kernel_ms"] > 0
+    assert full["output_digest"] == plain["output_digest"] and full["job_hits"] == plain["job_hits"]
+
+
 def test_weak_scaling_two_ranks_sum_their_shards():
     """--scaling weak (the driver's default): rank r owns records [r * R, (r + 1) * R); the job's record / hit counts are the sum"""
     import torch

@@ -7,7 +7,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 timeout -k 5 2400 python3 -m pytest tests -q -m gpu -x > $out/tests.log 2>&1; echo "tests rc=$?"; tail -4 $out/tests.log
 timeout -k 5 300 python3 __graft_entry__.py smoke > $out/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $out/smoke.log
-timeout -k 5 900 python3 bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; tail -c 300 $out/bench.err
+timeout -k 5 900 python3 bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; tail -c 300 $out/bench.err
 python3 - $out/bench.json <<'PY'
 import json, sys
 try:

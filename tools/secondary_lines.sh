@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 rm -f gpurun_out/r06_secondary.txt
 for args in "--op break" "--op break --irregular-frac 0.01" "--workload irregular --records 100000" "--workload config2" "--workload config2 --placement uniform" "--workload config2-lognormal" "--workload config4-shape --op break" "--workload config4-shape --op liftover"; do
-  tagname=$(echo "$args" | tr -d '-' | tr ' .' '__')
+  tagname=$(echo "$args" | tr -d '-' | tr ' .' '__'); args="$args --full"  # (the unplaced kernel time is in the line only with --full)
   timeout -k 5 900 python3 bench.py $args --steps 10 --no-cpu-baseline --no-box --e2e-records 0 2> /dev/null | tail -1 > gpurun_out/r06_${tagname}_bench.json
   python3 - "$args" gpurun_out/r06_${tagname}_bench.json <<'PY' | tee -a gpurun_out/r06_secondary.txt
 import json, sys
