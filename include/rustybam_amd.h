@@ -115,8 +115,11 @@ enum { RB_BSEARCH_MODERN = 0 /* rustc >= 1.82 (and < 1.52) */, RB_BSEARCH_LEGACY
         * The plan is the one built from the op offsets the batch had BEFORE the passes (records only shrink inside their old
         * extents, so its tiles still hold).  With it the README pipeline trim-paf | break-paf needs no rb_dev_gather_records
         * between the two: the clip kernels stream over the gaps the cuts left between the records of a tile.  A record a pass has
-        * MOVED (an irregular record's clip, written behind the ops in use) must lie below batch->n_ops = the plan's op count: if the
-        * passes moved any, gather first. */
+        * MOVED (an irregular record's clip, written behind the ops in use) lies at or behind batch->n_ops = the plan's op count: if the
+        * passes moved any, gather first.  The call REFUSES otherwise: it checks every record whose norm row has status RB_ST_OK, and
+        * returns RB_E_INVALID (rb_ctx_last_error names the record) before any clip kernel runs if [op_off[r] + first_op, + n_ops) is not
+        * inside [0, batch->n_ops).  That check waits for the stream once.  Norm rows that are stale but whose extents stay inside the
+        * batch are not caught: keeping them current is the caller's part. */
        RB_LIFT_OP_STARTS = 1 << 20 };
 
 /* rb_norm_row.flags / rb_reduce_row.flags */

@@ -798,7 +798,7 @@ extern "C" void rb_plan_destroy(rb_plan *pl) {
 
 // workspace layout: [hit_off (n_rec+1) u64][win_lo][block sums][arena cursors][jobs n_rec x 64 B][gen_list rows_cap u32][x_st rows_cap u64][x_en rows_cap u64]
 struct ws_layout {
-    size_t hit_off, win_lo, block_sums, arena, pend_count, pend_list, jobs, gen_list, x_st, x_en, bp_tmp, bp_off, bp_cur, brk_rows, copy_count, copy_list, decl_count, decl_list, gen_cp, diag_stamps, fb_count, fb_list, total;
+    size_t hit_off, win_lo, block_sums, arena, pend_count, pend_list, jobs, gen_list, x_st, x_en, bp_tmp, bp_off, bp_cur, brk_rows, copy_count, copy_list, decl_count, decl_list, gen_cp, diag_stamps, fb_count, fb_list, starts_bad, total;
 };
 // RB_DEBUG_NO_GEN_CP (diagnostics: the generic kernel walks every record from its first op, no room for checkpoints): read ONCE per
 // process -- the workspace layout and the kernel parameter must agree on it
@@ -836,6 +836,7 @@ static ws_layout ws_of(uint64_t n_rec, uint64_t rows_cap, uint64_t n_ops) {
     w.diag_stamps = take((n_rec + 1) * 4); // diagnostics build of the clip kernel: when each record's wave was done
     w.fb_count = take(256);
     w.fb_list = take((n_rec + 1) * 4); // the records of the tiles the tile kernel handed to the per-record kernel
+    w.starts_bad = take(256);          // RB_LIFT_OP_STARTS: the first record outside the batch
     w.total = o;
     return w;
 }
@@ -930,6 +931,19 @@ static int lift_common(rb_ctx *ctx, const rb_plan *plan, const rb_batch_view *b,
     if (p.op_starts && p.fused) return fail(ctx, RB_E_INVALID, "RB_LIFT_OP_STARTS takes finished norm_rows: not together with RB_LIFT_FUSED_SCAN");
     if (p.op_starts && (policy & RB_LIFT_DESCRIPTORS)) return fail(ctx, RB_E_INVALID, "RB_LIFT_OP_STARTS with RB_LIFT_DESCRIPTORS: a descriptor indexes the record's ORIGINAL cigar, which a batch cut in place no longer is");
     if (p.op_starts && b->n_ops > plan->n_ops) return fail(ctx, RB_E_INVALID, "RB_LIFT_OP_STARTS: batch->n_ops exceeds the plan's op count (gather the batch first)");
+    if (p.op_starts && b->n_rec) {
+        // the contract, enforced before any clip kernel runs: a record a pass has moved lies at or behind batch->n_ops, where the
+        // per-record state sized by the plan's op count (the generic kernel's checkpoints, gen_cp) and the tiles do not reach.  One
+        // check over the starts and the norm rows, and one wait for it
+        unsigned long long *bad = (unsigned long long *)(ws + w.starts_bad), first_bad = 0;
+        HIPCHK(ctx, rb_fill_async(bad, 0xFF, 8, ctx->stream));
+        HIPCHK(ctx, rb_launch_starts_check(b->op_off, norm, b->n_rec, b->n_ops, bad, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(&first_bad, bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (first_bad != ~0ull)
+            return fail(ctx, RB_E_INVALID, "RB_LIFT_OP_STARTS: record %llu lies outside the batch's %llu ops (a pass moved it: gather the batch first)",
+                        first_bad, (unsigned long long)b->n_ops);
+    }
     p.norm_w = const_cast<rb_norm_row *>(norm);
     p.pend_list = (uint32_t *)(ws + w.pend_list);
     p.pend_count = (unsigned long long *)(ws + w.pend_count);

@@ -271,6 +271,24 @@ extern "C" hipError_t rb_launch_swap(const rb_swap_params *p, hipStream_t stream
 }
 
 // ------------------------------------------------------------------------------------------------
+// RB_LIFT_OP_STARTS: the records a call will clip (norm status RB_ST_OK) must lie inside the batch, [op_off[r] + first_op, + n_ops)
+// within [0, n_ops).  *bad (set to ~0 by the caller) ends as the lowest record that does not.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rb_k_starts_check(const uint64_t *op_off, const rb_norm_row *norm, uint64_t n_rec, uint64_t n_ops,
+                                                         unsigned long long *bad) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rec || norm[r].status != RB_ST_OK) return;
+    const uint64_t s = op_off[r] + norm[r].first_op;
+    if (s < op_off[r] || s > n_ops || norm[r].n_ops > n_ops - s) atomicMin(bad, (unsigned long long)r);
+}
+extern "C" hipError_t rb_launch_starts_check(const uint64_t *op_off, const rb_norm_row *norm, uint64_t n_rec, uint64_t n_ops, unsigned long long *bad,
+                                             hipStream_t stream) {
+    if (n_rec == 0) return hipSuccess;
+    hipLaunchKernelGGL(rb_k_starts_check, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, stream, op_off, norm, n_rec, n_ops, bad);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // synthetic workload
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rb_k_synth(uint64_t seed, uint64_t first_record, uint64_t n_rec, const uint64_t *op_off, uint32_t *ops) {

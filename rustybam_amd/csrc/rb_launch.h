@@ -94,6 +94,8 @@ struct rb_compact_params {
 extern "C" hipError_t rb_launch_break_pieces(const rb_break_params *p, hipStream_t stream);
 extern "C" hipError_t rb_launch_break_place(const rb_break_params *p, hipStream_t stream);
 extern "C" hipError_t rb_launch_swap(const rb_swap_params *p, hipStream_t stream);
+extern "C" hipError_t rb_launch_starts_check(const uint64_t *op_off, const rb_norm_row *norm, uint64_t n_rec, uint64_t n_ops, unsigned long long *bad,
+                                             hipStream_t stream);
 extern "C" hipError_t rb_launch_synth(uint64_t seed, uint64_t first_record, uint64_t n_rec, const uint64_t *op_off, uint32_t *ops, hipStream_t stream);
 extern "C" hipError_t rb_launch_digest_rows(const rb_digest_params *p, hipStream_t stream);
 extern "C" hipError_t rb_launch_compact_clips(const rb_compact_params *p, hipStream_t stream);

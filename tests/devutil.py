@@ -48,10 +48,13 @@ class DevBatch:
         return self
 
     @classmethod
-    def from_trimmed(cls, torch, eng, dev, T):
+    def from_trimmed(cls, torch, eng, dev, T, allow_moved=False):
         """the batch of a trim_driver.ResidentTrim as its passes left it -- cut in place, op_off a table of starts, the extents in the norm
         rows -- for rb_dev_liftover / rb_dev_break with RB_LIFT_OP_STARTS: no rb_dev_gather_records in between.  The plan comes from the
-        op offsets the batch had before the passes.  Only valid while no pass has moved a record (T.pairs_by_wave == T.pairs_done)."""
+        op offsets the batch had before the passes.  Only valid while no pass has moved a record (T.pairs_by_wave == T.pairs_done):
+        refused otherwise.  allow_moved: build it anyway (the test that the library refuses such a batch itself)."""
+        if T.pairs_by_wave != T.pairs_done and not allow_moved:
+            raise ValueError(f"{T.pairs_done - T.pairs_by_wave} pairs were cut by the serial kernel, which moves records: gather the batch first")
         self = cls.__new__(cls)
         self.torch, self.eng, self.dev = torch, eng, dev
         self.n_rec, self.n_ops = T.n, T.n_ops0

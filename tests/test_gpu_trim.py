@@ -10,6 +10,7 @@ import pytest
 import rustybam_amd
 from rustybam_amd import trim_driver
 from rbtest_util import random_cigar, read_paf, recs_from_lines, sums, unpack
+from trim_util import format_resident
 
 pytestmark = pytest.mark.gpu
 
@@ -193,18 +194,7 @@ def test_trim_paf_fixture_with_the_batch_resident_on_the_device(golden, policy, 
     if policy == rustybam_amd.BSEARCH_MODERN:   # whole-chromosome alignments of up to 75 k ops: the wave kernel takes (nearly) all of their pairs
         assert T.pairs_by_wave >= 0.95 * T.pairs_done, f"{T.pairs_by_wave} of {T.pairs_done} pairs by the wave kernel"
     d_new, new_off, norm = T.gather()
-    ops = d_new.cpu().numpy().view(np.uint32)
-    lines = []
-    for i in T.order:
-        rid = ""
-        if norm0[i]["lead_ops"] or norm0[i]["trail_ops"]:
-            c = r.cigars[i]
-            lead, trail = c[:norm0[i]["lead_ops"]], c[len(c) - norm0[i]["trail_ops"]:][::-1]
-            rid = f"_TO.{unpack(lead)}.{unpack(trail)}"
-        cg = ops[int(new_off[i]):int(new_off[i + 1])]
-        lines.append("\t".join(map(str, [r.q_name[i], r.q_len[i], int(norm[i]["q_st"]), int(norm[i]["q_en"]), chr(r.strand[i]), r.t_name[i],
-                                          r.t_len[i], int(norm[i]["t_st"]), int(norm[i]["t_en"]), int(norm[i]["nmatch"]), int(norm[i]["aln_len"]),
-                                          r.mapq[i], "id:Z:" + rid, "cg:Z:" + unpack(cg)])) + "\n")
+    lines = format_resident(r, norm0, norm, d_new.cpu().numpy().view(np.uint32), new_off, T.order).splitlines(keepends=True)
     dig = json.load(open(os.path.join(golden, "digests.json")))[key]["md5"]
     assert len(lines) == 249
     assert hashlib.md5("".join(lines).encode()).hexdigest() == dig

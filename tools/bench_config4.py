@@ -113,8 +113,15 @@ def main():
     # ---- break-paf --max-size 100 on the batch as the passes left it ----
     in_place = T.pairs_by_wave == T.pairs_done  # (no pass moved a record: RB_LIFT_OP_STARTS applies)
     res_break = {}
-    B = DevBatch.from_trimmed(torch, eng, dev, T)
-    pol = MOD | rustybam_amd.LIFT_OP_STARTS | rustybam_amd.BREAK_ONE_WALK
+    if in_place:
+        B = DevBatch.from_trimmed(torch, eng, dev, T)
+        pol = MOD | rustybam_amd.LIFT_OP_STARTS | rustybam_amd.BREAK_ONE_WALK
+    else:  # (a pass moved records -- the serial kernel -- and the library refuses RB_LIFT_OP_STARTS on such a batch: break-paf on the dense copy)
+        T.fetch()
+        d_new, new_off, norm = T.gather()
+        d_c = [torch.from_numpy(np.ascontiguousarray(norm[k]).view(np.int64)).to(dev) for k in ("t_st", "t_en", "q_st", "q_en")]
+        B = DevBatch.from_device(torch, eng, dev, d_new, int(new_off[-1]), new_off, d_c, torch.from_numpy(strand).to(dev))
+        pol = MOD | rustybam_amd.LIFT_FUSED_SCAN | rustybam_amd.BREAK_ONE_WALK
     rows, out, cnt = B.run(None, max_size=100, rows_cap=4 * n, policy=pol)  # sizing (and the first launch of its kernels)
     n_pieces, one_walk = int(rows.shape[0]), not bool(cnt["redo_two_walk"])
     out_ops_emitted = int(rows[:, 3].to(torch.int64).sum().item())
@@ -154,7 +161,8 @@ def main():
               "pair": stage(k_pair, pair_bytes, "rb_dev_overlap_split, all passes, on the bytes the earlier rounds price (both records' ops whole + row + end words); "
                             f"on what the kernels touch ({pair_bytes_touched} B): {round(pair_bytes_touched / (k_pair * 1e-3) / PEAK, 4)}"),
               "apply": stage(k_apply, apply_bytes, "rb_dev_apply_pairs + rb_dev_trim_check, all passes"),
-              "break": stage(min(brk_ms), break_bytes, "rb_dev_break with RB_LIFT_OP_STARTS | RB_BREAK_ONE_WALK on the batch as the passes left it: 4 B per kept op + 48 B per "
+              "break": stage(min(brk_ms), break_bytes, ("rb_dev_break with RB_LIFT_OP_STARTS | RB_BREAK_ONE_WALK on the batch as the passes left it" if in_place else
+                             "rb_dev_break with RB_LIFT_FUSED_SCAN | RB_BREAK_ONE_WALK on the gathered copy (a pass moved records)") + ": 4 B per kept op + 48 B per "
                              "record + 88 B per piece + 4 B per emitted op; best of 3")}
     total_ms = sum(s["kernel_ms"] for s in stages.values())
     res = {"workload": f"config 4: {n} records, {total_ops} ops, {n // 4} query groups of 4, seed 0x5eed0004; batch resident in HBM",
