@@ -269,6 +269,13 @@ int rb_dev_memset(rb_ctx *ctx, void *dev_dst, int value, size_t bytes);         
 /* ---- K1: one pass over every record's ops ----------------------------------------------------- *
  * reduce_rows and/or norm_rows may be NULL.  [n_rec] each. */
 int rb_dev_scan_records(rb_ctx *ctx, const rb_batch_view *batch, rb_reduce_row *reduce_rows, rb_norm_row *norm_rows);
+/* Which kernel scanned what (tests, diagnostics; read-only).  rb_dev_scan_records has two kernels: a batch of at least 64 records whose
+ * mean is at most 1536 ops takes the ROW FORM (a row of 16 lanes per record, four records to a wavefront), which leaves its records of
+ * fewer than 4 or more than 2048 ops on a list for the wave-per-record kernel; every other batch goes to the wave-per-record kernel
+ * whole.  Same rows either way.  After a call on this context: out[0] = records the row form scanned itself, out[1] = records it
+ * listed; both 0 when the last call did not take the row form (or none was made).  Synchronises the context's stream and reads eight
+ * bytes back; rb_dev_scan_records itself does nothing for it but remember the batch's record count. */
+int rb_ctx_scan_route(rb_ctx *ctx, uint64_t out[2]);
 
 /* ---- schedule (host side, no device work besides small uploads) ------------------------------- *
  * Built from HOST copies of the small per-record / per-window arrays:

@@ -178,6 +178,13 @@ class Engine:
         self._chk(self.L.rb_dev_scan_records(self.ctx, C.byref(view), C.c_void_p(reduce_ptr or 0),
                                              C.c_void_p(norm_ptr or 0)), "rb_dev_scan_records")
 
+    def scan_route(self):
+        """-> (records the row form of the last scan on this context took itself, records it listed for the wave-per-record kernel);
+        (0, 0): the wave-per-record kernel took the whole batch (rb_ctx_scan_route)"""
+        o = (C.c_uint64 * 2)()
+        self._chk(self.L.rb_ctx_scan_route(self.ctx, o), "rb_ctx_scan_route")
+        return int(o[0]), int(o[1])
+
     def dev_digest_rows(self, view, rows_ptr, n_rows, out_ptr, row_base, rec_base, digest_ptr):
         self._chk(self.L.rb_dev_digest_rows(self.ctx, C.byref(view), C.c_void_p(rows_ptr), C.c_uint64(n_rows), C.c_void_p(out_ptr),
                                             C.c_uint64(row_base), C.c_uint64(rec_base), C.c_void_p(digest_ptr)), "rb_dev_digest_rows")

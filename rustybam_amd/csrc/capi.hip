@@ -72,6 +72,7 @@ struct rb_ctx {
     uint64_t trim_pend_cap = 0;
     void *scan_list = nullptr; // [count (256 B) | indices of the records the row form of the scan left to the wave-per-record kernel]
     uint64_t scan_list_cap = 0;
+    uint64_t scan_rows_n = 0; // records of the last rb_dev_scan_records call if it took the row form, 0 if not (rb_ctx_scan_route)
     // pinned staging ring of the host-buffer entry points (rb_dev_upload / rb_dev_download): large transfers go through two
     // page-locked chunks (hipHostMalloc), the copy into / out of a chunk on several host threads while the DMA of the other runs
     void *pin[2] = {nullptr, nullptr};
@@ -568,6 +569,7 @@ extern "C" int rb_dev_scan_records(rb_ctx *ctx, const rb_batch_view *b, rb_reduc
     p.norm_rows = norm_rows;
     p.list = nullptr;
     p.n_list = nullptr;
+    ctx->scan_rows_n = 0;
     // a batch of short records (config 4's shape: a few hundred ops each) goes through the row form, four records per wavefront, and
     // only what that lists through the wave-per-record kernel
     if (b->n_rec >= 64 && b->n_ops / b->n_rec <= RB_SCAN_ROWS_MEAN_MAX) {
@@ -582,10 +584,25 @@ extern "C" int rb_dev_scan_records(rb_ctx *ctx, const rb_batch_view *b, rb_reduc
         if (ctx->scan_list) {
             HIPCHK(ctx, rb_fill_async(ctx->scan_list, 0, 8, ctx->stream));
             HIPCHK(ctx, rb_launch_scan_rows(&p, ctx->scan_list, ctx->stream));
+            ctx->scan_rows_n = b->n_rec;
             return RB_OK;
         }
     }
     HIPCHK(ctx, rb_launch_scan_records(&p, ctx->stream));
+    return RB_OK;
+}
+
+// which kernel scanned what in the last rb_dev_scan_records call of this context: the list's count is still on the device
+extern "C" int rb_ctx_scan_route(rb_ctx *ctx, uint64_t out[2]) {
+    if (!ctx || !out) return RB_E_INVALID;
+    out[0] = out[1] = 0;
+    if (!ctx->scan_rows_n) return RB_OK; // the wave-per-record kernel took the whole batch (or nothing was scanned yet)
+    unsigned long long n_listed = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpyAsync(&n_listed, ctx->scan_list, sizeof n_listed, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    out[0] = ctx->scan_rows_n - n_listed;
+    out[1] = n_listed;
     return RB_OK;
 }
 

@@ -276,9 +276,12 @@ __global__ __launch_bounds__(256) void rb_k_scan_records(rb_scan_params p) {
                             } else {
                                 v_big |= 8u;
                                 // a continuation word: bits 28.. of the length of the op in front of it (no event of its own)
-                                if (opc == RB_OP_CONT && (prevw & 15u) <= 8u)
-                                    __hip_atomic_fetch_add(&hist[prevw & 15u][my_hist], (unsigned long long)(len & 15u) << RB_LEN_BITS_WORD, __ATOMIC_RELAXED,
-                                                           __HIP_MEMORY_SCOPE_WORKGROUP);
+                                // any other word of a code above 8 is an op of an unknown type: it consumes nothing, its length counts in the unit
+                                // total alone (kept with P's, which only the unit total sees)
+                                const bool cont = opc == RB_OP_CONT && (prevw & 15u) <= 8u;
+                                __hip_atomic_fetch_add(&hist[cont ? (prevw & 15u) : (uint32_t)RB_OP_P][my_hist],
+                                                       cont ? (unsigned long long)(len & 15u) << RB_LEN_BITS_WORD : (unsigned long long)len, __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_WORKGROUP);
                             }
                             v_reg &= (uint32_t)__builtin_amdgcn_sbfe((int)0x018F018Fu, w, 1u); // M I D N = X
                             v_minlen = v_minlen < len ? v_minlen : len;
@@ -428,9 +431,12 @@ __global__ __launch_bounds__(256) void rb_k_scan_rows(rb_scan_params p, unsigned
                             } else {
                                 v_big |= 8u;
                                 // a continuation word: bits 28.. of the length of the op in front of it (no event of its own)
-                                if (opc == RB_OP_CONT && (prevw & 15u) <= 8u)
-                                    __hip_atomic_fetch_add(&hist[prevw & 15u][lane], (unsigned long long)(len & 15u) << RB_LEN_BITS_WORD, __ATOMIC_RELAXED,
-                                                           __HIP_MEMORY_SCOPE_WORKGROUP);
+                                // any other word of a code above 8 is an op of an unknown type: it consumes nothing, its length counts in the unit
+                                // total alone (kept with P's, which only the unit total sees)
+                                const bool cont = opc == RB_OP_CONT && (prevw & 15u) <= 8u;
+                                __hip_atomic_fetch_add(&hist[cont ? (prevw & 15u) : (uint32_t)RB_OP_P][lane],
+                                                       cont ? (unsigned long long)(len & 15u) << RB_LEN_BITS_WORD : (unsigned long long)len, __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_WORKGROUP);
                             }
                             v_reg &= (uint32_t)__builtin_amdgcn_sbfe((int)0x018F018Fu, w, 1u); // M I D N = X
                             v_minlen = v_minlen < len ? v_minlen : len;
