@@ -1,4 +1,4 @@
-// rb_lift.h -- parameters and device helpers of the liftover / break-paf clip kernels (k_liftover.hip; also included by
+// rb_lift.h -- parameters and device helpers of the liftover / break-paf clip kernels (k_liftover.hip, rb_stream.h; also included by
 // capi.hip for the launch parameters): window search, per-boundary resolution, the per-pass window setup.
 #pragma once
 #include "rb_device.h"
@@ -8,9 +8,7 @@
 #define RB_HMAX 32            // hits resolved per streaming pass of one record (lanes 0-31 starts, 32-63 ends)
 #define RB_LDS_PER_HIT 6      // dwords of per-hit (start) state in LDS
 #define RB_ARENA_STRIDE 16    // u64 words between arena cursors (128 B)
-#ifndef RB_MS
 #define RB_MS 2               // positional copies ("slots") of the batch the streaming kernel can emit clips into
-#endif
 
 // One clip job per schedule slot, 64 bytes, written by rb_k_make_jobs after the hit scan: everything a wave needs to
 // start streaming its record arrives with one load instead of a chain of dependent ones (schedule -> record row ->
@@ -218,7 +216,7 @@ __device__ inline void rb_defer_record(rb_kparams kp, uint32_t r, const rb_norm_
 
 // ---- lane-local boundary resolution --------------------------------------------------------------
 // One lane resolves one window boundary.  It starts from a checkpoint (exclusive prefixes R,Q,U at an
-// op index that is a multiple of 16, written to LDS by the streaming pass), walks at most 16 ops held
+// op index that is a multiple of RB_CP_OPS, written to LDS by the streaming pass), walks at most RB_CP_OPS ops held
 // in registers to the reference-consuming op that contains offset D, then applies the reference's
 // tpos_to_idx + walk-to-match rules (paf.rs:541-561) with short look-ahead / look-back loads.
 struct rb_bres {
@@ -242,9 +240,7 @@ __device__ __forceinline__ bool rb_ism(uint32_t v) { return rb_in(RB_MATCH_MASK,
 
 // ops[] = the record's kept ops, n of them.  (cR,cQ,cU) = prefixes at op index cidx (checkpoint).
 // D in [cR, next checkpoint's R) and D < Rtot.  is_start selects search-right (true) / search-left.
-#ifndef RB_CP_OPS
-#define RB_CP_OPS 8 // ops between two checkpoints of the streaming kernel (16: every second lane leaves one; 8: every lane)
-#endif
+#define RB_CP_OPS 8 // ops between two checkpoints of the streaming kernel: every lane leaves one
 // Round 3: the search inside the checkpoint group is branch-free.  With the exclusive prefixes R_k of the reference lengths,
 // "R_{k+1} <= D" is a monotone predicate p_k over the group's ops (ops in front of or behind the record count as M of length 0), so
 // the op f that holds offset D is the first one with p_k false, its index the number of true ones, and the prefixes at f are the
@@ -262,10 +258,6 @@ __device__ __forceinline__ rb_bres rb_resolve(const uint32_t *__restrict__ ops, 
         const uint4 *q = reinterpret_cast<const uint4 *>(ops + cidx); // 16-byte aligned by construction
         const uint4 a0 = q[0], a1 = q[1];
         g[0] = a0.x; g[1] = a0.y; g[2] = a0.z; g[3] = a0.w; g[4] = a1.x; g[5] = a1.y; g[6] = a1.z; g[7] = a1.w;
-#if RB_CP_OPS == 16
-        const uint4 a2 = q[2], a3 = q[3];
-        g[8] = a2.x; g[9] = a2.y; g[10] = a2.z; g[11] = a2.w; g[12] = a3.x; g[13] = a3.y; g[14] = a3.z; g[15] = a3.w;
-#endif
         pv = ops[cidx > 0 ? cidx - 1 : 0]; // the op in front of the group (used only where the group's first op is f and f > 0)
     }
     uint32_t np = 0, fR = cR, fQ = cQ, fU = cU, fv = 0;

@@ -1,5 +1,5 @@
-"""The streaming clip kernel keeps its load ring in VGPRs v80..v95 that the compiler must not touch (k_liftover.hip: amdgpu_num_vgpr(80),
-the ring named literally in inline asm).  tools/check_ring.py (also run by the Makefile on every build) compiles the kernels to assembly
+"""The streaming clip kernel keeps its load ring in VGPRs v80..v95 that the compiler must not touch (rb_stream.h as k_liftover.hip includes
+it: amdgpu_num_vgpr(80), the ring named literally in inline asm).  tools/check_ring.py (also run by the Makefile on every build) compiles the kernels to assembly
 and fails if anything outside the inline-asm blocks of rb_k_liftover_stream names a register of the ring, single or inside a tuple."""
 import os
 import sys

@@ -1,9 +1,10 @@
 """Guard for the streaming clip kernel's load ring: VGPRs v80..v95 are reserved outside the compiler's allocation
-(k_liftover.hip: amdgpu_num_vgpr(80), the ring named literally in inline asm).  Nothing in the language guarantees that the
-compiler stays out of them, so this script compiles k_liftover.hip to assembly (hipcc cross-compiles without a GPU) and fails
-if any instruction outside the inline-asm blocks of rb_k_liftover_stream names a register in the ring -- a single register
+(rb_stream.h as k_liftover.hip includes it: amdgpu_num_vgpr(80), the ring named literally in inline asm).  Nothing in the language
+guarantees that the compiler stays out of them, so this script compiles k_liftover.hip to assembly (hipcc cross-compiles without a GPU)
+and fails if any instruction outside the inline-asm blocks of rb_k_liftover_stream names a register in the ring -- a single register
 v80..v95 or ANY tuple v[a:b] whose range intersects it (v[78:81] as well as v[80:83]).  Run by the Makefile on every build of
-k_liftover.o and by tests/test_ring_registers.py.  `--tile`: the same for the tile kernel's ring (k_tile.hip, rb_k_liftover_tile*)."""
+k_liftover.o and by tests/test_ring_registers.py.  `--list`: the same body over a list of records (k_liftover_list.hip), ring at
+v88..v103.  `--tile`: the tile kernel's ring (k_tile.hip, rb_k_liftover_tile*), v80..v95."""
 import os
 import re
 import subprocess
@@ -11,7 +12,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RING = (80, 95)
+RING = (80, 95)  # k_liftover.hip and k_tile.hip
+LIST_RING = (88, 103)  # k_liftover_list.hip
 _SINGLE = re.compile(r"\bv(\d+)\b")
 _TUPLE = re.compile(r"\bv\[(\d+):(\d+)\]")
 
@@ -61,37 +63,24 @@ def compile_to_asm(hipcc, extra=(), source="k_liftover.hip"):
         return open(out).read()
 
 
-def ring_of(flags, macro="RB_RING_BASE"):
-    """The ring a build uses: v80..v95 unless -DRB_RING_BASE=<n> (k_tile.hip: -DRBT_RING_BASE=<n>) moves it."""
-    base, pf = RING[0], 2
-    for f in flags:
-        m = re.match(r"-D" + macro + r"=(\d+)$", f)
-        if m:
-            base = int(m.group(1))
-        m = re.match(r"-DRBT?_PF=(\d+)$", f)
-        if m:
-            pf = int(m.group(1))
-    return (base, base + 8 * pf - 1)
-
-
 if __name__ == "__main__":
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     args = sys.argv[1:]
     tile = "--tile" in args  # k_tile.hip instead of k_liftover.hip
     args = [a for a in args if a != "--tile"]
-    lst = "--list" in args  # k_liftover_list.hip: the list form of the per-record kernel, ring at v88..v103
+    lst = "--list" in args  # k_liftover_list.hip: the list form of the per-record kernel
     args = [a for a in args if a != "--list"]
     if lst:
         text = compile_to_asm(hipcc, args, "k_liftover_list.hip")
-        bad = check_assembly(text, 2, (88, 103))
+        bad = check_assembly(text, 2, LIST_RING)
         sp = spills(text)
     elif tile:
         text = compile_to_asm(hipcc, args, "k_tile.hip")
-        bad = check_assembly(text, 2, ring_of(args, "RBT_RING_BASE"), "rb_k_liftover_tile")
+        bad = check_assembly(text, 2, RING, "rb_k_liftover_tile")
         sp = spills(text, "rb_k_liftover_tile")
     else:
         text = compile_to_asm(hipcc, args)
-        bad = check_assembly(text, ring=ring_of(args))
+        bad = check_assembly(text)
         sp = spills(text)
     for k, ln in bad[:10]:
         print(f"ring register used by the compiler in {k}: {ln}", file=sys.stderr)
