@@ -8,7 +8,8 @@
 // strand, the two records' runs are merged, and the first arg-max of prefix(left) + suffix(right)
 // (trim_overlap.rs:69-76) is found from run ends.  One thread per pair, serial: the pairs of one pass are
 // independent (one pair per query name and pass, paf.rs:264-284); the pass/recursion driver stays on the
-// host.  Fully general (all op codes, both binary-search policies).
+// host.  Fully general (all op codes, both binary-search policies).  The wave-per-pair form further down takes the regular records
+// under either policy (a template parameter, LEG: one instantiation each) and cuts them in place; what it declines comes here.
 #include "rb_trim.h"
 #include "rb_launch.h"
 #include <algorithm>
@@ -326,13 +327,14 @@ __device__ void rb_serial_pair(const rb_trim_params &p, const uint64_t pi) {
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Wave-per-pair form for the common case: both records REGULAR (only M I D N = X, every length >= 1, no two adjacent ops of one
-// type, a match-type op at both ends) of any length whose overlap spans at most RB_TW_CAP - 128 ops, modern binary-search policy.  Every question the serial
+// type, a match-type op at both ends) of any length whose overlap spans at most RB_TW_CAP - 128 ops, either binary-search policy (LEG).  Every question the serial
 // kernel answers by walking the ops becomes a binary search in prefix arrays built once per record with wave scans:
 // the op words are staged in LDS together with exclusive prefixes built with wave scans:
 //   Qc[i] query bases before op i     (a query offset x lies in the query-consuming op with Qc <= x < Qc + len)
 //   SP[i] score of the query bases before op i, in op order (score_of_qpos, trim_overlap.rs:6-19: an op's own score for all its
 //         bases but the last one in op order, which -- modern policy: last equal element -- takes the score of the last D / N
-//         op that follows before the next query op)
+//         op that follows before the next query op; legacy policy: the score of the unit the old search probes first in the equal
+//         range [klo, klo + run] of that base, rb_legacy_probe32 -- the op's own last unit or one of the run's, of however many ops)
 //   checkpoints every 16 ops of the units (U), query bases and reference bases before the op
 // A wave-uniform search is one ballot over the checkpoints plus the 16 ops of the chunk side by side; the per-lane searches of
 // the split candidates are binary searches in Qc.
@@ -377,7 +379,7 @@ struct rb_wpos { // an op (i = n: none) and the exclusive prefix of the searched
 
 
 // Stage the region of v that holds the query offsets [xa, xb] (op order).  false: it does not fit RB_TW_CAP ops.
-template <int CAP>
+template <int CAP, bool LEG>
 __device__ bool rb_tw_stage(rb_wrec &v, int lane, int32_t ms, int32_t ds, int32_t is, uint32_t xa, uint32_t xb) {
     v.bad = false;
     // phase A: 64 ops at a time from the record's first op, totals only, up to the step that holds xb; the region starts one step
@@ -496,6 +498,31 @@ __device__ bool rb_tw_stage(rb_wrec &v, int lane, int32_t ms, int32_t ds, int32_
         const uint32_t opc = rb_opc(w), len = in ? rb_len(w) : 0u;
         const bool q = in && rb_in(RB_QRY_MASK, opc), r = in && rb_in(RB_REF_MASK, opc);
         int32_t mm = 0;
+        uint32_t iu = 0;
+        if constexpr (LEG) {
+            // legacy policy: the last base takes the score of the unit the search probes first in the equal range [klo, klo + run]
+            // (rb_legacy_probe32) -- the op's own last unit or one inside the run behind it, of however many ops --, which depends on
+            // where the range lies in the record: the unit scan comes first, then the scores, a lane per op as before
+            iu = rb_wave_scan_incl(len);
+            if (q) {
+                const int32_t own = rb_tw_score(opc, ms, ds, is);
+                int32_t sp = own;
+                uint32_t run = 0;
+                for (uint32_t j = k + 1; !rb_in(RB_QRY_MASK, rb_opc(v.w[j])); j++) run += rb_len(v.w[j]); // (the sentinel at w[m] stops it)
+                if (run) {
+                    const uint32_t klo = Ub + iu - 1u, kk = rb_legacy_probe32(v.N, klo, klo + run);
+                    if (kk != klo) {
+                        uint32_t u = klo + 1u;
+                        for (uint32_t j = k + 1; !rb_in(RB_QRY_MASK, rb_opc(v.w[j])); j++) { // the run op that holds unit kk
+                            sp = rb_tw_score(rb_opc(v.w[j]), ms, ds, is);
+                            u += rb_len(v.w[j]);
+                            if (kk < u) break;
+                        }
+                    }
+                }
+                mm = (int32_t)(len - 1u) * own + sp;
+            }
+        } else
         if (q) { // own score for all bases but the last in op order, which takes the score of the last D / N op of the run behind it
             int32_t sp = rb_tw_score(opc, ms, ds, is);
             const int32_t own = sp;
@@ -507,7 +534,8 @@ __device__ bool rb_tw_stage(rb_wrec &v, int lane, int32_t ms, int32_t ds, int32_
             }
             mm = (int32_t)(len - 1u) * own + sp;
         }
-        const uint32_t iu = rb_wave_scan_incl(len), iq = rb_wave_scan_incl(q ? len : 0u), ir = rb_wave_scan_incl(r ? len : 0u);
+        if constexpr (!LEG) iu = rb_wave_scan_incl(len);
+        const uint32_t iq = rb_wave_scan_incl(q ? len : 0u), ir = rb_wave_scan_incl(r ? len : 0u);
         const int32_t isc = (int32_t)rb_wave_scan_incl((uint32_t)mm);
         if (in) {
             v.Qc[k] = Qb + iq - (q ? len : 0u);
@@ -625,6 +653,7 @@ struct rb_wcut { // in-place clip: the two words to rewrite (absolute indices in
     uint64_t at_first, at_last;
     uint32_t w_first, w_last;
 };
+template <bool LEG>
 __device__ uint32_t rb_tw_clip(rb_wrec &v, uint64_t new_q_st, uint64_t new_q_en, uint32_t *out, rb_pair_row *row, int s, uint64_t out_base,
                                int lane, rb_wcut *cut = nullptr, uint64_t rec_base = 0) {
     if (!(new_q_st >= v.q_st) || !(new_q_en <= v.q_en) || new_q_en == 0) return RB_ST_PANIC_ASSERT; // :787-788
@@ -634,7 +663,8 @@ __device__ uint32_t rb_tw_clip(rb_wrec &v, uint64_t new_q_st, uint64_t new_q_en,
     }
     const uint32_t n = v.n, N = v.N;
     // the match-type unit truncate_record_by_query ends up at for query position p: qpos_to_idx_match (paf.rs:564-590) = the last
-    // unit whose qpos equals p (modern policy), then the nearest match-type unit in the search direction
+    // unit whose qpos equals p (modern policy) or the one the legacy search probes first (LEG), then the nearest match-type unit in the
+    // search direction
     auto resolve = [&](uint64_t p, bool search_up, rb_wend *e) -> bool {
         if (p < v.q_st || p >= v.q_en) return false;
         const uint32_t x = (uint32_t)(v.minus ? v.q_en - 1 - p : p - v.q_st);
@@ -663,8 +693,18 @@ __device__ uint32_t rb_tw_clip(rb_wrec &v, uint64_t new_q_st, uint64_t new_q_en,
         bool moved = false; // the unit left the op that holds the base
         if (j + 1u == len) { // last base of the op: the D / N units behind it repeat its position
             uint32_t k2 = o.i - v.i0 + 1u;
+            if constexpr (LEG) {
+                uint32_t run = 0;
+                for (; k2 < v.m && !rb_in(RB_QRY_MASK, rb_opc(v.w[k2])); k2++) run += rb_len(v.w[k2]);
+                if (k2 >= v.m && v.i0 + v.m < n) return false; // (the run leaves the region)
+                if (run) { // the equal range is [u, u + run]: the unit is where the probe lands
+                    const uint32_t kk = rb_legacy_probe32(N, u, u + run);
+                    moved = kk != u, u = kk;
+                }
+            } else {
             for (; k2 < v.m && !rb_in(RB_QRY_MASK, rb_opc(v.w[k2])); k2++) u += rb_len(v.w[k2]), moved = true;
             if (k2 >= v.m && v.i0 + v.m < n) return false; // (the run leaves the region)
+            }
         }
         // nearest match-type unit, up (paf.rs:581-583) or down (:585-587); the op that holds unit u is the one just found unless the
         // unit moved into the run behind it (round 3: the second search is skipped then -- it was a tenth of a pair's instructions)
@@ -762,7 +802,7 @@ __device__ uint32_t rb_tw_clip(rb_wrec &v, uint64_t new_q_st, uint64_t new_q_en,
     return RB_ST_OK;
 }
 
-template <int CAP>
+template <int CAP, bool LEG>
 __device__ void rb_tw_pair(const rb_trim_params &p, const uint64_t pi, uint32_t (*lds_w)[3][CAP + 1], uint32_t (*lds_c)[3][CAP / 16 + 2]) {
     const int lane = rb_lane();
     rb_pair_row w;
@@ -789,7 +829,8 @@ __device__ void rb_tw_pair(const rb_trim_params &p, const uint64_t pi, uint32_t 
             p.rows[pi].status = RB_ST_PENDING_INTERNAL, p.rows[pi].split_idx = why;
         }
     };
-    if (p.policy == RB_BSEARCH_LEGACY || !(nl->flags & RB_F_REGULAR) || !(nr->flags & RB_F_REGULAR) || nl->n_ops == 0 || nr->n_ops == 0) {
+    // (LEG: this instantiation serves the legacy policy; the modern one declines it -- rb_launch_overlap_split picks by p->policy)
+    if ((!LEG && p.policy == RB_BSEARCH_LEGACY) || !(nl->flags & RB_F_REGULAR) || !(nr->flags & RB_F_REGULAR) || nl->n_ops == 0 || nr->n_ops == 0) {
         pending(1);
         return;
     }
@@ -818,11 +859,11 @@ __device__ void rb_tw_pair(const rb_trim_params &p, const uint64_t pi, uint32_t 
     span(L, &lxa, &lxb);
     span(R, &rxa, &rxb);
 #if RB_TW_STOP == 1
-    if (!rb_tw_stage<CAP>(L, lane, ms, ds, is, lxa, lxb)) pending(3);
+    if (!rb_tw_stage<CAP, LEG>(L, lane, ms, ds, is, lxa, lxb)) pending(3);
     if (lane == 0) p.rows[pi].split_idx = L.m;
     return;
 #endif
-    if (!rb_tw_stage<CAP>(L, lane, ms, ds, is, lxa, lxb) || !rb_tw_stage<CAP>(R, lane, ms, ds, is, rxa, rxb)) { // an overlap of more ops than the region holds
+    if (!rb_tw_stage<CAP, LEG>(L, lane, ms, ds, is, lxa, lxb) || !rb_tw_stage<CAP, LEG>(R, lane, ms, ds, is, rxa, rxb)) { // an overlap of more ops than the region holds
         pending(3);
         return;
     }
@@ -925,14 +966,14 @@ __device__ void rb_tw_pair(const rb_trim_params &p, const uint64_t pi, uint32_t 
     const uint64_t ob = p.pair_out_off[pi];
     rb_wcut cutL, cutR;
     const bool inpl = p.in_place != 0;
-    uint32_t st = rb_tw_clip(L, L.q_st, split, p.out_ops + ob, &w, 0, ob, lane, inpl ? &cutL : nullptr, (uint64_t)(L.ops - p.ops)); // trim_overlap.rs:77
+    uint32_t st = rb_tw_clip<LEG>(L, L.q_st, split, p.out_ops + ob, &w, 0, ob, lane, inpl ? &cutL : nullptr, (uint64_t)(L.ops - p.ops)); // trim_overlap.rs:77
 #if RB_TW_STOP == 5
     if (lane == 0) p.rows[pi] = w;
     return;
 #endif
     if (st == RB_ST_OK && !L.bad) {
         const uint64_t ob2 = ob + L.n;
-        st = rb_tw_clip(R, split, R.q_en, p.out_ops + ob2, &w, 1, ob2, lane, inpl ? &cutR : nullptr, (uint64_t)(R.ops - p.ops)); // :78
+        st = rb_tw_clip<LEG>(R, split, R.q_en, p.out_ops + ob2, &w, 1, ob2, lane, inpl ? &cutR : nullptr, (uint64_t)(R.ops - p.ops)); // :78
     }
     if (L.bad || R.bad) { // a boundary the region cannot answer: the serial kernel does the pair (it rewrites both clips)
         pending(L.bad ? 5 : 6);
@@ -977,16 +1018,16 @@ __device__ __forceinline__ bool rb_tw_walk_next(const rb_trim_params &p, rb_tw_w
 #ifndef RB_TW_WPE
 #define RB_TW_WPE 8
 #endif
-template <int CAP>
+template <int CAP, bool LEG>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RB_TW_WPE))) void rb_k_overlap_split_wave(rb_trim_params p) {
     __shared__ uint32_t lds_w[2][3][CAP + 1];
     __shared__ uint32_t lds_c[2][3][CAP / 16 + 2];
-    if (blockIdx.x < p.n_pairs) rb_tw_pair<CAP>(p, blockIdx.x, lds_w, lds_c);
+    if (blockIdx.x < p.n_pairs) rb_tw_pair<CAP, LEG>(p, blockIdx.x, lds_w, lds_c);
 }
 // third attempt: the region arrays of a wavefront live in a slab of device memory (same code: the arrays are pointers).  Stores
 // and loads of one wavefront go through its CU's vector L1 in program order, so a lane sees what another lane of its own wave
 // has stored (wavefront-scope fences are empty on this target for exactly that reason).
-template <int CAP>
+template <int CAP, bool LEG>
 __global__ __launch_bounds__(64) void rb_k_overlap_split_wave_scratch(rb_trim_params p) {
     if (!p.scratch || blockIdx.x >= p.scratch_blocks) return;
     uint32_t *slab = p.scratch + (size_t)blockIdx.x * RB_TW_SLAB_WORDS(CAP);
@@ -995,26 +1036,28 @@ __global__ __launch_bounds__(64) void rb_k_overlap_split_wave_scratch(rb_trim_pa
     rb_tw_walker wk;
     rb_tw_walk_begin(p, wk);
     for (uint64_t pi; rb_tw_walk_next(p, wk, &pi);) {
-        rb_tw_pair<CAP>(p, pi, aw, ac);
+        rb_tw_pair<CAP, LEG>(p, pi, aw, ac);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         __builtin_amdgcn_wave_barrier();
     }
 }
 // second attempt, for the pairs the first one left: a few wavefronts with a large region each walk the list
-template <int CAP>
+template <int CAP, bool LEG>
 __global__ __launch_bounds__(64) void rb_k_overlap_split_wave_pending(rb_trim_params p) {
     __shared__ uint32_t lds_w[2][3][CAP + 1];
     __shared__ uint32_t lds_c[2][3][CAP / 16 + 2];
     rb_tw_walker wk;
     rb_tw_walk_begin(p, wk);
     for (uint64_t pi; rb_tw_walk_next(p, wk, &pi);) {
-        rb_tw_pair<CAP>(p, pi, lds_w, lds_c);
+        rb_tw_pair<CAP, LEG>(p, pi, lds_w, lds_c);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // (the LDS arrays are reused by the next pair)
         __builtin_amdgcn_wave_barrier();
     }
 }
 extern "C" size_t rb_trim_scratch_bytes(uint32_t blocks) { return (size_t)blocks * RB_TW_SLAB_WORDS(RB_TW_CAP3) * 4u; }
-extern "C" hipError_t rb_launch_overlap_split(const rb_trim_params *p, hipStream_t stream) {
+// one instantiation of every wave kernel per binary-search policy: the modern code is what it was before the legacy one existed
+template <bool LEG>
+static hipError_t rb_launch_overlap_split_policy(const rb_trim_params *p, hipStream_t stream) {
     if (p->n_pairs == 0) return hipSuccess;
     rb_trim_params q = *p;
     q.only_pending = 0;
@@ -1027,18 +1070,18 @@ extern "C" hipError_t rb_launch_overlap_split(const rb_trim_params *p, hipStream
         e = rb_launch_overlap_split_quad(&q, 8, true, stream); // the pairs whose overlap does not fit 64 ops of a record's end: 128
         if (e != hipSuccess) return e;
         const unsigned g0 = (unsigned)(p->n_pairs < 8192 ? p->n_pairs : 8192);
-        hipLaunchKernelGGL(rb_k_overlap_split_wave_pending<RB_TW_CAP>, dim3(g0), dim3(64), 0, stream, q);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_wave_pending<RB_TW_CAP, LEG>), dim3(g0), dim3(64), 0, stream, q);
     } else {
-        hipLaunchKernelGGL(rb_k_overlap_split_wave<RB_TW_CAP>, dim3((unsigned)p->n_pairs), dim3(64), 0, stream, q);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_wave<RB_TW_CAP, LEG>), dim3((unsigned)p->n_pairs), dim3(64), 0, stream, q);
     }
     q.only_pending = 2; // (the attempts behind the first walk its list; what they decline is listed already)
     const unsigned g1 = (unsigned)(p->n_pairs < 8192 ? p->n_pairs : 8192);
-    hipLaunchKernelGGL(rb_k_overlap_split_wave_pending<RB_TW_CAP1>, dim3(g1), dim3(64), 0, stream, q);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_wave_pending<RB_TW_CAP1, LEG>), dim3(g1), dim3(64), 0, stream, q);
     const unsigned g2 = (unsigned)(p->n_pairs < 2048 ? p->n_pairs : 2048);
-    hipLaunchKernelGGL(rb_k_overlap_split_wave_pending<RB_TW_CAP2>, dim3(g2), dim3(64), 0, stream, q);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_wave_pending<RB_TW_CAP2, LEG>), dim3(g2), dim3(64), 0, stream, q);
     if (q.scratch && q.scratch_blocks) {
         const unsigned g3 = (unsigned)(p->n_pairs < q.scratch_blocks ? p->n_pairs : q.scratch_blocks);
-        hipLaunchKernelGGL(rb_k_overlap_split_wave_scratch<RB_TW_CAP3>, dim3(g3), dim3(64), 0, stream, q);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_wave_scratch<RB_TW_CAP3, LEG>), dim3(g3), dim3(64), 0, stream, q);
     }
     q.only_pending = 1;
     static const bool no_serial = getenv("RB_DEBUG_TRIM_NO_SERIAL") != nullptr; // diagnostics: leave what the wave kernels declined as it is
@@ -1046,6 +1089,9 @@ extern "C" hipError_t rb_launch_overlap_split(const rb_trim_params *p, hipStream
     const uint64_t sblocks = q.pend_list ? std::min<uint64_t>((p->n_pairs + 63) / 64, 256) : (p->n_pairs + 63) / 64;
     hipLaunchKernelGGL(rb_k_overlap_split, dim3((unsigned)sblocks), dim3(64), 0, stream, q);
     return hipGetLastError();
+}
+extern "C" hipError_t rb_launch_overlap_split(const rb_trim_params *p, hipStream_t stream) {
+    return p->policy == RB_BSEARCH_LEGACY ? rb_launch_overlap_split_policy<true>(p, stream) : rb_launch_overlap_split_policy<false>(p, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

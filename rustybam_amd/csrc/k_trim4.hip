@@ -1,6 +1,7 @@
 // k_trim4.hip -- trim-paf pair kernel, FOUR pairs per wavefront (gfx950): trim_overlapping_pafs (trim_overlap.rs:36-86) followed by
-// truncate_record_by_query on both records (paf.rs:785-823), for the common case -- both records REGULAR (rb_norm_row.flags), modern
-// binary-search policy, and the overlap within 16 T ops of one END of each record.
+// truncate_record_by_query on both records (paf.rs:785-823), for the common case -- both records REGULAR (rb_norm_row.flags) and the
+// overlap within 16 T ops of one END of each record.  Both binary-search policies: the policy is a template parameter (LEG), one
+// instantiation each, and the modern one is the code it was before the legacy one existed (profiles/r07_c4_legacy_summary.md).
 //
 // Why: the pairs of a pass overlap at the ends of their records (the left record's last query bases, the right record's first), a few
 // dozen ops; the wave-per-pair kernel (k_trim.hip) gives each of them 64 lanes and ~4100 instructions, most of them wave-uniform, and is
@@ -14,9 +15,16 @@
 //   * searches by query offset: a ballot over the 16 lanes' chunk bases, then the T ops of that chunk side by side; per-lane searches
 //     of the split candidates: a branch-free descent through the query prefixes in LDS.
 // Same arrays, same formulas and the same order of exits as rb_tw_pair (k_trim.hip) -- the two are checked against each other and
-// against the oracle by tests/test_gpu_trim.py and tests/soak/soak_trim.py.  A pair this kernel does not take (irregular record, legacy
-// policy, region too small, a walk that leaves the region, a non-query run of T ops) is listed in pend_list and done by the kernels
-// behind it: the wave-per-pair kernel with its larger regions, then the serial one.
+// against the oracle by tests/test_gpu_trim.py, tests/test_gpu_trim_legacy.py and tests/soak/soak_trim.py.  A pair this kernel does not
+// take (irregular record, region too small, a walk that leaves the region, a non-query run of T ops; under the legacy policy also a D / N
+// run of more than one op) is listed in pend_list and done by the kernels behind it: the wave-per-pair kernel with its larger regions,
+// then the serial one.
+//
+// The policy matters in one place: a query position that repeats in qpos_aln -- the last base (in op order) of a query op i that a run
+// of D / N ops of `run` units follows.  Its equal range is [klo, klo + run], klo = U_i + len_i - 1 (U_i: units before op i); the modern
+// search returns klo + run, the legacy one rb_legacy_probe32(N, klo, klo + run) (indices only: the same on both strands).  That unit
+// decides the score of the base (rb_q4_build) and where a cut that ends on it lands (rb_q4_clip); the split reads the score prefixes
+// and needs no policy of its own.
 #include "rb_trim.h"
 #include "rb_launch.h"
 
@@ -81,7 +89,7 @@ __device__ __forceinline__ void rb_q4_load(rb_qrec &v, uint32_t gl, uint32_t (&t
 }
 
 // prefixes of the region, into LDS.  false: a chunk of T ops without a query op (the run behind a last base would cross a lane).
-template <int T>
+template <int T, bool LEG>
 __device__ __forceinline__ bool rb_q4_build(rb_qrec &v, rb_q4_slab<T> &S, uint32_t gl, uint32_t gbase, uint32_t (&t)[T], bool from_end, int32_t ms,
                                             int32_t ds, int32_t is) {
     const uint32_t k0 = gl * T;
@@ -103,12 +111,52 @@ __device__ __forceinline__ bool rb_q4_build(rb_qrec &v, rb_q4_slab<T> &S, uint32
         if (q && in) hq = e;
     }
     if (rb_row_ballot(lead, gbase)) return false;
+    uint32_t iu = 0, tu = 0, bU = 0;
+    int32_t mm[T], ss = 0;
+    if constexpr (LEG) {
+        // legacy policy: which unit of the equal range [klo, klo + run] behind an op's last base the search returns depends on where the
+        // range lies in the record (rb_legacy_probe32), so the absolute unit prefix comes first, then the scores.  Of every two
+        // neighbouring ops at most one is a query op with a run behind it (the other IS the run), so a lane probes T / 2 times, all
+        // lanes side by side.  The run is one op -- in this lane or the next one's first; a run of several ops (D N ...: legal in a
+        // regular record, rare) leaves the pair to the kernels behind this one.
+        iu = rb_row_scan_incl(su), tu = rb_row_last(iu);
+        bU = from_end ? v.N - tu : 0u;
+        const uint32_t nx0 = rb_row_next(t[0]); // (lane 15: zero-length M -- behind the region: none, see lastq)
+        const bool nx1_nq = ((rb_row_ballot(!rb_in(RB_QRY_MASK, rb_opc(t[1])), gbase) >> 1) >> gl) & 1u; // the next lane's second op is no query op
+        uint32_t ue = bU + iu - su; // units before op e
+        bool multi = false;
+#pragma unroll
+        for (int e2 = 0; e2 < T; e2 += 2) {
+            bool run = false;
+            uint32_t klo = 0, rl = 0;
+            int32_t rsc = 0;
+#pragma unroll
+            for (int e = e2; e < e2 + 2; e++) {
+                const uint32_t w = t[e], wn = e + 1 < T ? t[e + 1 < T ? e + 1 : 0] : nx0, wn2 = e + 2 < T ? t[e + 2 < T ? e + 2 : 0] : nx0;
+                const uint32_t opc = rb_opc(w), len = rb_len(w);
+                const bool r = rb_in(RB_QRY_MASK, opc) && len != 0u && !rb_in(RB_QRY_MASK, rb_opc(wn));
+                multi |= r && (e + 2 <= T ? !rb_in(RB_QRY_MASK, rb_opc(wn2)) : nx1_nq);
+                run |= r;
+                klo = r ? ue + len - 1u : klo, rl = r ? rb_len(wn) : rl, rsc = r ? rb_tw_score(rb_opc(wn), ms, ds, is) : rsc;
+                ue += len;
+            }
+            const bool moved = run && rb_legacy_probe32(v.N, klo, klo + rl) != klo;
+#pragma unroll
+            for (int e = e2; e < e2 + 2; e++) {
+                const uint32_t opc = rb_opc(t[e]), len = rb_len(t[e]);
+                const int32_t own = rb_tw_score(opc, ms, ds, is);
+                const bool sp = moved && rb_in(RB_QRY_MASK, opc) && !rb_in(RB_QRY_MASK, rb_opc(e + 1 < T ? t[e + 1 < T ? e + 1 : 0] : nx0));
+                mm[e] = rb_in(RB_QRY_MASK, opc) && len ? (int32_t)(len - 1u) * own + (sp ? rsc : own) : 0;
+                ss += mm[e];
+            }
+        }
+        if (rb_row_ballot(multi, gbase)) return false;
+    } else {
     // the run behind this lane's last op begins in the next lane (behind the region: none -- see lastq)
     const bool nxt_nq = rb_row_next((uint32_t)(!rb_in(RB_QRY_MASK, rb_opc(t[0])))) != 0u;
     const int32_t nxt_e = (int32_t)rb_row_next((uint32_t)efirst);
     // score of every op's query bases: its own for all but the last one in op order, which takes the score of the last D / N op of the
     // run behind it (modern policy: the last equal element of qpos_aln)
-    int32_t mm[T], ss = 0;
     {
         bool nnq = nxt_nq;
         int32_t ne = nxt_e;
@@ -127,10 +175,14 @@ __device__ __forceinline__ bool rb_q4_build(rb_qrec &v, rb_q4_slab<T> &S, uint32
             ss += mm[e];
         }
     }
-    const uint32_t iu = rb_row_scan_incl(su), iq = rb_row_scan_incl(sq), ir = rb_row_scan_incl(sr);
+    }
+    if constexpr (!LEG) iu = rb_row_scan_incl(su);
+    const uint32_t iq = rb_row_scan_incl(sq), ir = rb_row_scan_incl(sr);
     const int32_t isc = (int32_t)rb_row_scan_incl((uint32_t)ss);
-    const uint32_t tu = rb_row_last(iu), tq = rb_row_last(iq), tr = rb_row_last(ir);
-    const uint32_t bU = from_end ? v.N - tu : 0u, bQ = from_end ? v.Qtot - tq : 0u, bR = from_end ? v.Rtot - tr : 0u;
+    if constexpr (!LEG) tu = rb_row_last(iu);
+    const uint32_t tq = rb_row_last(iq), tr = rb_row_last(ir);
+    if constexpr (!LEG) bU = from_end ? v.N - tu : 0u;
+    const uint32_t bQ = from_end ? v.Qtot - tq : 0u, bR = from_end ? v.Rtot - tr : 0u;
     uint32_t cq = bQ + iq - sq;
     int32_t cs = isc - ss;
     v.cq = cq, v.bQ = bQ, v.eQ = bQ + tq;
@@ -193,7 +245,7 @@ __device__ __forceinline__ uint32_t rb_q4_before(const rb_qrec &v, const rb_q4_s
     return rb_row_read(KIND == 0 ? v.cu : v.cr, gbase, c) + rb_row_sum(x);
 }
 // truncate_record_by_query (paf.rs:785-823) on a staged regular record: rb_tw_clip (k_trim.hip) for a row of 16 lanes
-template <int T>
+template <int T, bool LEG>
 __device__ __forceinline__ uint32_t rb_q4_clip(rb_qrec &v, const rb_q4_slab<T> &S, uint64_t new_q_st, uint64_t new_q_en, uint32_t *out, rb_pair_row *row,
                                                int s, uint64_t out_base, uint32_t gl, uint32_t gbase, bool in_place, rb_qcut &cut, uint64_t rec_base) {
     if (!(new_q_st >= v.q_st) || !(new_q_en <= v.q_en) || new_q_en == 0) return RB_ST_PANIC_ASSERT; // :787-788
@@ -203,7 +255,8 @@ __device__ __forceinline__ uint32_t rb_q4_clip(rb_qrec &v, const rb_q4_slab<T> &
     }
     const uint32_t n = v.n, N = v.N;
     // the match-type unit truncate_record_by_query ends up at for query position p: qpos_to_idx_match (paf.rs:564-590) = the last
-    // unit whose qpos equals p (modern policy), then the nearest match-type unit in the search direction
+    // unit whose qpos equals p (modern policy) or the one the legacy search probes first (LEG), then the nearest match-type unit in the
+    // search direction
     auto resolve = [&](uint64_t p, bool search_up, rb_qend *e) -> bool {
         if (p < v.q_st || p >= v.q_en) return false;
         const uint32_t x = (uint32_t)(v.minus ? v.q_en - 1 - p : p - v.q_st);
@@ -230,7 +283,20 @@ __device__ __forceinline__ uint32_t rb_q4_clip(rb_qrec &v, const rb_q4_slab<T> &
         uint32_t u = ub + j;
         rb_qpos om;
         om.i = o.i, om.w = o.w, om.pre = ub;
-        if (j + 1u == len) { // last base of the op: the D / N units behind it repeat its position, and the last of them is the unit
+        if constexpr (LEG) {
+            if (j + 1u == len) { // last base of the op: the D / N units behind it repeat its position; the unit is the one the probe lands on
+                const uint32_t k2 = o.i - v.i0 + 1u;
+                if (k2 >= v.m) {
+                    if (v.i0 + v.m < n) return false; // (the run, if there is one, lies behind the region)
+                } else if (!rb_in(RB_QRY_MASK, rb_opc(S.w[k2]))) {
+                    const uint32_t w2 = S.w[k2];
+                    // (a run that leaves the region or has a second op: the kernels behind this one)
+                    if (k2 + 1u >= v.m ? v.i0 + v.m < n : !rb_in(RB_QRY_MASK, rb_opc(S.w[k2 + 1u]))) return false;
+                    const uint32_t kk = rb_legacy_probe32(N, u, u + rb_len(w2));
+                    if (kk != u) om.i = v.i0 + k2, om.w = w2, om.pre = u + 1u, u = kk;
+                }
+            }
+        } else if (j + 1u == len) { // last base of the op: the D / N units behind it repeat its position, and the last of them is the unit
             uint32_t k2 = o.i - v.i0 + 1u;
             for (; k2 < v.m && !rb_in(RB_QRY_MASK, rb_opc(S.w[k2])); k2++) {
                 const uint32_t w2 = S.w[k2];
@@ -323,7 +389,7 @@ __device__ __forceinline__ uint32_t rb_q4_clip(rb_qrec &v, const rb_q4_slab<T> &
                      // of the overlap's end ops, 3 behind the split, 4 behind the left clip; 9: the whole pair, but a declined pair is listed without the atomic counter
                      // (measured: 2.41 ms with it, 2.39 - 2.41 without, per 2.5e6 pairs); the rows are wrong then, only the time is of interest
 #endif
-template <int T>
+template <int T, bool LEG>
 __device__ __forceinline__ void rb_q4_pair(const rb_trim_params &p, const uint64_t pi, const uint32_t gbase, const uint32_t gl, const uint32_t g) {
     __shared__ __attribute__((aligned(16))) rb_q4_slab<T> lds[4][2]; // (here and not in the kernels: as an argument it would be a generic pointer)
     rb_pair_row w;
@@ -354,7 +420,8 @@ __device__ __forceinline__ void rb_q4_pair(const rb_trim_params &p, const uint64
             p.rows[pi].status = RB_ST_PENDING_INTERNAL, p.rows[pi].split_idx = why;
         }
     };
-    if (p.policy == RB_BSEARCH_LEGACY || !(nl.flags & RB_F_REGULAR) || !(nr.flags & RB_F_REGULAR) || nl.n_ops == 0 || nr.n_ops == 0) {
+    // (LEG: this instantiation serves the legacy policy; the modern one declines it -- rb_launch_overlap_split_quad picks by p->policy)
+    if ((!LEG && p.policy == RB_BSEARCH_LEGACY) || !(nl.flags & RB_F_REGULAR) || !(nr.flags & RB_F_REGULAR) || nl.n_ops == 0 || nr.n_ops == 0) {
         pending(1);
         return;
     }
@@ -396,7 +463,7 @@ __device__ __forceinline__ void rb_q4_pair(const rb_trim_params &p, const uint64
     uint32_t tl[T], tr[T];
     rb_q4_load<T>(L, gl, tl);
     rb_q4_load<T>(R, gl, tr);
-    if (!rb_q4_build<T>(L, SL, gl, gbase, tl, lfe, ms, ds, is) || !rb_q4_build<T>(R, SR, gl, gbase, tr, rfe, ms, ds, is)) {
+    if (!rb_q4_build<T, LEG>(L, SL, gl, gbase, tl, lfe, ms, ds, is) || !rb_q4_build<T, LEG>(R, SR, gl, gbase, tr, rfe, ms, ds, is)) {
         pending(3);
         return;
     }
@@ -564,7 +631,7 @@ __device__ __forceinline__ void rb_q4_pair(const rb_trim_params &p, const uint64
     const uint64_t ob = inpl ? 0ull : p.pair_out_off[pi];
     rb_qcut cutL, cutR;
     unstash(L, SL);
-    uint32_t st = rb_q4_clip<T>(L, SL, L.q_st, split, p.out_ops + ob, &w, 0, ob, gl, gbase, inpl, cutL, (uint64_t)(L.ops - p.ops)); // trim_overlap.rs:77
+    uint32_t st = rb_q4_clip<T, LEG>(L, SL, L.q_st, split, p.out_ops + ob, &w, 0, ob, gl, gbase, inpl, cutL, (uint64_t)(L.ops - p.ops)); // trim_overlap.rs:77
 #if RB_Q4_STOP == 4
     if (gl == 0) p.rows[pi] = w;
     return;
@@ -581,7 +648,7 @@ __device__ __forceinline__ void rb_q4_pair(const rb_trim_params &p, const uint64
     unstash(R, SR);
     if (st == RB_ST_OK && !L.bad) {
         const uint64_t ob2 = ob + L.n;
-        st = rb_q4_clip<T>(R, SR, split, R.q_en, p.out_ops + ob2, &w, 1, ob2, gl, gbase, inpl, cutR, (uint64_t)(R.ops - p.ops)); // :78
+        st = rb_q4_clip<T, LEG>(R, SR, split, R.q_en, p.out_ops + ob2, &w, 1, ob2, gl, gbase, inpl, cutR, (uint64_t)(R.ops - p.ops)); // :78
     }
     if (L.bad || R.bad) { // a boundary the region cannot answer
         pending(L.bad ? 5 : 6);
@@ -611,20 +678,28 @@ __device__ __forceinline__ void rb_q4_pair(const rb_trim_params &p, const uint64
 }
 
 // first attempt: pairs 4 b .. 4 b + 3 to workgroup b
-template <int T>
+template <int T, bool LEG>
 __global__ __launch_bounds__(64) void rb_k_overlap_split_quad(rb_trim_params p) {
     const uint32_t lane = (uint32_t)rb_lane(), gbase = lane & 48u, gl = lane & 15u, g = lane >> 4;
     const uint64_t pi = (uint64_t)blockIdx.x * 4u + g;
-    if (pi < p.n_pairs) rb_q4_pair<T>(p, pi, gbase, gl, g);
+    if (pi < p.n_pairs) rb_q4_pair<T, LEG>(p, pi, gbase, gl, g);
+}
+// the legacy first attempt at T = 4, the kernel nearly every legacy pair ends in: the probes cost it six registers over the modern
+// instantiation's 91, one more than the 96 that five wavefronts per SIMD allow -- so it is told to stay there (96 VGPRs, no scratch:
+// profiles/r07_c4_legacy_summary.md)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void rb_k_overlap_split_quad4_legacy(rb_trim_params p) {
+    const uint32_t lane = (uint32_t)rb_lane(), gbase = lane & 48u, gl = lane & 15u, g = lane >> 4;
+    const uint64_t pi = (uint64_t)blockIdx.x * 4u + g;
+    if (pi < p.n_pairs) rb_q4_pair<4, true>(p, pi, gbase, gl, g);
 }
 // second attempt, with larger regions, for the pairs the first one listed: the workgroups walk the list, four entries at a time
-template <int T>
+template <int T, bool LEG>
 __global__ __launch_bounds__(64) void rb_k_overlap_split_quad_list(rb_trim_params p) {
     const uint32_t lane = (uint32_t)rb_lane(), gbase = lane & 48u, gl = lane & 15u, g = lane >> 4;
     const uint64_t n = *p.pend;
     for (uint64_t e = (uint64_t)blockIdx.x * 4u + g; e < n; e += (uint64_t)gridDim.x * 4u) {
         const uint64_t pi = p.pend_list[e];
-        if (p.rows[pi].status == RB_ST_PENDING_INTERNAL) rb_q4_pair<T>(p, pi, gbase, gl, g);
+        if (p.rows[pi].status == RB_ST_PENDING_INTERNAL) rb_q4_pair<T, LEG>(p, pi, gbase, gl, g);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // (the slabs are reused by the next entry)
         __builtin_amdgcn_wave_barrier();
     }
@@ -632,14 +707,16 @@ __global__ __launch_bounds__(64) void rb_k_overlap_split_quad_list(rb_trim_param
 extern "C" hipError_t rb_launch_overlap_split_quad(const rb_trim_params *p, int t, bool from_list, hipStream_t stream) {
     if (p->n_pairs == 0) return hipSuccess;
     const unsigned blocks = (unsigned)((p->n_pairs + 3) / 4);
-    if (from_list) {
-        const unsigned g = blocks < 16384u ? blocks : 16384u;
-        if (t == 4) hipLaunchKernelGGL(rb_k_overlap_split_quad_list<4>, dim3(g), dim3(64), 0, stream, *p);
-        else hipLaunchKernelGGL(rb_k_overlap_split_quad_list<8>, dim3(g), dim3(64), 0, stream, *p);
-    } else if (t == 4) {
-        hipLaunchKernelGGL(rb_k_overlap_split_quad<4>, dim3(blocks), dim3(64), 0, stream, *p);
-    } else {
-        hipLaunchKernelGGL(rb_k_overlap_split_quad<8>, dim3(blocks), dim3(64), 0, stream, *p);
-    }
+    const unsigned g = blocks < 16384u ? blocks : 16384u;
+    const bool leg = p->policy == RB_BSEARCH_LEGACY; // (one instantiation per policy: the modern code is what it was)
+    auto launch = [&](auto t_, auto leg_) {
+        constexpr int TT = decltype(t_)::value;
+        constexpr bool LG = decltype(leg_)::value;
+        if (from_list) hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_quad_list<TT, LG>), dim3(g), dim3(64), 0, stream, *p);
+        else if constexpr (TT == 4 && LG) hipLaunchKernelGGL(rb_k_overlap_split_quad4_legacy, dim3(blocks), dim3(64), 0, stream, *p);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_quad<TT, LG>), dim3(blocks), dim3(64), 0, stream, *p);
+    };
+    if (t == 4) leg ? launch(std::integral_constant<int, 4>{}, std::true_type{}) : launch(std::integral_constant<int, 4>{}, std::false_type{});
+    else leg ? launch(std::integral_constant<int, 8>{}, std::true_type{}) : launch(std::integral_constant<int, 8>{}, std::false_type{});
     return hipGetLastError();
 }

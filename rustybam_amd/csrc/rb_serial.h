@@ -41,6 +41,23 @@ __device__ inline uint64_t rb_s_legacy_probe(uint64_t N, uint64_t klo, uint64_t 
     return klo;
 }
 
+// the same probe in 32 bits, for the kernels that keep a lane per op (k_trim.hip's wave form, k_trim4.hip): a record's unit count fits
+// (rb_norm_row.aln_len), mid < N never overflows, and a step is a handful of 32-bit VALU instructions
+__device__ __forceinline__ uint32_t rb_legacy_probe32(uint32_t N, uint32_t klo, uint32_t khi) {
+    uint32_t size = N, left = 0, right = N;
+    while (left < right) {
+        const uint32_t mid = left + size / 2u;
+        if (mid < klo)
+            left = mid + 1u;
+        else if (mid > khi)
+            right = mid;
+        else
+            return mid;
+        size = right - left;
+    }
+    return klo;
+}
+
 // units k with qpos_aln[k] == p form a contiguous range; returns false when there is none
 // (paf.rs:505-534: '+' counts up from q_st - 1, '-' counts down from q_en; non-query units repeat the value)
 __device__ inline bool rb_s_qrange(const rb_sview &v, uint64_t p, uint64_t *klo, uint64_t *khi) {

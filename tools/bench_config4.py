@@ -13,8 +13,10 @@ resident host has them with the batch).  One JSON line: per stage kernel_ms, alg
 records/s on the sum of the stages.  `--gather`: also the round-5 route (rb_dev_gather_records, then rb_dev_break with the fused scan on
 the dense copy) for comparison.  Run under `rocprofv3 --kernel-trace --stats` for the per-kernel split (tools/prof_c4.sh).  No oracle
 here: parity of every stage is the business of tests/ (test_gpu_fullsize.py runs this workload; test_gpu_trim.py both break routes).
+`--legacy`: the same pipeline, stage for stage, under the legacy binary-search policy (tests/test_gpu_trim_legacy.py holds its parity);
+the JSON line says which in "policy".
 
-  python tools/bench_config4.py [--records 10000000] [--gather] [--host-buffers]
+  python tools/bench_config4.py [--records 10000000] [--legacy] [--gather] [--host-buffers]
 """
 import argparse
 import json
@@ -33,6 +35,7 @@ PEAK = 8e12
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=10_000_000)
+    ap.add_argument("--legacy", action="store_true", help="run every stage under the legacy binary-search policy (rustc < 1.82) instead of the modern one")
     ap.add_argument("--gather", action="store_true", help="also time the route through rb_dev_gather_records (round 5)")
     ap.add_argument("--host-buffers", action="store_true", help="also time rb_host_overlap_split on host arrays (PCIe-inclusive, 2e6 records at most)")
     a = ap.parse_args()
@@ -49,7 +52,7 @@ def main():
     t_st, t_en, q_st, q_en, strand = h["t_st"], h["t_en"], h["q_st"], h["q_en"], h["strand"]
     gen = time.time() - t0
     ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
-    MOD = rustybam_amd.BSEARCH_MODERN
+    MOD = rustybam_amd.BSEARCH_LEGACY if a.legacy else rustybam_amd.BSEARCH_MODERN  # (the policy of every stage below)
 
     # ---- scan: the rows ResidentTrim made when it took the batch, timed here on the same view into a second array ----
     d_norm2 = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
@@ -165,7 +168,8 @@ def main():
                              "rb_dev_break with RB_LIFT_FUSED_SCAN | RB_BREAK_ONE_WALK on the gathered copy (a pass moved records)") + ": 4 B per kept op + 48 B per "
                              "record + 88 B per piece + 4 B per emitted op; best of 3")}
     total_ms = sum(s["kernel_ms"] for s in stages.values())
-    res = {"workload": f"config 4: {n} records, {total_ops} ops, {n // 4} query groups of 4, seed 0x5eed0004; batch resident in HBM",
+    res = {"policy": "legacy" if a.legacy else "modern",
+           "workload": f"config 4: {n} records, {total_ops} ops, {n // 4} query groups of 4, seed 0x5eed0004; batch resident in HBM",
            "stages": stages, "pipeline_device_ms": round(total_ms, 3), "pipeline_records_per_s": n / (total_ms * 1e-3),
            "pipeline_cigar_ops_per_s": total_ops / (total_ms * 1e-3),
            "trim_passes": T.passes, "trim_pairs": pairs, "trim_wall_s": round(t_trim, 4), "trim_wall_over_kernels": round(t_trim * 1e3 / max(1e-9, k_sel + k_pair + k_apply), 2),
@@ -206,7 +210,7 @@ def main():
     if a.host_buffers and n <= 2_000_000:
         ops_h = capi.synth_fill_ops_host(SEED, 0, off)
         t0 = time.time()
-        eng.overlap_split(ops_h, off, t_st, t_en, q_st, q_en, strand, left.astype(np.uint32), (left + 1).astype(np.uint32))
+        eng.overlap_split(ops_h, off, t_st, t_en, q_st, q_en, strand, left.astype(np.uint32), (left + 1).astype(np.uint32), (1, 1, 1), MOD)
         res["host_buffer_overlap_split_s"] = round(time.time() - t0, 3)
     print(json.dumps(res))
 
