@@ -352,7 +352,9 @@ int rb_dev_overlap_split(rb_ctx *ctx, const rb_batch_view *batch, const rb_norm_
 
 /* rb_dev_trim_reserve (optional): rb_dev_overlap_split keeps, per context, a list of the pairs its first kernel leaves to the ones
  * behind it; the list grows with the largest n_pairs seen, and growing means a stream synchronisation and an allocation inside that
- * call.  A host that knows how many pairs a pass can have (one per query group) sizes the list up front with this. */
+ * call.  A host that knows how many pairs a pass can have (one per query group) sizes the list up front with this.
+ * The list (4 bytes per pair) is mandatory: if it cannot be allocated, this call and rb_dev_overlap_split return RB_E_NOMEM
+ * (rb_ctx_last_error says so) and no kernel runs -- there is no slower route without it. */
 int rb_dev_trim_reserve(rb_ctx *ctx, uint64_t n_pairs);
 
 /* ---- trim-paf with the batch resident on the device across the passes of Paf::overlapping_paf_recs (paf.rs:210-305) ----------

@@ -1129,13 +1129,17 @@ extern "C" int rb_dev_swap(rb_ctx *ctx, const rb_batch_view *b, uint32_t *out_op
 }
 
 static int trim_pend_reserve(rb_ctx *ctx, uint64_t n_pairs) {
-    if (ctx->trim_pend_cap >= n_pairs) return RB_OK;
+    if (ctx->trim_pend && ctx->trim_pend_cap >= n_pairs) return RB_OK;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->trim_pend) hipFree(ctx->trim_pend);
     ctx->trim_pend = nullptr, ctx->trim_pend_cap = 0;
     const uint64_t cap = n_pairs + n_pairs / 4 + 1024;
-    if (hipMalloc(&ctx->trim_pend, 256 + cap * 4) == hipSuccess) ctx->trim_pend_cap = cap;
-    else (void)hipGetLastError(); // (without a list the wave-per-pair kernel looks at every pair: slower, same rows)
+    const hipError_t e = hipMalloc(&ctx->trim_pend, 256 + cap * 4); // (4 bytes per pair, beside rows of 128 the caller has allocated)
+    if (e != hipSuccess) {
+        ctx->trim_pend = nullptr, (void)hipGetLastError();
+        return fail(ctx, RB_E_NOMEM, "hipMalloc(list of %llu pending pairs): %s", (unsigned long long)cap, hipGetErrorString(e));
+    }
+    ctx->trim_pend_cap = cap;
     return RB_OK;
 }
 extern "C" int rb_dev_trim_reserve(rb_ctx *ctx, uint64_t n_pairs) {
@@ -1163,7 +1167,7 @@ extern "C" int rb_dev_overlap_split(rb_ctx *ctx, const rb_batch_view *b, const r
     p.policy = policy & 1;
     p.rows = rows;
     p.out_ops = out_ops;
-    p.only_pending = 0;
+    p.list_declined = 0; // (rb_launch_overlap_split sets it for its first attempt)
     p.in_place = (policy & RB_TRIM_IN_PLACE) ? 1 : 0;
     if (p.in_place && out_ops != b->ops) return fail(ctx, RB_E_INVALID, "RB_TRIM_IN_PLACE: out_ops must be the batch's own ops array");
     if (!ctx->trim_scratch) { // (40 MB, once per context; without it those pairs simply stay with the serial kernel)
@@ -1177,12 +1181,9 @@ extern "C" int rb_dev_overlap_split(rb_ctx *ctx, const rb_batch_view *b, const r
         const int rc = trim_pend_reserve(ctx, n_pairs);
         if (rc) return rc;
     }
-    p.pend = nullptr, p.pend_list = nullptr;
-    if (ctx->trim_pend) {
-        p.pend = (unsigned long long *)ctx->trim_pend;
-        p.pend_list = (uint32_t *)((char *)ctx->trim_pend + 256);
-        HIPCHK(ctx, rb_fill_async(p.pend, 0, 8, ctx->stream));
-    }
+    p.pend = (unsigned long long *)ctx->trim_pend;
+    p.pend_list = (uint32_t *)((char *)ctx->trim_pend + 256);
+    HIPCHK(ctx, rb_fill_async(p.pend, 0, 8, ctx->stream));
     HIPCHK(ctx, rb_launch_overlap_split(&p, ctx->stream));
     return RB_OK;
 }

@@ -10,7 +10,9 @@
 // independent (one pair per query name and pass, paf.rs:264-284); the pass/recursion driver stays on the
 // host.  Fully general (all op codes, both binary-search policies).  The wave-per-pair form further down takes the regular records
 // under either policy (a template parameter, LEG: one instantiation each) and cuts them in place; what it declines comes here.
-#include "rb_trim.h"
+// This file is the pair step: the serial kernel, the wave form with its attempts, and rb_launch_overlap_split, which runs them behind
+// the row form (k_trim4.hip).  What the forms share is in rb_pair.h; selection and the kernels between passes are in k_trim_pass.hip.
+#include "rb_pair.h"
 #include "rb_launch.h"
 #include <algorithm>
 
@@ -181,32 +183,15 @@ __device__ uint32_t rb_clip_by_query(const rb_sview &v, uint64_t N, uint64_t new
 }
 
 __device__ void rb_serial_pair(const rb_trim_params &p, const uint64_t pi);
-__global__ __launch_bounds__(64) void rb_k_overlap_split(rb_trim_params p) {
-    if (p.only_pending && p.pend_list) { // what the wave kernels left, from their list
-        const uint64_t n = *p.pend;
-        for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (uint64_t)gridDim.x * blockDim.x) {
-            const uint64_t pi = p.pend_list[e];
-            if (p.rows[pi].status == 0x7FFF0001u) rb_serial_pair(p, pi);
-        }
-        return;
+__global__ __launch_bounds__(64) void rb_k_overlap_split(rb_trim_params p) { // what the staged forms left, from their list
+    const uint64_t n = *p.pend;
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t pi = p.pend_list[e];
+        if (p.rows[pi].status == RB_ST_PENDING_INTERNAL) rb_serial_pair(p, pi);
     }
-    const uint64_t pi = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (pi >= p.n_pairs) return;
-    if (p.only_pending && p.rows[pi].status != 0x7FFF0001u) return; // (what the wave-per-pair kernels left, every row looked at)
-    rb_serial_pair(p, pi);
 }
 __device__ void rb_serial_pair(const rb_trim_params &p, const uint64_t pi) {
-    rb_pair_row w;
-    w.split_idx = 0;
-    w.split_score = 0;
-    w.status = RB_ST_OK;
-    w._pad = 0;
-    for (int s = 0; s < 2; s++) {
-        w.t_st[s] = w.t_en[s] = w.q_st[s] = w.q_en[s] = 0;
-        w.nmatch[s] = w.aln_len[s] = 0;
-        w.out_off[s] = 0;
-        w.out_n[s] = 0;
-    }
+    rb_pair_row w = rb_pair_row_empty();
     const uint32_t rl = p.left[pi], rr = p.right[pi];
     const rb_norm_row *nl = &p.norm[rl], *nr = &p.norm[rr];
     if (nl->status != RB_ST_OK || nr->status != RB_ST_OK) { // aligned_pairs() panics (paf.rs:273-274, :782)
@@ -341,40 +326,23 @@ __device__ void rb_serial_pair(const rb_trim_params &p, const uint64_t pi) {
 // The split (trim_overlap.rs:50-76) is the first strict maximum of f(k) = l[0..k) + r[k..n): f is piecewise linear, so it is
 // evaluated only where either record's score changes (op starts and the special last base), all candidates in parallel.
 // Pairs this kernel does not take are marked RB_ST_PENDING_INTERNAL and done by rb_k_overlap_split afterwards.
-#ifndef RB_TW_CAP
 #define RB_TW_CAP 192   // ops of a record's region, first attempt: 5 KB of LDS per pair and 64 VGPRs = 32 pairs per CU.  The kernel waits on
                         // memory, not on the ALUs: 768 ops (8 pairs per CU, whole 500-op records staged) took 20.1 ms per 1.5e6 pairs, this 7.2
-#endif
-#ifndef RB_TW_CAP1
 #define RB_TW_CAP1 1024 // the pairs the first attempt lists, second attempt (26 KB: 6 pairs per CU)
-#endif
 #define RB_TW_CAP2 6144 // second attempt for the pairs whose overlap spans more ops (one pair per CU at a time; such overlaps are rare)
 #define RB_TW_CAP3 32768 // third attempt: the same arrays in device memory (whole-chromosome alignments that overlap by hundreds of kilobases)
 #define RB_TW_SLAB_WORDS(CAP) (2u * 3u * ((CAP) + 1u) + 2u * 3u * ((CAP) / 16u + 2u))
-#ifndef RB_TW_STOP
-#define RB_TW_STOP 0 // diagnostics (tools/prof_c4_decomp.sh): != 0 ends a pair early -- 1 behind the left record's staging, 2 behind both, 3 behind the
-                     // searches of the overlap's end ops, 4 behind the split, 5 behind the left clip; the rows are wrong then, only the time is of interest
-#endif
 
 // A record of a pair as the wave kernel sees it.  Only the REGION of the record that the overlap can touch is staged in LDS --
 // the ops that hold the overlapped query bases plus a 64-op step on either side -- with prefixes that are absolute (counted from
 // the record's first op), so a record may be as long as it likes: what lies in front of the region is streamed once for its
 // totals, what lies behind it is only copied when the clip keeps it.
-struct rb_wrec {
-    const uint32_t *ops; // the record's kept ops, in memory
-    uint32_t n;          // how many
-    uint32_t i0, m, ncp; // region = ops [i0, i0 + m); checkpoints in use = ceil(m / 16) + 1 (the last one holds the prefixes at the region's end)
-    uint64_t t_st, t_en, q_st, q_en;
-    bool minus;
-    bool bad;            // a search left the region: the pair goes to the serial kernel
-    uint32_t N, Qtot, Rtot; // totals of the whole record (units from the norm row, bases from the coordinates)
+struct rb_wrec : rb_prec {
+    uint32_t ncp;           // checkpoints in use = ceil(m / 16) + 1 (the last one holds the prefixes at the region's end)
     uint32_t *w;            // LDS [m + 1]: the op words of the region; w[m] = a zero-length M (ends every D / N run, contains nothing)
     uint32_t *Qc;           // LDS [m + 1]: query bases before op i0 + k
     int32_t *SP;            // LDS [m + 1]: score of the query bases of the region before op i0 + k, in op order
     uint32_t *cU, *cQ, *cR; // LDS [ncp]: units / query bases / reference bases before op i0 + 16 c
-};
-struct rb_wpos { // an op (i = n: none) and the exclusive prefix of the searched quantity at it
-    uint32_t i, w, pre;
 };
 
 
@@ -575,9 +543,9 @@ __device__ __forceinline__ uint32_t rb_tw_before(const rb_wrec &v, uint32_t i, i
 // wave-uniform search inside the region: the op that holds unit x (BY_UNIT) / query offset x, found by all lanes at once -- one
 // ballot over the checkpoints, then the 16 ops of that chunk side by side.  i = n: no op of the region holds x.
 template <bool BY_UNIT>
-__device__ rb_wpos rb_tw_find(const rb_wrec &v, uint32_t x, int lane) {
+__device__ rb_ppos rb_tw_find(const rb_wrec &v, uint32_t x, int lane) {
     const uint32_t *cp = BY_UNIT ? v.cU : v.cQ;
-    rb_wpos o;
+    rb_ppos o;
     o.i = v.n, o.w = RB_NULL_OP, o.pre = 0;
     // the last chunk whose checkpoint is <= x: 64 checkpoints per ballot, a 64-ary search when the region has more chunks
     uint32_t cbase = 0, ccount = v.ncp - 1u; // (the last entry is not a chunk)
@@ -616,7 +584,7 @@ __device__ rb_wpos rb_tw_find(const rb_wrec &v, uint32_t x, int lane) {
 // score of the region's query bases in front of query offset x (op order), wave-uniform x inside the region (or just behind it)
 __device__ __forceinline__ int64_t rb_tw_W(rb_wrec &v, uint32_t x, int lane, int32_t ms, int32_t ds, int32_t is) {
     if (x >= v.Qc[v.m]) return v.SP[v.m];
-    const rb_wpos o = rb_tw_find<false>(v, x, lane);
+    const rb_ppos o = rb_tw_find<false>(v, x, lane);
     if (o.i >= v.n) {
         v.bad = true;
         return 0;
@@ -642,261 +610,88 @@ __device__ __forceinline__ int64_t rb_tw_G_lane(const rb_wrec &v, uint64_t p, in
     return !v.minus ? rb_tw_W_lane(v, (uint32_t)(p - v.q_st), ms, ds, is) : -rb_tw_W_lane(v, (uint32_t)(v.q_en - p), ms, ds, is);
 }
 
-// truncate_record_by_query (paf.rs:785-823) on a staged regular record; same results as rb_clip_by_query.  One end of the new
-// query range is the record's own end (trim_overlap.rs:77-78), the other lies in the staged region.
-struct rb_wend { // a unit of the record: its index, the op that holds it, and the prefixes before that op
-    uint32_t k;   // unit
-    rb_wpos o;    // op, its word, units before it
-    uint32_t R, Q; // reference / query bases before the op
-};
-struct rb_wcut { // in-place clip: the two words to rewrite (absolute indices into the ops array) once BOTH clips of the pair stand
-    uint64_t at_first, at_last;
-    uint32_t w_first, w_last;
-};
-template <bool LEG>
-__device__ uint32_t rb_tw_clip(rb_wrec &v, uint64_t new_q_st, uint64_t new_q_en, uint32_t *out, rb_pair_row *row, int s, uint64_t out_base,
-                               int lane, rb_wcut *cut = nullptr, uint64_t rec_base = 0) {
-    if (!(new_q_st >= v.q_st) || !(new_q_en <= v.q_en) || new_q_en == 0) return RB_ST_PANIC_ASSERT; // :787-788
-    if (new_q_en <= new_q_st) { // an empty range: the serial kernel says what the reference does with it
-        v.bad = true;
-        return RB_ST_OK;
-    }
-    const uint32_t n = v.n, N = v.N;
-    // the match-type unit truncate_record_by_query ends up at for query position p: qpos_to_idx_match (paf.rs:564-590) = the last
-    // unit whose qpos equals p (modern policy) or the one the legacy search probes first (LEG), then the nearest match-type unit in the
-    // search direction
-    auto resolve = [&](uint64_t p, bool search_up, rb_wend *e) -> bool {
-        if (p < v.q_st || p >= v.q_en) return false;
-        const uint32_t x = (uint32_t)(v.minus ? v.q_en - 1 - p : p - v.q_st);
-        if (x < v.Qc[0] || x >= v.Qc[v.m]) {
-            // outside the region: only the record's own first / last query base is asked for there.  A regular record starts and
-            // ends on a match op; its last base is its last unit, its first base its first unit unless that op has one base and a
-            // D / N run behind it (the run repeats the position: left to the serial kernel)
-            if (x == 0u) {
-                const uint32_t w0 = v.ops[0];
-                if (rb_len(w0) < 2u && n > 1u && !rb_in(RB_QRY_MASK, rb_opc(v.ops[1]))) return false;
-                e->k = 0, e->o.i = 0, e->o.w = w0, e->o.pre = 0, e->R = 0, e->Q = 0;
-                return true;
-            }
-            if (x + 1u == v.Qtot) {
-                const uint32_t wl = v.ops[n - 1u], len = rb_len(wl);
-                e->k = N - 1u, e->o.i = n - 1u, e->o.w = wl, e->o.pre = N - len, e->R = v.Rtot - len, e->Q = v.Qtot - len;
-                return true;
-            }
-            return false;
-        }
-        const rb_wpos o = rb_tw_find<false>(v, x, lane);
-        if (o.i >= n) return false;
-        const uint32_t j = x - o.pre, len = rb_len(o.w);
-        const uint32_t ub = rb_tw_before<0>(v, o.i, lane);
-        uint32_t u = ub + j;
+// the region as truncate_record_by_query (rb_pair_clip, rb_pair.h) asks for it, for a wavefront
+struct rb_tw_region {
+    static constexpr uint32_t WIDTH = 64u;
+    const rb_wrec &v;
+    int ln;
+    __device__ __forceinline__ uint32_t lane() const { return (uint32_t)ln; }
+    __device__ __forceinline__ uint32_t word(uint32_t k) const { return v.w[k]; }
+    __device__ __forceinline__ uint32_t qpre(uint32_t k) const { return v.Qc[k]; }
+    __device__ __forceinline__ uint32_t q_begin() const { return v.Qc[0]; }
+    __device__ __forceinline__ uint32_t q_end() const { return v.Qc[v.m]; }
+    __device__ __forceinline__ uint32_t first_word() const { return v.ops[0]; }
+    __device__ __forceinline__ uint32_t second_word() const { return v.ops[1]; }
+    __device__ __forceinline__ uint32_t last_word() const { return v.ops[v.n - 1u]; }
+    __device__ __forceinline__ rb_ppos find_q(uint32_t x) const { return rb_tw_find<false>(v, x, ln); }
+    __device__ __forceinline__ uint32_t units_before(uint32_t i) const { return rb_tw_before<0>(v, i, ln); }
+    __device__ __forceinline__ uint32_t ref_before(uint32_t i) const { return rb_tw_before<1>(v, i, ln); }
+    // a run of any number of ops: the unit first, then the op that holds it by a second search (skipped when the unit stays in o: it was a
+    // tenth of a pair's instructions)
+    template <bool LEG>
+    __device__ __forceinline__ bool behind_last_base(const rb_ppos &o, uint32_t &u, rb_ppos &om) const {
+        uint32_t k2 = o.i - v.i0 + 1u;
         bool moved = false; // the unit left the op that holds the base
-        if (j + 1u == len) { // last base of the op: the D / N units behind it repeat its position
-            uint32_t k2 = o.i - v.i0 + 1u;
-            if constexpr (LEG) {
-                uint32_t run = 0;
-                for (; k2 < v.m && !rb_in(RB_QRY_MASK, rb_opc(v.w[k2])); k2++) run += rb_len(v.w[k2]);
-                if (k2 >= v.m && v.i0 + v.m < n) return false; // (the run leaves the region)
-                if (run) { // the equal range is [u, u + run]: the unit is where the probe lands
-                    const uint32_t kk = rb_legacy_probe32(N, u, u + run);
-                    moved = kk != u, u = kk;
-                }
-            } else {
+        if constexpr (LEG) {
+            uint32_t run = 0;
+            for (; k2 < v.m && !rb_in(RB_QRY_MASK, rb_opc(v.w[k2])); k2++) run += rb_len(v.w[k2]);
+            if (k2 >= v.m && v.i0 + v.m < v.n) return false; // (the run leaves the region)
+            if (run) { // the equal range is [u, u + run]: the unit is where the probe lands
+                const uint32_t kk = rb_legacy_probe32(v.N, u, u + run);
+                moved = kk != u, u = kk;
+            }
+        } else {
             for (; k2 < v.m && !rb_in(RB_QRY_MASK, rb_opc(v.w[k2])); k2++) u += rb_len(v.w[k2]), moved = true;
-            if (k2 >= v.m && v.i0 + v.m < n) return false; // (the run leaves the region)
-            }
+            if (k2 >= v.m && v.i0 + v.m < v.n) return false; // (the run leaves the region)
         }
-        // nearest match-type unit, up (paf.rs:581-583) or down (:585-587); the op that holds unit u is the one just found unless the
-        // unit moved into the run behind it (round 3: the second search is skipped then -- it was a tenth of a pair's instructions)
-        rb_wpos om;
-        if (!moved) om.i = o.i, om.w = o.w, om.pre = ub;
-        else om = rb_tw_find<true>(v, u, lane);
-        if (om.i >= n) return false;
-        uint32_t km = u;
-        if (!rb_in(RB_MATCH_MASK, rb_opc(om.w))) {
-            if (search_up) {
-                uint32_t uu = om.pre + rb_len(om.w), k2 = om.i - v.i0 + 1u;
-                for (; k2 < v.m && !rb_in(RB_MATCH_MASK, rb_opc(v.w[k2])); k2++) uu += rb_len(v.w[k2]);
-                if (k2 >= v.m) return false; // (no match op behind it inside the region; at the record's end the reference panics: serial kernel)
-                km = uu;
-                om.i = v.i0 + k2, om.w = v.w[k2], om.pre = uu;
-            } else {
-                uint32_t uu = om.pre, k2 = om.i - v.i0;
-                bool got = false;
-                while (k2 > 0u) {
-                    k2--;
-                    if (rb_in(RB_MATCH_MASK, rb_opc(v.w[k2]))) {
-                        got = true;
-                        break;
-                    }
-                    uu -= rb_len(v.w[k2]);
-                }
-                if (!got) return false;
-                km = uu - 1u;
-                om.i = v.i0 + k2, om.w = v.w[k2], om.pre = uu - rb_len(v.w[k2]);
-            }
-        }
-        e->k = km, e->o = om, e->R = rb_tw_before<1>(v, om.i, lane), e->Q = v.Qc[om.i - v.i0];
-        return true;
-    };
-    rb_wend A, B; // paf.rs:792-796: the start searches up on '+' and down on '-', the end the other way
-    if (!resolve(new_q_st, !v.minus, &A) || !resolve(new_q_en - 1, v.minus, &B)) {
-        v.bad = true;
-        return RB_ST_OK;
+        if (moved) om = rb_tw_find<true>(v, u, ln);
+        return om.i < v.n;
     }
-    auto unit = [&](const rb_wend &e, uint64_t *tpos, uint64_t *qpos) { // both are match-type units
-        const uint32_t off = e.k - e.o.pre;
-        *tpos = v.t_st + e.R + off;
-        *qpos = v.minus ? v.q_en - 1 - e.Q - off : v.q_st + e.Q + off;
-    };
-    uint64_t tp, qp_st, qp_en;
-    unit(A, &tp, &qp_st);
-    unit(B, &tp, &qp_en);
-    const uint64_t nq_st = qp_st, nq_en = qp_en + 1;
-    if (A.k > B.k) { // :799-801
-        const rb_wend t = A;
-        A = B;
-        B = t;
-    }
-    uint64_t t0, t1, qd;
-    unit(A, &t0, &qd);
-    unit(B, &t1, &qd);
-    const uint64_t nt_st = t0, nt_en = t1 + 1; // :802-803
-    // subset_cigar + collapse (:807-808): ops ia..ib with the first / last length cut; adjacent ops differ, nothing merges; both
-    // ends are match-type units, so the strip of :819-822 removes nothing
-    // Round 3: the copy is only a copy.  check_integrity of the clipped record (:819-822) compares the sums of its ops with
-    // coordinates that were derived from those very prefixes: for a regular record it cannot fail, and nmatch follows from the spans
-    // (a match-type op counts in reference, query and units, an I in query and units, a D / N in reference and units, so
-    // matches = ref + query - units: the clip kernel's identity).  Round 2 summed three 64-bit totals over every copied op: 470 of a
-    // pair's 2640 vector instructions.
-    const uint32_t ia = A.o.i, ib = B.o.i, cnt = ib - ia + 1;
-    if (cut) { // (in place: nothing is copied; rec_base = where the record's kept ops begin in the ops array)
-        const uint32_t lf = cnt == 1 ? B.k - A.k + 1u : A.o.pre + rb_len(A.o.w) - A.k, ll = cnt == 1 ? lf : B.k - B.o.pre + 1u;
-        cut->at_first = rec_base + ia, cut->at_last = rec_base + ib;
-        cut->w_first = (lf << 4) | rb_opc(A.o.w), cut->w_last = (ll << 4) | rb_opc(B.o.w);
-        out_base = rec_base + ia;
-    } else {
-        for (uint32_t j = (uint32_t)lane; j < cnt; j += 64) {
-            const uint32_t wv = v.ops[ia + j];
-            uint32_t len = rb_len(wv);
-            if (cnt == 1) len = B.k - A.k + 1u;
-            else if (j == 0) len = A.o.pre + len - A.k;
-            else if (j == cnt - 1) len = B.k - B.o.pre + 1u;
-            out[j] = (len << 4) | rb_opc(wv);
-        }
-    }
-    // (what CAN fail is the query side: the new start and end are resolved independently -- up and down --, and when the end lands on
-    //  a lower query position than the start the coordinates say end + 1 - start while the ops between the two units still hold
-    //  |end - start| + 1 query bases: check_integrity's unwrap panics)
-    if (nt_en < nt_st) return RB_ST_PANIC_INTEGRITY_T;
-    if (qp_en < qp_st) return RB_ST_PANIC_INTEGRITY_Q;
-    const uint32_t units = B.k - A.k + 1u;
-    row->t_st[s] = nt_st;
-    row->t_en[s] = nt_en;
-    row->q_st[s] = nq_st;
-    row->q_en[s] = nq_en;
-    row->nmatch[s] = (uint32_t)((nt_en - nt_st) + (nq_en - nq_st) - units);
-    row->aln_len[s] = units;
-    row->out_off[s] = out_base;
-    row->out_n[s] = cnt;
-    return RB_ST_OK;
-}
+};
 
 template <int CAP, bool LEG>
 __device__ void rb_tw_pair(const rb_trim_params &p, const uint64_t pi, uint32_t (*lds_w)[3][CAP + 1], uint32_t (*lds_c)[3][CAP / 16 + 2]) {
     const int lane = rb_lane();
-    rb_pair_row w;
-    w.split_idx = 0;
-    w.split_score = 0;
-    w.status = RB_ST_OK;
-    w._pad = 0;
-    for (int s = 0; s < 2; s++) {
-        w.t_st[s] = w.t_en[s] = w.q_st[s] = w.q_en[s] = 0;
-        w.nmatch[s] = w.aln_len[s] = 0;
-        w.out_off[s] = 0;
-        w.out_n[s] = 0;
-    }
-    const uint32_t rl = p.left[pi], rr = p.right[pi];
-    const rb_norm_row *nl = &p.norm[rl], *nr = &p.norm[rr];
-    if (nl->status != RB_ST_OK || nr->status != RB_ST_OK) { // aligned_pairs() panics (paf.rs:273-274, :782)
-        w.status = nl->status != RB_ST_OK ? nl->status : nr->status;
-        if (lane == 0) p.rows[pi] = w;
-        return;
-    }
-    auto pending = [&](uint32_t why = 0) { // (why: diagnostics, RB_DEBUG_TRIM_NO_SERIAL; the serial kernel rewrites the whole row)
-        if (lane == 0) {
-            if (p.pend_list && !p.only_pending) p.pend_list[atomicAdd(p.pend, 1ull)] = (uint32_t)pi; // (listed once: by the first attempt)
-            p.rows[pi].status = RB_ST_PENDING_INTERNAL, p.rows[pi].split_idx = why;
-        }
-    };
+    rb_pair_row w = rb_pair_row_empty();
+    rb_wrec L, R;
+    uint64_t st_ovl, en_ovl;
     // (LEG: this instantiation serves the legacy policy; the modern one declines it -- rb_launch_overlap_split picks by p->policy)
-    if ((!LEG && p.policy == RB_BSEARCH_LEGACY) || !(nl->flags & RB_F_REGULAR) || !(nr->flags & RB_F_REGULAR) || nl->n_ops == 0 || nr->n_ops == 0) {
-        pending(1);
+    const uint32_t why = rb_pair_open<LEG>(p, pi, lane == 0, w, L, R, &st_ovl, &en_ovl);
+    if (why == RB_PAIR_CLOSED) return;
+    if (why != RB_PAIR_OPENED) {
+        rb_pair_pending(p, pi, lane == 0, why);
         return;
     }
     const int32_t ms = p.match_score, ds = p.diff_score, is = p.indel_score;
-    rb_wrec L, R;
-    L.ops = p.ops + p.op_off[rl] + nl->first_op, L.n = nl->n_ops;
-    L.t_st = nl->t_st, L.t_en = nl->t_en, L.q_st = nl->q_st, L.q_en = nl->q_en, L.minus = p.strand[rl] == (uint8_t)'-';
-    L.N = nl->aln_len, L.Qtot = (uint32_t)(nl->q_en - nl->q_st), L.Rtot = (uint32_t)(nl->t_en - nl->t_st);
     L.w = lds_w[0][0], L.Qc = lds_w[0][1], L.SP = reinterpret_cast<int32_t *>(lds_w[0][2]), L.cU = lds_c[0][0], L.cQ = lds_c[0][1], L.cR = lds_c[0][2];
-    R.ops = p.ops + p.op_off[rr] + nr->first_op, R.n = nr->n_ops;
-    R.t_st = nr->t_st, R.t_en = nr->t_en, R.q_st = nr->q_st, R.q_en = nr->q_en, R.minus = p.strand[rr] == (uint8_t)'-';
-    R.N = nr->aln_len, R.Qtot = (uint32_t)(nr->q_en - nr->q_st), R.Rtot = (uint32_t)(nr->t_en - nr->t_st);
     R.w = lds_w[1][0], R.Qc = lds_w[1][1], R.SP = reinterpret_cast<int32_t *>(lds_w[1][2]), R.cU = lds_c[1][0], R.cQ = lds_c[1][1], R.cR = lds_c[1][2];
-    const uint64_t st_ovl = L.q_st > R.q_st ? L.q_st : R.q_st; // trim_overlap.rs:43-44
-    const uint64_t en_ovl = L.q_en < R.q_en ? L.q_en : R.q_en;
-    if (en_ovl <= st_ovl || st_ovl < L.q_st || en_ovl > L.q_en || st_ovl < R.q_st || en_ovl > R.q_en) { // (no overlap: the serial kernel says what the reference does)
-        pending(2);
-        return;
-    }
-    // query offsets of the overlap in each record's op order
-    auto span = [&](const rb_wrec &v, uint32_t *xa, uint32_t *xb) {
-        *xa = (uint32_t)(!v.minus ? st_ovl - v.q_st : v.q_en - en_ovl);
-        *xb = (uint32_t)(!v.minus ? en_ovl - 1 - v.q_st : v.q_en - 1 - st_ovl);
-    };
-    uint32_t lxa, lxb, rxa, rxb;
-    span(L, &lxa, &lxb);
-    span(R, &rxa, &rxb);
-#if RB_TW_STOP == 1
-    if (!rb_tw_stage<CAP, LEG>(L, lane, ms, ds, is, lxa, lxb)) pending(3);
-    if (lane == 0) p.rows[pi].split_idx = L.m;
-    return;
-#endif
+    const uint32_t lxa = L.xa, lxb = L.xb, rxa = R.xa, rxb = R.xb;
     if (!rb_tw_stage<CAP, LEG>(L, lane, ms, ds, is, lxa, lxb) || !rb_tw_stage<CAP, LEG>(R, lane, ms, ds, is, rxa, rxb)) { // an overlap of more ops than the region holds
-        pending(3);
+        rb_pair_pending(p, pi, lane == 0, 3);
         return;
     }
-#if RB_TW_STOP == 2
-    if (lane == 0) p.rows[pi].split_idx = L.m + R.m;
-    return;
-#endif
     int64_t best = 0;
     uint64_t best_idx = 0;
     // the ops that hold the first and the last overlapped query base of each record, searched ONCE (round 3: the scores at the ends
     // of the overlap and the candidate ranges below each searched them again -- seven wave searches of a pair's instructions)
-    const rb_wpos La = rb_tw_find<false>(L, lxa, lane), Lb = rb_tw_find<false>(L, lxb, lane), Ra = rb_tw_find<false>(R, rxa, lane), Rb = rb_tw_find<false>(R, rxb, lane);
+    const rb_ppos La = rb_tw_find<false>(L, lxa, lane), Lb = rb_tw_find<false>(L, lxb, lane), Ra = rb_tw_find<false>(R, rxa, lane), Rb = rb_tw_find<false>(R, rxb, lane);
     if (La.i >= L.n || Lb.i >= L.n || Ra.i >= R.n || Rb.i >= R.n) {
-        pending(4);
+        rb_pair_pending(p, pi, lane == 0, 4);
         return;
     }
-#if RB_TW_STOP == 3
-    if (lane == 0) p.rows[pi].split_idx = La.i + Lb.i + Ra.i + Rb.i;
-    return;
-#endif
     // W (score of the query bases in front of offset x, op order) at x = xa and at x = xb + 1, from those ops
-    auto W_at_first = [&](const rb_wrec &v, const rb_wpos &o, uint32_t xa) -> int64_t {
+    auto W_at_first = [&](const rb_wrec &v, const rb_ppos &o, uint32_t xa) -> int64_t {
         return (int64_t)v.SP[o.i - v.i0] + (int64_t)(xa - o.pre) * rb_tw_score(rb_opc(o.w), ms, ds, is);
     };
-    auto W_behind_last = [&](const rb_wrec &v, const rb_wpos &o, uint32_t xb) -> int64_t {
+    auto W_behind_last = [&](const rb_wrec &v, const rb_ppos &o, uint32_t xb) -> int64_t {
         const uint32_t k = o.i - v.i0;
         return xb + 1u < o.pre + rb_len(o.w) ? (int64_t)v.SP[k] + (int64_t)(xb + 1u - o.pre) * rb_tw_score(rb_opc(o.w), ms, ds, is) : (int64_t)v.SP[k + 1u];
     };
     // G(p) = W(p - q_st) on '+', -W(q_en - p) on '-': st_ovl is offset xa on '+' and xb + 1 on '-', en_ovl the other way round
-    auto G_st = [&](const rb_wrec &v, const rb_wpos &oa, const rb_wpos &ob, uint32_t xa, uint32_t xb) -> int64_t {
+    auto G_st = [&](const rb_wrec &v, const rb_ppos &oa, const rb_ppos &ob, uint32_t xa, uint32_t xb) -> int64_t {
         return !v.minus ? W_at_first(v, oa, xa) : -W_behind_last(v, ob, xb);
     };
-    auto G_en = [&](const rb_wrec &v, const rb_wpos &oa, const rb_wpos &ob, uint32_t xa, uint32_t xb) -> int64_t {
+    auto G_en = [&](const rb_wrec &v, const rb_ppos &oa, const rb_ppos &ob, uint32_t xa, uint32_t xb) -> int64_t {
         return !v.minus ? W_behind_last(v, ob, xb) : -W_at_first(v, oa, xa);
     };
     {
@@ -953,41 +748,30 @@ __device__ void rb_tw_pair(const rb_trim_params &p, const uint64_t pi, uint32_t 
         if (cb > best) best = cb, best_idx = ck;
     }
     if (L.bad || R.bad) {
-        pending(4);
+        rb_pair_pending(p, pi, lane == 0, 4);
         return;
     }
     w.split_idx = best_idx;
     w.split_score = (int32_t)best;
-#if RB_TW_STOP == 4
-    if (lane == 0) p.rows[pi] = w;
-    return;
-#endif
     const uint64_t split = st_ovl + best_idx;
     const uint64_t ob = p.pair_out_off[pi];
-    rb_wcut cutL, cutR;
+    rb_pcut cutL, cutR;
     const bool inpl = p.in_place != 0;
-    uint32_t st = rb_tw_clip<LEG>(L, L.q_st, split, p.out_ops + ob, &w, 0, ob, lane, inpl ? &cutL : nullptr, (uint64_t)(L.ops - p.ops)); // trim_overlap.rs:77
-#if RB_TW_STOP == 5
-    if (lane == 0) p.rows[pi] = w;
-    return;
-#endif
+    uint32_t st = rb_pair_clip<LEG>(L, rb_tw_region{L, lane}, L.q_st, split, p.out_ops + ob, &w, 0, ob, inpl, cutL, (uint64_t)(L.ops - p.ops)); // trim_overlap.rs:77
     if (st == RB_ST_OK && !L.bad) {
         const uint64_t ob2 = ob + L.n;
-        st = rb_tw_clip<LEG>(R, split, R.q_en, p.out_ops + ob2, &w, 1, ob2, lane, inpl ? &cutR : nullptr, (uint64_t)(R.ops - p.ops)); // :78
+        st = rb_pair_clip<LEG>(R, rb_tw_region{R, lane}, split, R.q_en, p.out_ops + ob2, &w, 1, ob2, inpl, cutR, (uint64_t)(R.ops - p.ops)); // :78
     }
     if (L.bad || R.bad) { // a boundary the region cannot answer: the serial kernel does the pair (it rewrites both clips)
-        pending(L.bad ? 5 : 6);
+        rb_pair_pending(p, pi, lane == 0, L.bad ? 5 : 6);
         return;
     }
-    if (inpl && st == RB_ST_OK && lane == 0) { // both clips stand: their end words, where they are (first before last: one op -> the same word twice)
-        p.out_ops[cutL.at_first] = cutL.w_first, p.out_ops[cutL.at_last] = cutL.w_last;
-        p.out_ops[cutR.at_first] = cutR.w_first, p.out_ops[cutR.at_last] = cutR.w_last;
-    }
+    if (inpl && st == RB_ST_OK && lane == 0) rb_pair_write_cuts(p.out_ops, cutL, cutR);
     w.status = st;
     w._pad = 1; // (diagnostic: done by the wave kernel; the serial kernel leaves 0)
     if (lane == 0) p.rows[pi] = w;
 }
-// the list (or, without one, every row) as the attempts behind the first walk it: a workgroup looks at 64 entries at a time, one per
+// the list as the attempts behind the first walk it: a workgroup looks at 64 entries at a time, one per
 // lane, and does those that are still pending one after the other (round 6; one entry at a time, two dependent loads each, took a
 // 48-workgroup attempt 0.35 ms to find out that a list of 150,000 pairs held nothing for it)
 struct rb_tw_walker {
@@ -996,7 +780,7 @@ struct rb_tw_walker {
     uint32_t pi; // per lane: the entry this lane looked at
 };
 __device__ __forceinline__ void rb_tw_walk_begin(const rb_trim_params &p, rb_tw_walker &w) {
-    w.n = p.pend_list ? rb_first64(*p.pend) : p.n_pairs;
+    w.n = rb_first64(*p.pend);
     w.e0 = 0, w.todo = 0ull, w.pi = 0u;
 }
 __device__ __forceinline__ bool rb_tw_walk_next(const rb_trim_params &p, rb_tw_walker &w, uint64_t *pi) { // wave-uniform
@@ -1005,7 +789,7 @@ __device__ __forceinline__ bool rb_tw_walk_next(const rb_trim_params &p, rb_tw_w
         //  entries at a time)
         if (w.e0 * gridDim.x + blockIdx.x >= w.n) return false;
         const uint64_t e = (w.e0 + (uint64_t)rb_lane()) * gridDim.x + blockIdx.x;
-        w.pi = e < w.n ? (p.pend_list ? p.pend_list[e] : (uint32_t)e) : 0u;
+        w.pi = e < w.n ? p.pend_list[e] : 0u;
         w.todo = rb_ballot(e < w.n && p.rows[w.pi].status == RB_ST_PENDING_INTERNAL);
         w.e0 += 64u;
     }
@@ -1013,16 +797,6 @@ __device__ __forceinline__ bool rb_tw_walk_next(const rb_trim_params &p, rb_tw_w
     w.todo &= w.todo - 1ull;
     *pi = (uint64_t)rb_readlane<uint32_t>(w.pi, l);
     return true;
-}
-// first attempt: a wavefront per pair
-#ifndef RB_TW_WPE
-#define RB_TW_WPE 8
-#endif
-template <int CAP, bool LEG>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RB_TW_WPE))) void rb_k_overlap_split_wave(rb_trim_params p) {
-    __shared__ uint32_t lds_w[2][3][CAP + 1];
-    __shared__ uint32_t lds_c[2][3][CAP / 16 + 2];
-    if (blockIdx.x < p.n_pairs) rb_tw_pair<CAP, LEG>(p, blockIdx.x, lds_w, lds_c);
 }
 // third attempt: the region arrays of a wavefront live in a slab of device memory (same code: the arrays are pointers).  Stores
 // and loads of one wavefront go through its CU's vector L1 in program order, so a lane sees what another lane of its own wave
@@ -1041,7 +815,7 @@ __global__ __launch_bounds__(64) void rb_k_overlap_split_wave_scratch(rb_trim_pa
         __builtin_amdgcn_wave_barrier();
     }
 }
-// second attempt, for the pairs the first one left: a few wavefronts with a large region each walk the list
+// the attempts in LDS, for the pairs the row form listed: wavefronts with a region of CAP ops each walk the list
 template <int CAP, bool LEG>
 __global__ __launch_bounds__(64) void rb_k_overlap_split_wave_pending(rb_trim_params p) {
     __shared__ uint32_t lds_w[2][3][CAP + 1];
@@ -1060,22 +834,17 @@ template <bool LEG>
 static hipError_t rb_launch_overlap_split_policy(const rb_trim_params *p, hipStream_t stream) {
     if (p->n_pairs == 0) return hipSuccess;
     rb_trim_params q = *p;
-    q.only_pending = 0;
-    // first attempt: four pairs per wavefront (k_trim4.hip); what it lists goes to the wave-per-pair kernel.  Without a list (its
-    // allocation failed) the wave-per-pair kernel looks at every pair, as it did before round 6.
-    if (q.pend_list) {
-        hipError_t e = rb_launch_overlap_split_quad(&q, 4, false, stream);
-        if (e != hipSuccess) return e;
-        q.only_pending = 2;
-        e = rb_launch_overlap_split_quad(&q, 8, true, stream); // the pairs whose overlap does not fit 64 ops of a record's end: 128
-        if (e != hipSuccess) return e;
-        const unsigned g0 = (unsigned)(p->n_pairs < 8192 ? p->n_pairs : 8192);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_wave_pending<RB_TW_CAP, LEG>), dim3(g0), dim3(64), 0, stream, q);
-    } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_wave<RB_TW_CAP, LEG>), dim3((unsigned)p->n_pairs), dim3(64), 0, stream, q);
-    }
-    q.only_pending = 2; // (the attempts behind the first walk its list; what they decline is listed already)
+    // first attempt: four pairs per wavefront (k_trim4.hip), which lists what it declines; every attempt behind it walks that list and
+    // leaves what it declines in turn where it is
+    q.list_declined = 1;
+    hipError_t e = rb_launch_overlap_split_quad(&q, 4, false, stream);
+    if (e != hipSuccess) return e;
+    q.list_declined = 0;
+    e = rb_launch_overlap_split_quad(&q, 8, true, stream); // the pairs whose overlap does not fit 64 ops of a record's end: 128
+    if (e != hipSuccess) return e;
+    // then a wavefront per pair, with larger and larger regions
     const unsigned g1 = (unsigned)(p->n_pairs < 8192 ? p->n_pairs : 8192);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_wave_pending<RB_TW_CAP, LEG>), dim3(g1), dim3(64), 0, stream, q);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_wave_pending<RB_TW_CAP1, LEG>), dim3(g1), dim3(64), 0, stream, q);
     const unsigned g2 = (unsigned)(p->n_pairs < 2048 ? p->n_pairs : 2048);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_wave_pending<RB_TW_CAP2, LEG>), dim3(g2), dim3(64), 0, stream, q);
@@ -1083,241 +852,12 @@ static hipError_t rb_launch_overlap_split_policy(const rb_trim_params *p, hipStr
         const unsigned g3 = (unsigned)(p->n_pairs < q.scratch_blocks ? p->n_pairs : q.scratch_blocks);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(rb_k_overlap_split_wave_scratch<RB_TW_CAP3, LEG>), dim3(g3), dim3(64), 0, stream, q);
     }
-    q.only_pending = 1;
-    static const bool no_serial = getenv("RB_DEBUG_TRIM_NO_SERIAL") != nullptr; // diagnostics: leave what the wave kernels declined as it is
+    static const bool no_serial = getenv("RB_DEBUG_TRIM_NO_SERIAL") != nullptr; // diagnostics: leave what the staged forms declined as it is
     if (no_serial) return hipGetLastError();
-    const uint64_t sblocks = q.pend_list ? std::min<uint64_t>((p->n_pairs + 63) / 64, 256) : (p->n_pairs + 63) / 64;
+    const uint64_t sblocks = std::min<uint64_t>((p->n_pairs + 63) / 64, 256);
     hipLaunchKernelGGL(rb_k_overlap_split, dim3((unsigned)sblocks), dim3(64), 0, stream, q);
     return hipGetLastError();
 }
 extern "C" hipError_t rb_launch_overlap_split(const rb_trim_params *p, hipStream_t stream) {
     return p->policy == RB_BSEARCH_LEGACY ? rb_launch_overlap_split_policy<true>(p, stream) : rb_launch_overlap_split_policy<false>(p, stream);
-}
-
-// ------------------------------------------------------------------------------------------------
-// between two passes of trim-paf: the clipped records of a pass become the batch's current records (include/rustybam_amd.h,
-// rb_dev_apply_pairs), and the current records gathered into a dense batch again (rb_dev_gather_records)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rb_k_apply_pairs(rb_apply_params p) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t k = t >> 1;
-    const int s = (int)(t & 1);
-    if (k >= p.n_pairs) return;
-    const rb_pair_row *row = &p.rows[k];
-    if (row->status != RB_ST_OK) return;
-    const uint32_t rec = s ? p.right[k] : p.left[k];
-    rb_norm_row n = p.norm[rec];
-    n.t_st = row->t_st[s], n.t_en = row->t_en[s], n.q_st = row->q_st[s], n.q_en = row->q_en[s];
-    n.first_op = 0, n.n_ops = row->out_n[s];
-    n.lead_ops = n.trail_ops = 0; // (a clip starts and ends on a match op: remove_trailing_indels finds nothing, paf.rs:218-220)
-    n.nmatch = row->nmatch[s], n.aln_len = row->aln_len[s];
-    p.norm[rec] = n;
-    p.op_off[rec] = row->out_off[s];
-}
-extern "C" hipError_t rb_launch_apply_pairs(const rb_apply_params *p, hipStream_t stream) {
-    if (p->n_pairs == 0) return hipSuccess;
-    hipLaunchKernelGGL(rb_k_apply_pairs, dim3((unsigned)((2 * p->n_pairs + 255) / 256)), dim3(256), 0, stream, *p);
-    return hipGetLastError();
-}
-
-__global__ __launch_bounds__(256) void rb_k_gather_records(rb_gather_params p) {
-    if (!p.fill) { // the kept length of every record
-        const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-        if (r < p.n_rec) p.new_off[r] = p.norm[r].status == RB_ST_OK ? p.norm[r].n_ops : 0u;
-        return;
-    }
-    const uint64_t r = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (r >= p.n_rec) return;
-    const uint64_t n = p.new_off[r + 1] - p.new_off[r];
-    const uint32_t *src = p.ops + p.op_off[r] + p.norm[r].first_op;
-    uint32_t *dst = p.new_ops + p.new_off[r];
-    for (uint64_t j = rb_lane(); j < n; j += 64) dst[j] = src[j];
-}
-extern "C" hipError_t rb_launch_gather_records(const rb_gather_params *p, hipStream_t stream) {
-    if (p->n_rec == 0) return hipSuccess;
-    if (!p->fill) hipLaunchKernelGGL(rb_k_gather_records, dim3((unsigned)((p->n_rec + 255) / 256)), dim3(256), 0, stream, *p);
-    else hipLaunchKernelGGL(rb_k_gather_records, dim3((unsigned)((p->n_rec + 3) / 4)), dim3(256), 0, stream, *p);
-    return hipGetLastError();
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// trim-paf: the pass driver's heavy half on the device (round 3).  Paf::overlapping_paf_recs (paf.rs:223-284) scans, per query
-// name, all pairs of records for overlaps on the query (bed::get_overlap, bed.rs:74-85), flags contained records (:244-249),
-// sorts ALL pairs by overlap (descending, stable) and then takes the first pair of every query name (:264-284).  Per query group
-// that is: the pair with the LARGEST overlap, among equals the FIRST in scan order (i ascending, then j) -- a segmented arg-max, no
-// global sort.  Groups are independent, so one pass = one launch: rb_k_trim_select (a thread per group; groups of more than
-// RB_TS_BIG records by the whole wave, one after the other), an exclusive scan that gives the chosen pairs dense slots and their
-// places in the ops arena, rb_k_trim_place.  The host keeps only the recursion loop (:286-288) and reads 64 bytes per pass.
-// ------------------------------------------------------------------------------------------------
-#define RB_TS_BIG 48u
-
-struct rb_tsel_best {
-    uint64_t ov;  // overlap (0: none yet)
-    uint64_t ord; // scan order i * m + j of the pair that holds it
-    uint32_t l, r;
-};
-__device__ __forceinline__ void rb_tsel_pair(const rb_tsel_params &p, uint32_t ri, uint32_t rj, uint64_t ord, rb_tsel_best &b, uint64_t &n_pairs) {
-    const rb_norm_row *a = &p.norm[ri], *c = &p.norm[rj];
-    const uint64_t st1 = a->q_st, en1 = a->q_en, st2 = c->q_st, en2 = c->q_en;
-    const uint64_t mn = en1 < en2 ? en1 : en2, mx = st1 > st2 ? st1 : st2;
-    if (mn <= mx) return;                       // bed.rs:74-85: no overlap
-    const uint64_t ov = mn - mx;
-    if (ov == en2 - st2) { p.contained[rj] = 1; return; } // paf.rs:244-249
-    if (ov == en1 - st1) { p.contained[ri] = 1; return; }
-    n_pairs++;
-    if (ov > b.ov || (ov == b.ov && ord < b.ord)) {
-        b.ov = ov, b.ord = ord;
-        if (st1 <= st2) b.l = ri, b.r = rj; // the smaller q_st is "left" (:252-256)
-        else b.l = rj, b.r = ri;
-    }
-}
-template <bool BIG_ONLY> // BIG_ONLY: the groups of up to 16 records have been done by rb_k_trim_select_rows
-__global__ __launch_bounds__(256) void rb_k_trim_select(rb_tsel_params p) {
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = rb_lane();
-    const uint64_t gg0 = g < p.n_groups ? p.grp_off[g] : 0, gm = g < p.n_groups ? p.grp_off[g + 1] - gg0 : 0;
-    const bool live = g < p.n_groups && (!BIG_ONLY || gm > 16u);
-    const uint64_t g0 = live ? gg0 : 0, m = live ? gm : 0;
-    for (uint64_t k = 0; k < m && m <= RB_TS_BIG; k++) p.contained[p.order[g0 + k]] = 0;
-    rb_tsel_best b = {0, 0, 0, 0};
-    uint64_t n_pairs = 0;
-    if (live && m <= RB_TS_BIG) {
-        for (uint64_t i = 0; i + 1 < m; i++) {
-            const uint32_t ri = p.order[g0 + i];
-            for (uint64_t j = i + 1; j < m; j++) rb_tsel_pair(p, ri, p.order[g0 + j], i * m + j, b, n_pairs);
-        }
-    }
-    // big groups of this wave: all lanes on one group at a time (lane l takes the pairs whose j is l mod 64)
-    unsigned long long big = __ballot(live && m > RB_TS_BIG);
-    while (big) {
-        const int src = __builtin_ctzll(big);
-        big &= big - 1ull;
-        const uint64_t bg0 = __shfl(g0, src, 64), bm = __shfl(m, src, 64);
-        for (uint64_t k = (uint64_t)lane; k < bm; k += 64) p.contained[p.order[bg0 + k]] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        rb_tsel_best bb = {0, 0, 0, 0};
-        uint64_t np = 0;
-        for (uint64_t i = 0; i + 1 < bm; i++) {
-            const uint32_t ri = p.order[bg0 + i];
-            for (uint64_t j = i + 1 + (uint64_t)lane; j < bm; j += 64) rb_tsel_pair(p, ri, p.order[bg0 + j], i * bm + j, bb, np);
-        }
-        for (int off = 32; off > 0; off >>= 1) { // the wave's best: largest overlap, then smallest scan order
-            const uint64_t oov = __shfl_xor(bb.ov, off, 64), oord = __shfl_xor(bb.ord, off, 64);
-            const uint32_t ol = (uint32_t)__shfl_xor((int)bb.l, off, 64), orr = (uint32_t)__shfl_xor((int)bb.r, off, 64);
-            if (oov > bb.ov || (oov == bb.ov && oov != 0 && oord < bb.ord)) bb.ov = oov, bb.ord = oord, bb.l = ol, bb.r = orr;
-            np += __shfl_xor(np, off, 64);
-        }
-        if (lane == src) b = bb, n_pairs = np;
-    }
-    if (!live) return;
-    p.slot[g] = b.ov ? (uint64_t)p.norm[b.l].n_ops + (uint64_t)p.norm[b.r].n_ops : 0ull;
-    // has: 1 for a group with a pair, and in the high half the pairs the group leaves for a later pass (one pair per name and pass, :266-284):
-    // the scan that gives the pairs their dense slots sums those as well (no atomic: 2.5e6 adds to one word were most of a pass's selection)
-    // (a group's share is capped at (2^32 - 1) / n_groups so that the sum cannot leave its 32 bits: n_deferred is 0 exactly when nothing is left,
-    //  and the exact count whenever no single group leaves more than that)
-    const uint64_t dcap = 0xFFFFFFFFull / p.n_groups, dleft = n_pairs > 1 ? n_pairs - 1 : 0ull;
-    p.has[g] = (b.ov ? 1ull : 0ull) | ((dleft < dcap ? dleft : dcap) << 32);
-    p.cand[2 * g] = b.l, p.cand[2 * g + 1] = b.r;
-}
-// The same selection for groups of up to 16 records, a group per ROW of 16 lanes (round 6): lane j holds record j of the group -- ONE read of its
-// norm row, where the thread-per-group form above walks every pair with four strided loads --, the outer index i runs row-uniform, record i's
-// span reaches the lanes by ds_bpermute, lane j keeps the best pair (i, j) it has seen, and the row's best (largest overlap, then the smallest
-// scan order i m + j) falls out of four rotate-and-compare steps.  Groups of more than 16 records are left to the kernel above (big_only).
-__global__ __launch_bounds__(256) void rb_k_trim_select_rows(rb_tsel_params p) {
-    const int lane = rb_lane();
-    const uint32_t gbase = (uint32_t)lane & 48u, gl = (uint32_t)lane & 15u;
-    const uint64_t g = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 4u + ((uint32_t)lane >> 4);
-    const bool live = g < p.n_groups;
-    const uint64_t g0 = live ? p.grp_off[g] : 0, m64 = live ? p.grp_off[g + 1] - g0 : 0;
-    const bool mine = live && m64 <= 16u; // (row-uniform)
-    const uint32_t m = mine ? (uint32_t)m64 : 0u;
-    const bool have = gl < m;
-    const uint32_t r = have ? p.order[g0 + gl] : 0u;
-    uint64_t st = 0, en = 0;
-    if (have) st = p.norm[r].q_st, en = p.norm[r].q_en;
-    bool cont = false;
-    rb_tsel_best b = {0, 0, 0, 0};
-    uint32_t np = 0; // candidate pairs this lane has seen as their j
-    uint32_t w_m = m; // (the wavefront walks as far as its largest group)
-#pragma unroll
-    for (int off = 16; off < 64; off <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)w_m, off, 64);
-        w_m = w_m > o ? w_m : o;
-    }
-    w_m = rb_first(w_m);
-    for (uint32_t i = 0; i + 1u < w_m; i++) {
-        // record i of every row's group, to all lanes of the row (rows whose group is shorter see zeros and have no lane behind i)
-        const uint32_t ri = rb_row_read(r, gbase, i);
-        const uint64_t st1 = ((uint64_t)rb_row_read((uint32_t)(st >> 32), gbase, i) << 32) | rb_row_read((uint32_t)st, gbase, i);
-        const uint64_t en1 = ((uint64_t)rb_row_read((uint32_t)(en >> 32), gbase, i) << 32) | rb_row_read((uint32_t)en, gbase, i);
-        const bool pair = have && gl > i && i + 1u < m;
-        const uint64_t mn = en1 < en ? en1 : en, mx = st1 > st ? st1 : st;
-        const bool ovl = pair && mn > mx;                      // bed.rs:74-85
-        const uint64_t ov = ovl ? mn - mx : 0;
-        const bool c2 = ovl && ov == en - st;                  // paf.rs:244-249: record j is contained
-        const bool c1 = ovl && !c2 && ov == en1 - st1;         // ... record i is
-        cont |= c2;
-        if (rb_row_ballot(c1, gbase) != 0u && gl == i) cont = true;
-        if (ovl && !c2 && !c1) {
-            np++;
-            const uint64_t ord = (uint64_t)i * m + gl;
-            if (ov > b.ov || (ov == b.ov && ord < b.ord)) {
-                b.ov = ov, b.ord = ord;
-                if (st1 <= st) b.l = ri, b.r = r; // the smaller q_st is "left" (:252-256)
-                else b.l = r, b.r = ri;
-            }
-        }
-    }
-    // the row's best pair and its number of candidates
-    uint32_t np_row = rb_row_sum(np);
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-        const uint64_t oov = ((uint64_t)rb_row_ror((uint32_t)(b.ov >> 32), off) << 32) | rb_row_ror((uint32_t)b.ov, off);
-        const uint64_t oord = ((uint64_t)rb_row_ror((uint32_t)(b.ord >> 32), off) << 32) | rb_row_ror((uint32_t)b.ord, off);
-        const uint32_t ol = rb_row_ror(b.l, off), orr = rb_row_ror(b.r, off);
-        if (oov > b.ov || (oov == b.ov && oov != 0 && oord < b.ord)) b.ov = oov, b.ord = oord, b.l = ol, b.r = orr;
-    }
-    if (have) p.contained[r] = cont ? 1 : 0;
-    if (mine && gl == 0u) {
-        p.slot[g] = b.ov ? (uint64_t)p.norm[b.l].n_ops + (uint64_t)p.norm[b.r].n_ops : 0ull;
-        const uint64_t dcap = 0xFFFFFFFFull / p.n_groups, dleft = np_row > 1u ? np_row - 1u : 0u; // (the cap: rb_k_trim_select)
-        p.has[g] = (b.ov ? 1ull : 0ull) | ((dleft < dcap ? dleft : dcap) << 32); // (high half: pairs left for a later pass)
-        p.cand[2 * g] = b.l, p.cand[2 * g + 1] = b.r;
-    }
-}
-__global__ __launch_bounds__(256) void rb_k_trim_place(rb_tsel_params p) {
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= p.n_groups) return;
-    const uint64_t h0 = p.has[g], h1 = p.has[g + 1]; // scanned: low half = pairs in front of the group, high half = deferred pairs in front of it
-    const uint64_t k = h0 & 0xFFFFFFFFull, k1 = h1 & 0xFFFFFFFFull;
-    if (g + 1 == p.n_groups) p.pass->n_pairs = k1, p.pass->n_deferred = h1 >> 32, p.pass->ops_end = p.out_base + p.slot[g + 1];
-    if (k1 == k) return; // no pair in this group
-    p.left[k] = p.cand[2 * g], p.right[k] = p.cand[2 * g + 1];
-    p.pair_out_off[k] = p.out_base + p.slot[g];
-}
-// the worst status of a pass's pair rows (0 = every pair was cut), for the host's one read per pass
-__global__ __launch_bounds__(256) void rb_k_trim_check(const rb_pair_row *rows, uint64_t n_pairs, rb_trim_pass *pass) {
-    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n_pairs && rows[k].status != RB_ST_OK) atomicMax(&pass->bad_status, rows[k].status);
-}
-extern "C" hipError_t rb_launch_trim_select(const rb_tsel_params *p, uint64_t *block_sums, hipStream_t stream) {
-    hipError_t e = rb_fill_async(p->pass, 0, sizeof(rb_trim_pass), stream); // (the library's own fill kernel: capi.hip says why)
-    if (e != hipSuccess) return e;
-    if (p->n_groups == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((p->n_groups + 255) / 256);
-    hipLaunchKernelGGL(rb_k_trim_select_rows, dim3((unsigned)((p->n_groups + 15) / 16)), dim3(256), 0, stream, *p);
-    hipLaunchKernelGGL(rb_k_trim_select<true>, dim3(blocks), dim3(256), 0, stream, *p);
-    e = rb_launch_exclusive_scan(p->slot, p->n_groups, block_sums, nullptr, stream);
-    if (e != hipSuccess) return e;
-    e = rb_launch_exclusive_scan(p->has, p->n_groups, block_sums, nullptr, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rb_k_trim_place, dim3(blocks), dim3(256), 0, stream, *p);
-    return hipGetLastError();
-}
-extern "C" hipError_t rb_launch_trim_check(const rb_pair_row *rows, uint64_t n_pairs, rb_trim_pass *pass, hipStream_t stream) {
-    if (n_pairs == 0) return hipSuccess;
-    hipLaunchKernelGGL(rb_k_trim_check, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, rows, n_pairs, pass);
-    return hipGetLastError();
 }

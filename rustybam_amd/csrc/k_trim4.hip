@@ -14,8 +14,9 @@
 //     sums), so what lies outside the region is never read, but for the record's first two ops and its last one, fetched with the rest;
 //   * searches by query offset: a ballot over the 16 lanes' chunk bases, then the T ops of that chunk side by side; per-lane searches
 //     of the split candidates: a branch-free descent through the query prefixes in LDS.
-// Same arrays, same formulas and the same order of exits as rb_tw_pair (k_trim.hip) -- the two are checked against each other and
-// against the oracle by tests/test_gpu_trim.py, tests/test_gpu_trim_legacy.py and tests/soak/soak_trim.py.  A pair this kernel does not
+// Same arrays and formulas as rb_tw_pair (k_trim.hip); how a pair is opened and declined and the clip itself are the SAME code
+// (rb_pair.h) -- the two forms are checked against each other and against the oracle by tests/test_gpu_trim.py,
+// tests/test_gpu_trim_legacy.py and tests/soak/soak_trim.py.  A pair this kernel does not
 // take (irregular record, region too small, a walk that leaves the region, a non-query run of T ops; under the legacy policy also a D / N
 // run of more than one op) is listed in pend_list and done by the kernels behind it: the wave-per-pair kernel with its larger regions,
 // then the serial one.
@@ -23,9 +24,9 @@
 // The policy matters in one place: a query position that repeats in qpos_aln -- the last base (in op order) of a query op i that a run
 // of D / N ops of `run` units follows.  Its equal range is [klo, klo + run], klo = U_i + len_i - 1 (U_i: units before op i); the modern
 // search returns klo + run, the legacy one rb_legacy_probe32(N, klo, klo + run) (indices only: the same on both strands).  That unit
-// decides the score of the base (rb_q4_build) and where a cut that ends on it lands (rb_q4_clip); the split reads the score prefixes
+// decides the score of the base (rb_q4_build) and where a cut that ends on it lands (rb_q4_region::behind_last_base); the split reads the score prefixes
 // and needs no policy of its own.
-#include "rb_trim.h"
+#include "rb_pair.h"
 #include "rb_launch.h"
 
 // ---- a record's region in LDS -----------------------------------------------------------------------------------------------------
@@ -42,31 +43,11 @@ struct rb_q4_slab {
 };
 static_assert((2 * sizeof(rb_q4_slab<4>) / 4) % 64 == 16 && (2 * sizeof(rb_q4_slab<8>) / 4) % 64 == 16, "slab stride");
 
-struct rb_qrec { // row-uniform values, one copy per lane
-    const uint32_t *ops;
-    uint32_t n, i0, m;
-    uint64_t t_st, t_en, q_st, q_en;
-    bool minus, bad;
-    uint32_t N, Qtot, Rtot;
+struct rb_qrec : rb_prec { // row-uniform values, one copy per lane
     uint32_t bQ, eQ;           // query bases before the region / before its end
     uint32_t lastq;            // the region's last query op (absolute index); n: none
     uint32_t w0, w1, wl;       // the record's first, second and last op word
-#ifdef RB_Q4_DEBUG
-    uint32_t dbg[5];
-#endif
     uint32_t cq, cu, cr;       // PER LANE: query bases / units / reference bases before this lane's chunk (op i0 + T lane), absolute
-};
-struct rb_qpos {
-    uint32_t i, w, pre;
-};
-struct rb_qend {
-    uint32_t k;
-    rb_qpos o;
-    uint32_t R, Q;
-};
-struct rb_qcut {
-    uint64_t at_first, at_last;
-    uint32_t w_first, w_last;
 };
 
 template <int T>
@@ -186,9 +167,6 @@ __device__ __forceinline__ bool rb_q4_build(rb_qrec &v, rb_q4_slab<T> &S, uint32
     uint32_t cq = bQ + iq - sq;
     int32_t cs = isc - ss;
     v.cq = cq, v.bQ = bQ, v.eQ = bQ + tq;
-#ifdef RB_Q4_DEBUG
-    v.dbg[0] = bU, v.dbg[1] = bR, v.dbg[2] = tu, v.dbg[3] = tr, v.dbg[4] = tq;
-#endif
     v.cu = bU + iu - su, v.cr = bR + ir - sr;
     uint32_t qv[T];
     int32_t sv[T];
@@ -218,8 +196,8 @@ __device__ __forceinline__ bool rb_q4_build(rb_qrec &v, rb_q4_slab<T> &S, uint32
 
 // the query op of the region that holds query offset x (row-uniform); i = n: none
 template <int T>
-__device__ __forceinline__ rb_qpos rb_q4_find(const rb_qrec &v, const rb_q4_slab<T> &S, uint32_t x, uint32_t gl, uint32_t gbase) {
-    rb_qpos o;
+__device__ __forceinline__ rb_ppos rb_q4_find(const rb_qrec &v, const rb_q4_slab<T> &S, uint32_t x, uint32_t gl, uint32_t gbase) {
+    rb_ppos o;
     o.i = v.n, o.w = RB_NULL_OP, o.pre = 0;
     const uint32_t lem = rb_row_ballot(v.cq <= x, gbase);
     if (!lem) return o; // in front of the region
@@ -244,227 +222,86 @@ __device__ __forceinline__ uint32_t rb_q4_before(const rb_qrec &v, const rb_q4_s
     }
     return rb_row_read(KIND == 0 ? v.cu : v.cr, gbase, c) + rb_row_sum(x);
 }
-// truncate_record_by_query (paf.rs:785-823) on a staged regular record: rb_tw_clip (k_trim.hip) for a row of 16 lanes
-template <int T, bool LEG>
-__device__ __forceinline__ uint32_t rb_q4_clip(rb_qrec &v, const rb_q4_slab<T> &S, uint64_t new_q_st, uint64_t new_q_en, uint32_t *out, rb_pair_row *row,
-                                               int s, uint64_t out_base, uint32_t gl, uint32_t gbase, bool in_place, rb_qcut &cut, uint64_t rec_base) {
-    if (!(new_q_st >= v.q_st) || !(new_q_en <= v.q_en) || new_q_en == 0) return RB_ST_PANIC_ASSERT; // :787-788
-    if (new_q_en <= new_q_st) { // an empty range: the serial kernel says what the reference does with it
-        v.bad = true;
-        return RB_ST_OK;
-    }
-    const uint32_t n = v.n, N = v.N;
-    // the match-type unit truncate_record_by_query ends up at for query position p: qpos_to_idx_match (paf.rs:564-590) = the last
-    // unit whose qpos equals p (modern policy) or the one the legacy search probes first (LEG), then the nearest match-type unit in the
-    // search direction
-    auto resolve = [&](uint64_t p, bool search_up, rb_qend *e) -> bool {
-        if (p < v.q_st || p >= v.q_en) return false;
-        const uint32_t x = (uint32_t)(v.minus ? v.q_en - 1 - p : p - v.q_st);
-        if (x < v.bQ || x >= v.eQ) {
-            // outside the region: only the record's own first / last query base is asked for there.  A regular record starts and
-            // ends on a match op; its last base is its last unit, its first base its first unit unless that op has one base and a
-            // D / N run behind it (the run repeats the position: left to the kernels behind this one)
-            if (x == 0u) {
-                if (rb_len(v.w0) < 2u && n > 1u && !rb_in(RB_QRY_MASK, rb_opc(v.w1))) return false;
-                e->k = 0, e->o.i = 0, e->o.w = v.w0, e->o.pre = 0, e->R = 0, e->Q = 0;
-                return true;
+// the region as truncate_record_by_query (rb_pair_clip, rb_pair.h) asks for it, for a row of 16 lanes
+template <int T>
+struct rb_q4_region {
+    static constexpr uint32_t WIDTH = 16u;
+    const rb_qrec &v;
+    const rb_q4_slab<T> &S;
+    uint32_t gl, gbase;
+    __device__ __forceinline__ uint32_t lane() const { return gl; }
+    __device__ __forceinline__ uint32_t word(uint32_t k) const { return S.w[k]; }
+    __device__ __forceinline__ uint32_t qpre(uint32_t k) const { return S.Qc[k]; }
+    __device__ __forceinline__ uint32_t q_begin() const { return v.bQ; }
+    __device__ __forceinline__ uint32_t q_end() const { return v.eQ; }
+    __device__ __forceinline__ uint32_t first_word() const { return v.w0; }
+    __device__ __forceinline__ uint32_t second_word() const { return v.w1; }
+    __device__ __forceinline__ uint32_t last_word() const { return v.wl; }
+    __device__ __forceinline__ rb_ppos find_q(uint32_t x) const { return rb_q4_find<T>(v, S, x, gl, gbase); }
+    __device__ __forceinline__ uint32_t units_before(uint32_t i) const { return rb_q4_before<T, 0>(v, S, i, gl, gbase); }
+    __device__ __forceinline__ uint32_t ref_before(uint32_t i) const { return rb_q4_before<T, 1>(v, S, i, gl, gbase); }
+    // the op is updated as the run is walked; under the legacy policy the run is one op (rb_q4_build declines the others)
+    template <bool LEG>
+    __device__ __forceinline__ bool behind_last_base(const rb_ppos &o, uint32_t &u, rb_ppos &om) const {
+        if constexpr (LEG) { // the unit is the one the probe lands on
+            const uint32_t k2 = o.i - v.i0 + 1u;
+            if (k2 >= v.m) {
+                if (v.i0 + v.m < v.n) return false; // (the run, if there is one, lies behind the region)
+            } else if (!rb_in(RB_QRY_MASK, rb_opc(S.w[k2]))) {
+                const uint32_t w2 = S.w[k2];
+                // (a run that leaves the region or has a second op: the kernels behind this one)
+                if (k2 + 1u >= v.m ? v.i0 + v.m < v.n : !rb_in(RB_QRY_MASK, rb_opc(S.w[k2 + 1u]))) return false;
+                const uint32_t kk = rb_legacy_probe32(v.N, u, u + rb_len(w2));
+                if (kk != u) om.i = v.i0 + k2, om.w = w2, om.pre = u + 1u, u = kk;
             }
-            if (x + 1u == v.Qtot) {
-                const uint32_t len = rb_len(v.wl);
-                e->k = N - 1u, e->o.i = n - 1u, e->o.w = v.wl, e->o.pre = N - len, e->R = v.Rtot - len, e->Q = v.Qtot - len;
-                return true;
-            }
-            return false;
-        }
-        const rb_qpos o = rb_q4_find<T>(v, S, x, gl, gbase);
-        if (o.i >= n) return false;
-        const uint32_t j = x - o.pre, len = rb_len(o.w);
-        const uint32_t ub = rb_q4_before<T, 0>(v, S, o.i, gl, gbase);
-        uint32_t u = ub + j;
-        rb_qpos om;
-        om.i = o.i, om.w = o.w, om.pre = ub;
-        if constexpr (LEG) {
-            if (j + 1u == len) { // last base of the op: the D / N units behind it repeat its position; the unit is the one the probe lands on
-                const uint32_t k2 = o.i - v.i0 + 1u;
-                if (k2 >= v.m) {
-                    if (v.i0 + v.m < n) return false; // (the run, if there is one, lies behind the region)
-                } else if (!rb_in(RB_QRY_MASK, rb_opc(S.w[k2]))) {
-                    const uint32_t w2 = S.w[k2];
-                    // (a run that leaves the region or has a second op: the kernels behind this one)
-                    if (k2 + 1u >= v.m ? v.i0 + v.m < n : !rb_in(RB_QRY_MASK, rb_opc(S.w[k2 + 1u]))) return false;
-                    const uint32_t kk = rb_legacy_probe32(N, u, u + rb_len(w2));
-                    if (kk != u) om.i = v.i0 + k2, om.w = w2, om.pre = u + 1u, u = kk;
-                }
-            }
-        } else if (j + 1u == len) { // last base of the op: the D / N units behind it repeat its position, and the last of them is the unit
+        } else { // the last unit of the run
             uint32_t k2 = o.i - v.i0 + 1u;
             for (; k2 < v.m && !rb_in(RB_QRY_MASK, rb_opc(S.w[k2])); k2++) {
                 const uint32_t w2 = S.w[k2];
                 om.i = v.i0 + k2, om.w = w2, om.pre = u + 1u;
                 u += rb_len(w2);
             }
-            if (k2 >= v.m && v.i0 + v.m < n) return false; // (the run leaves the region)
+            if (k2 >= v.m && v.i0 + v.m < v.n) return false; // (the run leaves the region)
         }
-        // nearest match-type unit, up (paf.rs:581-583) or down (:585-587)
-        uint32_t km = u;
-        if (!rb_in(RB_MATCH_MASK, rb_opc(om.w))) {
-            if (search_up) {
-                uint32_t uu = om.pre + rb_len(om.w), k2 = om.i - v.i0 + 1u;
-                for (; k2 < v.m && !rb_in(RB_MATCH_MASK, rb_opc(S.w[k2])); k2++) uu += rb_len(S.w[k2]);
-                if (k2 >= v.m) return false; // (no match op behind it inside the region; at the record's end the reference panics: serial kernel)
-                km = uu;
-                om.i = v.i0 + k2, om.w = S.w[k2], om.pre = uu;
-            } else {
-                uint32_t uu = om.pre, k2 = om.i - v.i0;
-                bool got = false;
-                while (k2 > 0u) {
-                    k2--;
-                    if (rb_in(RB_MATCH_MASK, rb_opc(S.w[k2]))) {
-                        got = true;
-                        break;
-                    }
-                    uu -= rb_len(S.w[k2]);
-                }
-                if (!got) return false;
-                km = uu - 1u;
-                om.i = v.i0 + k2, om.w = S.w[k2], om.pre = uu - rb_len(S.w[k2]);
-            }
-        }
-        e->k = km, e->o = om, e->R = rb_q4_before<T, 1>(v, S, om.i, gl, gbase), e->Q = S.Qc[om.i - v.i0];
         return true;
-    };
-    rb_qend A, B; // paf.rs:792-796: the start searches up on '+' and down on '-', the end the other way
-    if (!resolve(new_q_st, !v.minus, &A) || !resolve(new_q_en - 1, v.minus, &B)) {
-        v.bad = true;
-        return RB_ST_OK;
     }
-    auto unit = [&](const rb_qend &e, uint64_t *tpos, uint64_t *qpos) { // both are match-type units
-        const uint32_t off = e.k - e.o.pre;
-        *tpos = v.t_st + e.R + off;
-        *qpos = v.minus ? v.q_en - 1 - e.Q - off : v.q_st + e.Q + off;
-    };
-    uint64_t tp, qp_st, qp_en;
-    unit(A, &tp, &qp_st);
-    unit(B, &tp, &qp_en);
-    const uint64_t nq_st = qp_st, nq_en = qp_en + 1;
-    if (A.k > B.k) { // :799-801
-        const rb_qend t = A;
-        A = B;
-        B = t;
-    }
-    uint64_t t0, t1, qd;
-    unit(A, &t0, &qd);
-    unit(B, &t1, &qd);
-    const uint64_t nt_st = t0, nt_en = t1 + 1; // :802-803
-    // subset_cigar + collapse (:807-808): ops ia..ib with the first / last length cut; adjacent ops differ, nothing merges; both ends
-    // are match-type units, so the strip of :819-822 removes nothing (rb_tw_clip says why nothing is summed)
-    const uint32_t ia = A.o.i, ib = B.o.i, cnt = ib - ia + 1;
-    const uint32_t lf = cnt == 1 ? B.k - A.k + 1u : A.o.pre + rb_len(A.o.w) - A.k, ll = cnt == 1 ? lf : B.k - B.o.pre + 1u;
-    cut.at_first = rec_base + ia, cut.at_last = rec_base + ib;
-    cut.w_first = (lf << 4) | rb_opc(A.o.w), cut.w_last = (ll << 4) | rb_opc(B.o.w);
-    if (in_place) { // (nothing is copied; rec_base = where the record's kept ops begin in the ops array)
-        out_base = rec_base + ia;
-    } else {
-        for (uint32_t j = gl; j < cnt; j += 16u) {
-            const uint32_t wv = v.ops[ia + j];
-            out[j] = j == 0 ? ((lf << 4) | rb_opc(wv)) : (j == cnt - 1 ? ((ll << 4) | rb_opc(wv)) : wv);
-        }
-    }
-    if (nt_en < nt_st) return RB_ST_PANIC_INTEGRITY_T;
-    if (qp_en < qp_st) return RB_ST_PANIC_INTEGRITY_Q;
-    const uint32_t units = B.k - A.k + 1u;
-    row->t_st[s] = nt_st;
-    row->t_en[s] = nt_en;
-    row->q_st[s] = nq_st;
-    row->q_en[s] = nq_en;
-    row->nmatch[s] = (uint32_t)((nt_en - nt_st) + (nq_en - nq_st) - units);
-    row->aln_len[s] = units;
-    row->out_off[s] = out_base;
-    row->out_n[s] = cnt;
-    return RB_ST_OK;
-}
+};
 
-#ifndef RB_Q4_STOP
-#define RB_Q4_STOP 0 // diagnostics (tools/r06_quad_decomp.sh): != 0 ends a pair early -- 1 behind the staging of both records, 2 behind the searches
-                     // of the overlap's end ops, 3 behind the split, 4 behind the left clip; 9: the whole pair, but a declined pair is listed without the atomic counter
-                     // (measured: 2.41 ms with it, 2.39 - 2.41 without, per 2.5e6 pairs); the rows are wrong then, only the time is of interest
-#endif
 template <int T, bool LEG>
 __device__ __forceinline__ void rb_q4_pair(const rb_trim_params &p, const uint64_t pi, const uint32_t gbase, const uint32_t gl, const uint32_t g) {
     __shared__ __attribute__((aligned(16))) rb_q4_slab<T> lds[4][2]; // (here and not in the kernels: as an argument it would be a generic pointer)
-    rb_pair_row w;
-    w.split_idx = 0;
-    w.split_score = 0;
-    w.status = RB_ST_OK;
-    w._pad = 0;
-    for (int s = 0; s < 2; s++) {
-        w.t_st[s] = w.t_en[s] = w.q_st[s] = w.q_en[s] = 0;
-        w.nmatch[s] = w.aln_len[s] = 0;
-        w.out_off[s] = 0;
-        w.out_n[s] = 0;
-    }
-    const uint32_t rl = p.left[pi], rr = p.right[pi];
-    const rb_norm_row nl = p.norm[rl], nr = p.norm[rr];
-    if (nl.status != RB_ST_OK || nr.status != RB_ST_OK) { // aligned_pairs() panics (paf.rs:273-274, :782)
-        w.status = nl.status != RB_ST_OK ? nl.status : nr.status;
-        if (gl == 0) p.rows[pi] = w;
-        return;
-    }
-    auto pending = [&](uint32_t why) { // (why: diagnostics, RB_DEBUG_TRIM_NO_SERIAL; whoever does the pair rewrites the whole row)
-        if (gl == 0) {
-#if RB_Q4_STOP == 9 // (diagnostics, timing only: what the one counter costs -- the list is garbage)
-            if (!p.only_pending) p.pend_list[pi] = (uint32_t)pi;
-#else
-            if (!p.only_pending) p.pend_list[atomicAdd(p.pend, 1ull)] = (uint32_t)pi; // (listed once: by the first attempt)
-#endif
-            p.rows[pi].status = RB_ST_PENDING_INTERNAL, p.rows[pi].split_idx = why;
-        }
-    };
+    rb_pair_row w = rb_pair_row_empty();
+    rb_qrec L, R;
+    uint64_t st_ovl, en_ovl;
     // (LEG: this instantiation serves the legacy policy; the modern one declines it -- rb_launch_overlap_split_quad picks by p->policy)
-    if ((!LEG && p.policy == RB_BSEARCH_LEGACY) || !(nl.flags & RB_F_REGULAR) || !(nr.flags & RB_F_REGULAR) || nl.n_ops == 0 || nr.n_ops == 0) {
-        pending(1);
-        return;
-    }
+    uint32_t why = rb_pair_open<LEG>(p, pi, gl == 0u, w, L, R, &st_ovl, &en_ovl);
+    if (why == RB_PAIR_CLOSED) return;
     const int32_t ms = p.match_score, ds = p.diff_score, is = p.indel_score;
-    {   // the sums below are 32 bits wide: scores so large that a sum over both records' query bases could leave 2^29 are left to the
-        // wave-per-pair kernel, which sums in 64 bits
+    if (why != 1u) { // the sums below are 32 bits wide: scores so large that a sum over both records' query bases could leave 2^29 are left to the
+                     // wave-per-pair kernel, which sums in 64 bits (in the order of exits this comes behind decline 1 and before decline 2)
         const uint32_t a = (uint32_t)(ms < 0 ? -ms : ms), b = (uint32_t)(ds < 0 ? -ds : ds), c = (uint32_t)(is < 0 ? -is : is);
         const uint64_t smax = a > b ? (a > c ? a : c) : (b > c ? b : c);
-        if (smax * ((nl.q_en - nl.q_st) + (nr.q_en - nr.q_st)) >= (1ull << 29)) {
-            pending(8);
-            return;
-        }
+        if (smax * ((L.q_en - L.q_st) + (R.q_en - R.q_st)) >= (1ull << 29)) why = 8u;
     }
-    rb_qrec L, R;
-    L.ops = p.ops + p.op_off[rl] + nl.first_op, L.n = nl.n_ops;
-    L.t_st = nl.t_st, L.t_en = nl.t_en, L.q_st = nl.q_st, L.q_en = nl.q_en, L.minus = p.strand[rl] == (uint8_t)'-';
-    L.N = nl.aln_len, L.Qtot = (uint32_t)(nl.q_en - nl.q_st), L.Rtot = (uint32_t)(nl.t_en - nl.t_st), L.bad = false;
-    R.ops = p.ops + p.op_off[rr] + nr.first_op, R.n = nr.n_ops;
-    R.t_st = nr.t_st, R.t_en = nr.t_en, R.q_st = nr.q_st, R.q_en = nr.q_en, R.minus = p.strand[rr] == (uint8_t)'-';
-    R.N = nr.aln_len, R.Qtot = (uint32_t)(nr.q_en - nr.q_st), R.Rtot = (uint32_t)(nr.t_en - nr.t_st), R.bad = false;
-    const uint64_t st_ovl = L.q_st > R.q_st ? L.q_st : R.q_st; // trim_overlap.rs:43-44
-    const uint64_t en_ovl = L.q_en < R.q_en ? L.q_en : R.q_en;
-    if (en_ovl <= st_ovl || st_ovl < L.q_st || en_ovl > L.q_en || st_ovl < R.q_st || en_ovl > R.q_en) { // (no overlap: the serial kernel says what the reference does)
-        pending(2);
+    if (why != RB_PAIR_OPENED) {
+        rb_pair_pending(p, pi, gl == 0u, why);
         return;
     }
-    // query offsets of the overlap in each record's op order, and the end of the record they lie at
-    auto span = [&](rb_qrec &v, uint32_t *xa, uint32_t *xb) -> bool {
-        *xa = (uint32_t)(!v.minus ? st_ovl - v.q_st : v.q_en - en_ovl);
-        *xb = (uint32_t)(!v.minus ? en_ovl - 1 - v.q_st : v.q_en - 1 - st_ovl);
-        const bool from_end = v.n > 16u * T && *xa > v.Qtot - 1u - (*xb < v.Qtot ? *xb : v.Qtot - 1u);
+    // the end of the record the overlap lies at: the region is the record's first or last 16 T ops
+    auto place = [&](rb_qrec &v) -> bool {
+        const bool from_end = v.n > 16u * T && v.xa > v.Qtot - 1u - (v.xb < v.Qtot ? v.xb : v.Qtot - 1u);
         v.m = v.n < 16u * T ? v.n : 16u * T;
         v.i0 = from_end ? v.n - v.m : 0u;
         return from_end;
     };
-    uint32_t lxa, lxb, rxa, rxb;
-    const bool lfe = span(L, &lxa, &lxb), rfe = span(R, &rxa, &rxb);
+    const uint32_t lxa = L.xa, lxb = L.xb, rxa = R.xa, rxb = R.xb;
+    const bool lfe = place(L), rfe = place(R);
     rb_q4_slab<T> &SL = lds[g][0], &SR = lds[g][1];
     uint32_t tl[T], tr[T];
     rb_q4_load<T>(L, gl, tl);
     rb_q4_load<T>(R, gl, tr);
     if (!rb_q4_build<T, LEG>(L, SL, gl, gbase, tl, lfe, ms, ds, is) || !rb_q4_build<T, LEG>(R, SR, gl, gbase, tr, rfe, ms, ds, is)) {
-        pending(3);
+        rb_pair_pending(p, pi, gl == 0u, 3);
         return;
     }
     // What only the CUTS need of a record -- where its ops lie, its coordinates, its totals, its first two ops and its last -- waits in the slab's
@@ -492,33 +329,25 @@ __device__ __forceinline__ void rb_q4_pair(const rb_trim_params &p, const uint64
     stash(R, SR);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-#if RB_Q4_STOP == 1
-    if (gl == 0) p.rows[pi].split_idx = L.eQ + R.eQ;
-    return;
-#endif
     int32_t best = 0;
     uint32_t best_idx = 0;
     // the ops that hold the first and the last overlapped query base of each record
-    const rb_qpos La = rb_q4_find<T>(L, SL, lxa, gl, gbase), Lb = rb_q4_find<T>(L, SL, lxb, gl, gbase);
-    const rb_qpos Ra = rb_q4_find<T>(R, SR, rxa, gl, gbase), Rb = rb_q4_find<T>(R, SR, rxb, gl, gbase);
+    const rb_ppos La = rb_q4_find<T>(L, SL, lxa, gl, gbase), Lb = rb_q4_find<T>(L, SL, lxb, gl, gbase);
+    const rb_ppos Ra = rb_q4_find<T>(R, SR, rxa, gl, gbase), Rb = rb_q4_find<T>(R, SR, rxb, gl, gbase);
     if (La.i >= L.n || Lb.i >= L.n || Ra.i >= R.n || Rb.i >= R.n) { // the overlap is not inside the regions
-        pending(4);
+        rb_pair_pending(p, pi, gl == 0u, 4);
         return;
     }
     // the run behind the last overlapped base must end inside the region (its score is that base's score)
     if ((Lb.i >= L.lastq && L.i0 + L.m < L.n) || (Rb.i >= R.lastq && R.i0 + R.m < R.n)) {
-        pending(7);
+        rb_pair_pending(p, pi, gl == 0u, 7);
         return;
     }
-#if RB_Q4_STOP == 2
-    if (gl == 0) p.rows[pi].split_idx = La.i + Lb.i + Ra.i + Rb.i;
-    return;
-#endif
     // Everything below works in k = bases behind st_ovl (0 .. n), 32 bits, and on query offsets in op order, so that the two strands
     // share one instruction stream: the boundary k of the overlap is query offset x = xa + k on '+' and xb + 1 - k on '-' (op order
     // runs against the positions there), and G(k) = W(x) on '+', -W(x) on '-', W = score of the query bases in front of offset x.
     const uint32_t n_ovl = (uint32_t)(en_ovl - st_ovl);
-    auto W_ends = [&](const rb_qrec &v, const rb_q4_slab<T> &S, const rb_qpos &oa, const rb_qpos &ob, uint32_t xa, uint32_t xb, int32_t *g0, int32_t *gn) {
+    auto W_ends = [&](const rb_qrec &v, const rb_q4_slab<T> &S, const rb_ppos &oa, const rb_ppos &ob, uint32_t xa, uint32_t xb, int32_t *g0, int32_t *gn) {
         const int32_t Wa = S.SP[oa.i - v.i0] + (xa - oa.pre) * rb_tw_score(rb_opc(oa.w), ms, ds, is); // W(xa)
         const uint32_t kb = ob.i - v.i0;
         const int32_t Wb = xb + 1u < ob.pre + rb_len(ob.w) ? S.SP[kb] + (xb + 1u - ob.pre) * rb_tw_score(rb_opc(ob.w), ms, ds, is)
@@ -620,22 +449,14 @@ __device__ __forceinline__ void rb_q4_pair(const rb_trim_params &p, const uint64
         });
         if (cb > best) best = cb, best_idx = ck;
     }
-#if RB_Q4_STOP == 3
-    if (gl == 0) p.rows[pi].split_idx = best_idx;
-    return;
-#endif
     w.split_idx = best_idx;
     w.split_score = best;
     const uint64_t split = st_ovl + best_idx;
     const bool inpl = p.in_place != 0;
     const uint64_t ob = inpl ? 0ull : p.pair_out_off[pi];
-    rb_qcut cutL, cutR;
+    rb_pcut cutL, cutR;
     unstash(L, SL);
-    uint32_t st = rb_q4_clip<T, LEG>(L, SL, L.q_st, split, p.out_ops + ob, &w, 0, ob, gl, gbase, inpl, cutL, (uint64_t)(L.ops - p.ops)); // trim_overlap.rs:77
-#if RB_Q4_STOP == 4
-    if (gl == 0) p.rows[pi] = w;
-    return;
-#endif
+    uint32_t st = rb_pair_clip<LEG>(L, rb_q4_region<T>{L, SL, gl, gbase}, L.q_st, split, p.out_ops + ob, &w, 0, ob, inpl, cutL, (uint64_t)(L.ops - p.ops)); // trim_overlap.rs:77
     // ... and what the left cut left (its half of the row, its two end words) waits there while the right record is cut
     if (gl == 0u) {
         uint32_t *y = SL.pad;
@@ -648,10 +469,10 @@ __device__ __forceinline__ void rb_q4_pair(const rb_trim_params &p, const uint64
     unstash(R, SR);
     if (st == RB_ST_OK && !L.bad) {
         const uint64_t ob2 = ob + L.n;
-        st = rb_q4_clip<T, LEG>(R, SR, split, R.q_en, p.out_ops + ob2, &w, 1, ob2, gl, gbase, inpl, cutR, (uint64_t)(R.ops - p.ops)); // :78
+        st = rb_pair_clip<LEG>(R, rb_q4_region<T>{R, SR, gl, gbase}, split, R.q_en, p.out_ops + ob2, &w, 1, ob2, inpl, cutR, (uint64_t)(R.ops - p.ops)); // :78
     }
     if (L.bad || R.bad) { // a boundary the region cannot answer
-        pending(L.bad ? 5 : 6);
+        rb_pair_pending(p, pi, gl == 0u, L.bad ? 5 : 6);
         return;
     }
     if (gl == 0) {
@@ -664,15 +485,9 @@ __device__ __forceinline__ void rb_q4_pair(const rb_trim_params &p, const uint64
             w.nmatch[0] = c.x, w.aln_len[0] = c.y, w.out_off[0] = ((uint64_t)c.w << 32) | c.z, w.out_n[0] = d.x;
             cutL.w_first = d.y, cutL.w_last = d.z, cutL.at_first = ((uint64_t)e.x << 32) | d.w, cutL.at_last = ((uint64_t)e.z << 32) | e.y;
         }
-        if (inpl && st == RB_ST_OK) { // both clips stand: their end words, where they are (first before last: one op -> the same word twice)
-            p.out_ops[cutL.at_first] = cutL.w_first, p.out_ops[cutL.at_last] = cutL.w_last;
-            p.out_ops[cutR.at_first] = cutR.w_first, p.out_ops[cutR.at_last] = cutR.w_last;
-        }
+        if (inpl && st == RB_ST_OK) rb_pair_write_cuts(p.out_ops, cutL, cutR);
         w.status = st;
         w._pad = 1; // (diagnostic: done by a wave kernel; the serial kernel leaves 0)
-#ifdef RB_Q4_DEBUG
-        w.t_st[0] = ((uint64_t)L.dbg[0] << 32) | L.dbg[1], w.t_en[0] = ((uint64_t)L.dbg[2] << 32) | L.dbg[3], w.q_st[0] = ((uint64_t)L.dbg[4] << 32) | L.N, w.q_en[0] = ((uint64_t)L.i0 << 32) | L.m;
-#endif
         p.rows[pi] = w;
     }
 }

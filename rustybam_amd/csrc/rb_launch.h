@@ -128,7 +128,7 @@ struct rb_format_params {
 extern "C" hipError_t rb_launch_parse_cigars(const rb_parse_params *p, bool fill, hipStream_t stream);
 extern "C" hipError_t rb_launch_format_cigars(const rb_format_params *p, bool fill, hipStream_t stream);
 
-// ---- k_trim.hip, k_trim4.hip: trim-paf ----
+// ---- k_trim.hip, k_trim4.hip, k_trim_pass.hip: trim-paf ----
 struct rb_apply_params {
     uint64_t n_pairs;
     const uint32_t *left, *right;

@@ -1,5 +1,5 @@
-// rb_trim.h -- what the trim-paf pair kernels share (k_trim.hip: the wave-per-pair and the serial kernel; k_trim4.hip: four pairs per
-// wavefront) and what capi.hip fills in.
+// rb_trim.h -- the parameters of the trim-paf pair kernels (k_trim.hip: the wave-per-pair and the serial kernel; k_trim4.hip: four pairs
+// per wavefront), which capi.hip fills in.  What the kernels themselves share is in rb_pair.h.
 #pragma once
 #include "rb_serial.h"
 
@@ -15,11 +15,11 @@ struct rb_trim_params {
     int policy;
     rb_pair_row *rows;
     uint32_t *out_ops;
-    int only_pending;
+    int list_declined;       // != 0: this is the first attempt -- it lists the pairs it declines in pend_list (set by rb_launch_overlap_split)
     uint32_t *scratch;       // device memory for the third attempt of the wave kernel (regions too large for LDS), or NULL
     uint32_t scratch_blocks; // slabs in it
-    // pairs the first wave kernel declines, so that the attempts behind it do not have to look at every row: pend[0] = how many,
-    // pend_list[0 .. n_pairs) their indices (NULL: every row is looked at)
+    // pairs the first attempt declines, so that the attempts behind it do not have to look at every row: pend[0] = how many,
+    // pend_list[0 .. n_pairs) their indices
     unsigned long long *pend;
     uint32_t *pend_list;
     // RB_TRIM_IN_PLACE (out_ops is the batch's own ops array): a regular record the wave kernel clips is not copied -- a clip by query

@@ -87,7 +87,7 @@ def main():
     eng.trim_reserve(n // 4 + 1)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    if os.environ.get("RB_C4_ONE_PASS"):  # (diagnostics, tools/prof_c4_decomp.sh: one pass of a library variant whose rows are wrong, then out)
+    if os.environ.get("RB_C4_ONE_PASS"):  # (diagnostics: one pass of a library variant whose rows are wrong, then out)
         try:
             T.run((1, 1, 1), MOD, max_passes=1)
         except Exception as e:  # (more passes wanted, or rows a stopped variant left unfinished)
