@@ -20,6 +20,7 @@
  *                            + PafRecord::truncate_record_by_query        paf.rs:785-823
  *                            (the pass / recursion driver Paf::overlapping_paf_recs, paf.rs:210-305, stays on the host)
  *   rb_dev_nucfreq        <- nucfreq::nucfreq / region_nucfreq            nucfreq.rs:61-95, :111-125
+ *   rb_dev_largest        <- liftover --largest: sort_by id, group_by id, max_by_key     main.rs:200-208
  *
  * Conventions
  *   - Plain C types only.  Every `rb_dev_*` pointer argument is a DEVICE pointer (HBM) owned by
@@ -322,6 +323,24 @@ int rb_dev_liftover(rb_ctx *ctx, const rb_plan *plan, const rb_batch_view *batch
                     int bsearch_policy, void *workspace, rb_hit_row *rows, uint64_t rows_cap, uint32_t *out_ops,
                     uint64_t out_cap, rb_counters *counters);
 
+/* ---- liftover --largest (main.rs:200-208) ------------------------------------------------------ *
+ * The reference sorts the records of trim_paf_by_rgns stably by id and keeps, per id, the LAST record of largest t_en - t_st.  Here the
+ * hit rows of rb_dev_liftover are reduced to one row per KEY where they lie: the host interns the id strings into dense u32 keys (in
+ * ascending bytewise order of the strings, if sel[] is to come out in the reference's print order); the device never sees a string.
+ *   key of row k   rec_key[rows[k].rec] if rows[k].flags & RB_HIT_INSIDE (liftover.rs:23-25: the record keeps its OWN id), else
+ *                  win_key[rows[k].win] (liftover.rs:20).  Rows whose status is not RB_ST_OK take no part (the reference dropped them or
+ *                  panicked) and their keys are not looked at; a row whose key is >= n_keys takes no part either and is counted in out[1].
+ *   winner of a key the row of largest t_en - t_st (a full u64), among equals the LARGEST ROW INDEX: hit rows are in the order of the
+ *                  reference's record list, so that is max_by_key's last maximum behind the stable sort.
+ *   rows [n_rows] as rb_dev_liftover wrote them (16-byte aligned); win_key [n_win]; rec_key [n_rec] (NULL allowed only if no row is INSIDE: an
+ *   INSIDE row then counts as a bad key); sel [n_keys] OUT: the winners' row indices, dense, in ascending key order; out: DEVICE memory,
+ *   16 bytes OUT: out[0] = n_sel, out[1] = rows ignored because their key was >= n_keys (or rec_key was NULL); scratch:
+ *   rb_largest_scratch_bytes(n_keys) bytes, 256-byte aligned, zeroed by the call itself on the stream, every time.  Enqueues on the context's
+ *   stream, does not synchronise.  n_rows == 0 or n_keys == 0 is valid (n_sel = 0).  Two calls on the same rows write the same bytes. */
+size_t rb_largest_scratch_bytes(uint64_t n_keys);
+int rb_dev_largest(rb_ctx *ctx, const rb_hit_row *rows, uint64_t n_rows, const uint32_t *win_key, const uint32_t *rec_key,
+                   uint64_t n_keys, uint64_t *sel, uint64_t *out, void *scratch);
+
 /* ---- break-paf -------------------------------------------------------------------------------- *
  * Pieces between indels longer than max_size, record order then piece order; same row shape,
  * rb_hit_row.win = piece ordinal among the candidate windows of the record. */
@@ -442,6 +461,13 @@ void rb_host_free(void *p);
  *     is computed), scanned (reduce_out / norm_out, either may be NULL), lifted over the windows in descriptor mode, and the
  *     clipped CIGAR of every hit row is printed on the device: row k's text is row_text[row_text_off[k] .. [k + 1]) (empty
  *     for rows whose status is not RB_ST_OK).  rows / row_text_off / row_text are malloc'ed (rb_host_free).
+ * rb_host_liftover_largest_text: the same for liftover --largest.  win_key [n_win] and inside_key (the key of the empty id "", which a record
+ *     read from a file has) are keys below n_keys (n_keys < 2^32 - 1).  The hit rows stay on the device; rb_dev_largest picks one per key,
+ *     and only those rows are downloaded, given format items and printed: rows / row_text_off / row_text come back with n_sel entries in
+ *     ascending key order, rows[].rec and rows[].win still index the input.  *declined != 0: nothing was selected and *n_rows = 0, the
+ *     caller takes the record route --  1: a record whose norm row has RB_F_STRIPPED has an OK INSIDE row (its id carries a _TO.<lead>.<trail>
+ *     suffix, paf.rs:726-731, that no key stands for; minimap2-style input has no such record); 2: some hit row has a status of
+ *     RB_ST_PANIC_NOTFOUND or above (the reference panics inside trim_paf_by_rgns, before it selects).
  */
 size_t rb_text_scratch_bytes(uint64_t n);
 int rb_dev_parse_cigars(rb_ctx *ctx, const uint8_t *text, const uint64_t *text_off, const uint64_t *text_end, uint64_t n_rec,
@@ -459,6 +485,12 @@ int rb_host_liftover_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint
                           const uint8_t *strand, const uint32_t *contig, uint64_t n_win, const uint32_t *w_contig, const uint64_t *w_st,
                           const uint64_t *w_en, int bsearch_policy, uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out,
                           rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters);
+int rb_host_liftover_largest_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                  const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
+                                  const uint8_t *strand, const uint32_t *contig, uint64_t n_win, const uint32_t *w_contig, const uint64_t *w_st,
+                                  const uint64_t *w_en, int bsearch_policy, uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out,
+                                  rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters,
+                                  const uint32_t *win_key, uint64_t n_keys, uint32_t inside_key, int *declined);
 /* the same around rb_dev_break (break-paf, main.rs:271-281), and the record scan alone (stats --paf, main.rs:50-58) */
 int rb_host_break_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
                        const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,

@@ -313,6 +313,46 @@ class Engine:
                                       C.c_void_p(out_ptr), C.c_uint64(out_cap), C.c_void_p(counters_ptr)),
                   "rb_dev_break")
 
+    def largest_scratch_bytes(self, n_keys):
+        f = self.L.rb_largest_scratch_bytes
+        f.restype = C.c_size_t
+        return int(f(C.c_uint64(n_keys)))
+
+    def dev_largest(self, rows_ptr, n_rows, win_key_ptr, rec_key_ptr, n_keys, sel_ptr, out_ptr, scratch_ptr):
+        """liftover --largest over hit rows where they lie (every pointer a device address, rec_key_ptr may be 0); enqueues on the context's
+        stream: sel_ptr[0 .. out_ptr[0]) = the winners' row indices in key order, out_ptr[1] = rows left out for their key"""
+        self._chk(self.L.rb_dev_largest(self.ctx, C.c_void_p(rows_ptr or 0), C.c_uint64(n_rows), C.c_void_p(win_key_ptr or 0),
+                                        C.c_void_p(rec_key_ptr or 0), C.c_uint64(n_keys), C.c_void_p(sel_ptr or 0), C.c_void_p(out_ptr),
+                                        C.c_void_p(scratch_ptr or 0)), "rb_dev_largest")
+
+    def largest(self, rows, win_key, rec_key, n_keys):
+        """rb_dev_largest on host arrays (rows: HIT_DT; rec_key may be None): uploads, runs, downloads -> (sel u64 [n_sel], n_bad)"""
+        rows, win_key = _arr(rows, HIT_DT), _arr(win_key, np.uint32)
+        rec_key = None if rec_key is None else _arr(rec_key, np.uint32)
+        n_keys = int(n_keys)
+        bufs = []
+
+        def dev(n_bytes, src=None):
+            bufs.append(self.dev_alloc(max(n_bytes, 256)))
+            if src is not None and src.nbytes:
+                self._chk(self.L.rb_dev_upload(self.ctx, C.c_void_p(bufs[-1]), _p(src), C.c_size_t(src.nbytes)), "rb_dev_upload")
+            return bufs[-1]
+        try:
+            d_rows, d_wk = dev(rows.nbytes, rows), dev(win_key.nbytes, win_key)
+            d_rk = 0 if rec_key is None else dev(rec_key.nbytes, rec_key)
+            d_sel, d_out, d_scr = dev(8 * n_keys), dev(16), dev(self.largest_scratch_bytes(n_keys))
+            self.dev_largest(d_rows, len(rows), d_wk, d_rk, n_keys, d_sel, d_out, d_scr)
+            out = np.zeros(2, np.uint64)
+            self._chk(self.L.rb_dev_download(self.ctx, _p(out), C.c_void_p(d_out), C.c_size_t(16)), "rb_dev_download")
+            sel = np.zeros(int(out[0]), np.uint64)
+            if len(sel):
+                self._chk(self.L.rb_dev_download(self.ctx, _p(sel), C.c_void_p(d_sel), C.c_size_t(sel.nbytes)), "rb_dev_download")
+            return sel, int(out[1])
+        finally:
+            self.sync()
+            for b in bufs:
+                self.dev_free(b)
+
     # ---- host-buffer wrappers ----
     def scan_records(self, ops, op_off, t_st, t_en, q_st, q_en, strand):
         ops, op_off = _arr(ops, np.uint32), _arr(op_off, np.uint64)

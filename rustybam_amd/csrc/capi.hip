@@ -1240,6 +1240,37 @@ extern "C" int rb_dev_gather_records(rb_ctx *ctx, uint64_t n_rec, const uint32_t
     return RB_OK;
 }
 
+// ---- liftover --largest ---------------------------------------------------------------------------
+// scratch of rb_dev_largest: [best_span (n_keys + 1) u64][best_row n_keys u64][block sums of the scan]
+static size_t largest_span_bytes(uint64_t n_keys) { return ((size_t)(n_keys + 1) * 8 + 255) & ~(size_t)255; }
+static size_t largest_row_bytes(uint64_t n_keys) { return ((size_t)n_keys * 8 + 255) & ~(size_t)255; }
+extern "C" size_t rb_largest_scratch_bytes(uint64_t n_keys) {
+    return largest_span_bytes(n_keys) + largest_row_bytes(n_keys) + (rb_scan_block_sums_count(n_keys) + 4) * 8;
+}
+// worst_status: NULL, or 4 bytes of device memory for the largest panic status among all rows (rb_launch.h)
+static int largest_impl(rb_ctx *ctx, const rb_hit_row *rows, uint64_t n_rows, const uint32_t *win_key, const uint32_t *rec_key, uint64_t n_keys,
+                        uint64_t *sel, uint64_t *out, void *scratch, uint32_t *worst_status) {
+    if (!ctx || !out || (n_rows && (!rows || !win_key)) || (n_keys && (!sel || !scratch))) return RB_E_INVALID;
+    if (((uintptr_t)rows & 15u) != 0) return fail(ctx, RB_E_INVALID, "rows must be 16-byte aligned");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    rb_largest_params p;
+    memset(&p, 0, sizeof p);
+    char *sc = (char *)scratch;
+    p.rows = rows, p.n_rows = n_rows, p.win_key = win_key, p.rec_key = rec_key, p.n_keys = n_keys;
+    p.best_span = (unsigned long long *)sc;
+    p.best_row = (unsigned long long *)(sc + largest_span_bytes(n_keys));
+    p.sel = sel, p.out = (unsigned long long *)out, p.worst_status = worst_status;
+    HIPCHK(ctx, rb_fill_async(out, 0, 16, ctx->stream));
+    if (worst_status) HIPCHK(ctx, rb_fill_async(worst_status, 0, 4, ctx->stream));
+    if (n_keys) HIPCHK(ctx, rb_fill_async(sc, 0, largest_span_bytes(n_keys) + largest_row_bytes(n_keys), ctx->stream)); // (every call: nothing of the last one counts)
+    HIPCHK(ctx, rb_launch_largest(&p, (uint64_t *)(sc + largest_span_bytes(n_keys) + largest_row_bytes(n_keys)), ctx->stream));
+    return RB_OK;
+}
+extern "C" int rb_dev_largest(rb_ctx *ctx, const rb_hit_row *rows, uint64_t n_rows, const uint32_t *win_key, const uint32_t *rec_key,
+                              uint64_t n_keys, uint64_t *sel, uint64_t *out, void *scratch) {
+    return largest_impl(ctx, rows, n_rows, win_key, rec_key, n_keys, sel, out, scratch, nullptr);
+}
+
 // ---- CIGAR text ----------------------------------------------------------------------------------
 extern "C" size_t rb_text_scratch_bytes(uint64_t n) { return (rb_scan_block_sums_count(n) + 4) * 8; }
 extern "C" int rb_dev_parse_cigars(rb_ctx *ctx, const uint8_t *text, const uint64_t *text_off, const uint64_t *text_end, uint64_t n_rec,
@@ -1596,14 +1627,23 @@ extern "C" int rb_host_format_cigars(rb_ctx *ctx, const uint32_t *ops, uint64_t 
     return RB_OK;
 }
 
-// text in -> text out around the clip kernels; scan_only stops after the record scan (rb_host_scan_text)
+// what rb_host_liftover_largest_text adds to rb_host_liftover_text
+struct largest_text {
+    const uint32_t *win_key;
+    uint64_t n_keys;
+    uint32_t inside_key;
+    int *declined;
+};
+// text in -> text out around the clip kernels; scan_only stops after the record scan (rb_host_scan_text).  lg: liftover --largest -- the hit
+// rows stay on the device, rb_dev_largest picks one per key, and only those rows come back, get format items and are printed
 static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool scan_only, uint64_t n_rec, const uint8_t *text,
                           uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en,
                           const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand, const uint32_t *contig, uint64_t n_win,
                           const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en, int policy, uint8_t *cig_status,
                           rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off,
-                          uint8_t **row_text, rb_counters *counters) {
+                          uint8_t **row_text, rb_counters *counters, const largest_text *lg = nullptr) {
     if (!ctx || (n_rec && (!cig_off || !cig_end || !cig_status))) return RB_E_INVALID;
+    if (lg) *lg->declined = 0;
     if (n_rec == 0) { // an empty file: no rows, no text
         if (rows) *rows = nullptr;
         if (n_rows) *n_rows = 0;
@@ -1686,8 +1726,39 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
     uint32_t *d_out = nullptr;
     rc = lift_sized(ctx, b, op_off.data(), contig, n_win, w_contig, w_st, w_en, d_norm, is_break, max_size, policy | RB_LIFT_DESCRIPTORS,
                     &d_rows, &d_out, &hc, tl);
+    uint64_t nr = hc.n_hits;
+    const rb_hit_row *d_take = d_rows; // the rows that go to the host, and the descriptor of row k of them at d_take_desc[4k]
+    const uint32_t *d_take_desc = d_out;
+    if (!rc && lg) { // ---- one row per key ----
+        const uint32_t *d_wkey = nullptr;
+        uint32_t *d_rkey = nullptr, *d_sdesc = nullptr;
+        uint64_t *d_sel = nullptr, *d_lout = nullptr; // d_lout: out[0], out[1] of rb_dev_largest, then the worst panic status of all rows
+        rb_hit_row *d_srows = nullptr;
+        void *d_lscr = nullptr;
+        uint64_t lout[3] = {0, 0, 0};
+        rc = b.up(lg->win_key, (size_t)n_win, &d_wkey);
+        if (!rc) rc = b.alloc((size_t)n_rec, &d_rkey);
+        if (!rc) rc = b.alloc((size_t)lg->n_keys + 1, &d_sel);
+        if (!rc) rc = b.alloc(3, &d_lout);
+        if (!rc) rc = b.alloc(rb_largest_scratch_bytes(lg->n_keys), (uint8_t **)&d_lscr);
+        if (!rc && rb_launch_largest_rec_keys(d_norm, n_rec, lg->inside_key, d_rkey, ctx->stream) != hipSuccess) rc = fail(ctx, RB_E_HIP, "rb_launch_largest_rec_keys");
+        if (!rc) rc = largest_impl(ctx, d_rows, nr, d_wkey, d_rkey, lg->n_keys, d_sel, d_lout, d_lscr, (uint32_t *)(d_lout + 2));
+        if (!rc) rc = rb_dev_download(ctx, lout, d_lout, sizeof lout);
+        if (rc) return rc;
+        // every window key is inside the key space (checked by the caller of this function), so a row left out is an INSIDE row of a
+        // stripped record; a panic status anywhere is the reference's panic inside trim_paf_by_rgns, before it selects anything
+        if ((uint32_t)lout[2] != 0 || lout[1] != 0) {
+            *lg->declined = (uint32_t)lout[2] != 0 ? 2 : 1;
+            return RB_OK;
+        }
+        nr = lout[0];
+        rc = b.alloc((size_t)nr + 1, &d_srows);
+        if (!rc) rc = b.alloc((size_t)nr * 4 + 4, &d_sdesc);
+        if (!rc && rb_launch_largest_gather(d_rows, d_out, d_sel, nr, d_srows, d_sdesc, ctx->stream) != hipSuccess) rc = fail(ctx, RB_E_HIP, "rb_launch_largest_gather");
+        d_take = d_srows, d_take_desc = d_sdesc;
+        rb_lap("largest + gather", tl);
+    }
     // ---- rows to the host, clip items back to the device, text out ----
-    const uint64_t nr = hc.n_hits;
     std::vector<uint32_t> desc;
     uint64_t *d_first = nullptr, *d_toff = nullptr;
     uint32_t *d_cnt3 = nullptr; // count | first_len | last_len, three arrays of nr
@@ -1697,10 +1768,10 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
         *row_text_off = (uint64_t *)malloc((size_t)(nr + 2) * 8);
         if (!*rows || !*row_text_off) rc = fail(ctx, RB_E_NOMEM, "malloc(rows)");
     }
-    if (!rc && nr) rc = rb_dev_download(ctx, *rows, d_rows, (size_t)nr * sizeof(rb_hit_row));
+    if (!rc && nr) rc = rb_dev_download(ctx, *rows, d_take, (size_t)nr * sizeof(rb_hit_row));
     if (!rc && nr) {
         desc.resize((size_t)nr * 4);
-        rc = rb_dev_download(ctx, desc.data(), d_out, (size_t)nr * 16); // descriptor of row k at out_ops[4k]
+        rc = rb_dev_download(ctx, desc.data(), d_take_desc, (size_t)nr * 16); // descriptor of row k at out_ops[4k]
     }
     rb_lap("rows D2H", tl);
     if (!rc) {
@@ -1761,6 +1832,22 @@ extern "C" int rb_host_liftover_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t 
                                      uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters) {
     return host_lift_text(ctx, false, 0, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig, n_win,
                           w_contig, w_st, w_en, policy, cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, counters);
+}
+extern "C" int rb_host_liftover_largest_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                             const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
+                                             const uint64_t *q_en, const uint8_t *strand, const uint32_t *contig, uint64_t n_win,
+                                             const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en, int policy, uint8_t *cig_status,
+                                             rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows,
+                                             uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters, const uint32_t *win_key,
+                                             uint64_t n_keys, uint32_t inside_key, int *declined) {
+    if (!ctx || !declined || (n_win && !win_key)) return RB_E_INVALID;
+    // (0xFFFFFFFF is the key the wrapper gives a stripped record: it must lie outside the key space)
+    if (n_keys >= 0xFFFFFFFFull || inside_key >= n_keys) return fail(ctx, RB_E_INVALID, "inside_key %u outside the %llu keys", inside_key, (unsigned long long)n_keys);
+    for (uint64_t i = 0; i < n_win; i++)
+        if (win_key[i] >= n_keys) return fail(ctx, RB_E_INVALID, "window %llu: key %u outside the %llu keys", (unsigned long long)i, win_key[i], (unsigned long long)n_keys);
+    const largest_text lg{win_key, n_keys, inside_key, declined};
+    return host_lift_text(ctx, false, 0, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig, n_win,
+                          w_contig, w_st, w_en, policy, cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, counters, &lg);
 }
 extern "C" int rb_host_break_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
                                   const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,

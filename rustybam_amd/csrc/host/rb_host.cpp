@@ -1165,7 +1165,9 @@ std::vector<std::string> assemble_lines(const TextFile &f, const std::vector<rb_
 }
 } // namespace
 
-bool liftover_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text, TextRuns *runs) {
+// largest: main.rs:200-208 on the device (rb_host_liftover_largest_text) -- the rows that come back are the one record per id, in id order
+static bool lift_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text, TextRuns *runs,
+                           bool largest) {
     // (one-shot command: the gigabytes behind these two are left to the end of the process instead of being unmapped piece by piece)
     TextFile &f = *new TextFile;
     if (!f.load(paf_path)) return false; // the caller takes the general path
@@ -1187,19 +1189,45 @@ bool liftover_file_text(Engine &eng, const std::string &paf_path, const std::vec
     std::vector<rb_norm_row> norm(n);
     TextRows &R = *new TextRows;
     rb_counters cnt;
-    eng.check(rb_host_liftover_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
-                                    f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(), w_contig.data(),
-                                    w_st.data(), w_en.data(), eng.bsearch_policy, cig_status.data(), red.data(), norm.data(), &R.rows,
-                                    &R.n_rows, &R.toff, &R.text, &cnt),
-              "rb_host_liftover_text");
-    lap("rb_host_liftover_text", tl);
+    int declined = 0;
+    if (largest) {
+        // the ids as keys: the window ids and "" (the id of a record that lies inside its window, liftover.rs:23-25), numbered in ascending
+        // bytewise order -- Rust's String order, the order of main.rs:201's sort -- so the rows come back in the order they are printed in
+        std::vector<std::string_view> ids(1, std::string_view());
+        for (const Region &r : rgns) ids.emplace_back(r.id);
+        std::sort(ids.begin(), ids.end());
+        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        std::vector<uint32_t> win_key(rgns.size());
+        for (size_t i = 0; i < rgns.size(); i++) win_key[i] = (uint32_t)(std::lower_bound(ids.begin(), ids.end(), std::string_view(rgns[i].id)) - ids.begin());
+        eng.check(rb_host_liftover_largest_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(),
+                                                f.t_st.data(), f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(),
+                                                w_contig.data(), w_st.data(), w_en.data(), eng.bsearch_policy, cig_status.data(), red.data(),
+                                                norm.data(), &R.rows, &R.n_rows, &R.toff, &R.text, &cnt, win_key.data(), ids.size(), 0u, &declined),
+                  "rb_host_liftover_largest_text");
+        lap("rb_host_liftover_largest_text", tl);
+    } else {
+        eng.check(rb_host_liftover_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
+                                        f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(), w_contig.data(),
+                                        w_st.data(), w_en.data(), eng.bsearch_policy, cig_status.data(), red.data(), norm.data(), &R.rows,
+                                        &R.n_rows, &R.toff, &R.text, &cnt),
+                  "rb_host_liftover_text");
+        lap("rb_host_liftover_text", tl);
+    }
     if (!f.check_loaded(cig_status, red)) return false;
     for (size_t i = 0; i < n; i++) panic_on(norm[i].status, "aligned_pairs", i); // liftover.rs:119-121
+    if (declined) return false; // a stripped record inside a window, or a hit row that panics: the record route knows its id / replays the panic
     RunMarks marks;
     out_text = assemble_lines(f, norm, R, &rgns, runs ? &marks : nullptr);
     if (runs) marks_to_runs(marks, out_text, *runs);
     lap("assemble lines", tl);
     return true;
+}
+
+bool liftover_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text, TextRuns *runs) {
+    return lift_file_text(eng, paf_path, rgns, out_text, runs, false);
+}
+bool liftover_largest_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text) {
+    return lift_file_text(eng, paf_path, rgns, out_text, nullptr, true);
 }
 
 // main.rs:271-281, text in -> text out

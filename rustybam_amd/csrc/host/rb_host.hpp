@@ -106,6 +106,10 @@ std::vector<std::string> trim_paf_by_rgns_text(Engine &eng, const std::vector<Re
 // (rb_host_liftover_text); false = the file needs the general path (a line with two cg tags), nothing was produced
 bool liftover_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text,
                         TextRuns *runs = nullptr);
+// main.rs:186-214 with --largest (no --qbed), text in -> text out: the hit rows never leave the device, rb_dev_largest keeps the last record of
+// largest target span per id (main.rs:200-208) and only those records are printed, in id order (rb_host_liftover_largest_text); false = take
+// the record route (two cg tags, a stripped record that lies inside a window, a hit row that panics), nothing was produced
+bool liftover_largest_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text);
 // the same two routes as a pipeline over chunks of a big plain file (a few host threads, each with its own context on `device`):
 // the sink receives the chunks' outputs in file order while later chunks are still being read / clipped / printed.  A chunk's text
 // is contig-major within the chunk (runs); false = not applicable or a line needs the general parser (pipeline_started(): the

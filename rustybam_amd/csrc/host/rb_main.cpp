@@ -1013,6 +1013,16 @@ int main(int argc, char **argv) {
                     done(0);
                 }
             }
+            if (largest && !qbed && text_path && !g_worker.on) { // the same with main.rs:200-208 on the device: only one record per id is printed
+                std::vector<std::string> text;
+                if (rb::liftover_largest_file_text(eng, paf_path, rgns, text)) {
+                    lap("liftover --largest (text to text)", tl);
+                    emit(text);
+                    fflush(stdout);
+                    lap("write", tl);
+                    done(0);
+                }
+            }
             rb::Paf paf = rb::Paf::from_file(eng, paf_path);
             lap("decode + check_integrity", tl);
             if (largest) { // main.rs:200-208: stable sort by id, keep the LAST record with maximal target span per id

@@ -167,6 +167,25 @@ extern "C" hipError_t rb_launch_gather_records(const rb_gather_params *p, hipStr
 extern "C" hipError_t rb_launch_trim_select(const rb_tsel_params *p, uint64_t *block_sums, hipStream_t stream);
 extern "C" hipError_t rb_launch_trim_check(const rb_pair_row *rows, uint64_t n_pairs, rb_trim_pass *pass, hipStream_t stream);
 
+// ---- k_largest.hip: liftover --largest ----
+struct rb_largest_params {
+    const rb_hit_row *rows;
+    uint64_t n_rows;
+    const uint32_t *win_key; // [n_win] key of a row that is not INSIDE
+    const uint32_t *rec_key; // [n_rec] key of an INSIDE row (NULL: such a row has a bad key)
+    uint64_t n_keys;
+    unsigned long long *best_span; // [n_keys + 1] zeroed; pass 1: the largest span of every key.  Behind pass 2 it is free again and holds
+                                   // the compaction's counts (1: the key has a winner), then their exclusive prefix
+    unsigned long long *best_row;  // [n_keys] zeroed; pass 2: 1 + the largest row index among the key's rows of that span (0: no row)
+    uint64_t *sel;                 // [n_keys] OUT the winners' row indices, dense, in ascending key order
+    unsigned long long *out;       // zeroed; [0] = n_sel, [1] = rows left out for their key
+    uint32_t *worst_status;        // NULL, or zeroed: the largest status of RB_ST_PANIC_NOTFOUND and above among ALL rows (rb_host_liftover_largest_text)
+};
+extern "C" hipError_t rb_launch_largest(const rb_largest_params *p, uint64_t *block_sums, hipStream_t stream);
+extern "C" hipError_t rb_launch_largest_rec_keys(const rb_norm_row *norm, uint64_t n_rec, uint32_t inside_key, uint32_t *rec_key, hipStream_t stream);
+extern "C" hipError_t rb_launch_largest_gather(const rb_hit_row *rows, const uint32_t *out_ops, const uint64_t *sel, uint64_t n_sel, rb_hit_row *sel_rows,
+                                               uint32_t *sel_desc, hipStream_t stream);
+
 // ---- k_nucfreq.hip: nucfreq ----
 struct rb_nf_params {
     uint64_t n_reads;
