@@ -858,9 +858,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RB_GW_WPE))
             continue;
         }
         const uint64_t N = rec_units; // all units of the (normalised) record
-#if defined(RB_GW_STOP) && RB_GW_STOP == 1 // (diagnostics, timing only: the hit ends behind pass 1)
-        if (s_lo != 0x12345ull) { if (lane == 0) row->status = (uint16_t)(s_lo & 1u); continue; }
-#endif
         s_lo = rb_wave_min_u64(s_lo), s_hi = rb_wave_max_u64(s_hi), e_lo = rb_wave_min_u64(e_lo), e_hi = rb_wave_max_u64(e_hi);
         if (s_lo == ~0ull || e_lo == ~0ull) { // binary_search Err -> panic (liftover.rs:31, :42)
             w.status = RB_ST_PANIC_NOTFOUND;
@@ -938,9 +935,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RB_GW_WPE))
             if (lane == 0) *row = w;
             continue;
         }
-#if defined(RB_GW_STOP) && RB_GW_STOP == 2 // (diagnostics, timing only: the hit ends behind pass 2)
-        if (a != 0x12345ull) { if (lane == 0) row->status = (uint16_t)((a + b + Ra + Qa + Ma + nRb + nQb + nMb + ia + ib) & 1u); continue; }
-#endif
         w.t_st = t_st + Ra; // liftover.rs:57-60, :77-82 (a and b are match-type units)
         w.t_en = t_st + nRb;
         if (!minus) w.q_st = q_st + Qa, w.q_en = q_st + nQb;

@@ -13,29 +13,26 @@
 //   rb_k_nf_plan_tiles  thread per tile of NF_TILE positions: its region, and the range of reads that can overlap it
 //   rb_k_nf_crowded / _deep_regions / _admit   htslib's cap of 8000 buffered reads, replayed per region only where it can be reached:
 //                       a bitmap of the reads each such region's fetch drops (see the comment at rb_k_nf_admit)
-//   rb_k_nf_tiles       workgroup per tile: the tile's counters live in LDS (4 x u16 in one u64 per position, or 4 bytes in one dword
-//                       where at most 255 reads are in range: then one ds_add_u64 covers two positions; + a coverage
-//                       difference array).  Each wave takes every NF_WAVES-th read of the tile's range: the reads' records sit one
-//                       per lane, and the reads go by as a stream of chunks of 64 ops, three under way (round 6: the bases of one
-//                       parked in LDS while the next is scanned -- wave scans give every op its reference / query start, all lanes
+//   rb_k_nf_tiles       workgroup per tile, in three builds by the number of reads in range (see "Three builds" below): the tile's
+//                       counters live in LDS (4 bytes in one dword per position where at most 255 reads are in range, else 4 x u16 in
+//                       one u64; + the coverage differences).  Each wave takes every NF_WAVES-th read of the tile's range: the reads'
+//                       records sit one per lane, and the reads go by as a stream of chunks of 64 ops, three under way (the bases of
+//                       one parked in LDS while the next is scanned -- wave scans give every op its reference / query start, all lanes
 //                       at once their op's share of the tile -- and the one after has its ops requested).  For every match-type op
 //                       that overlaps the tile each lane takes 8 consecutive positions: two dwords of the staged bases give a lane
 //                       its 8 base codes, a 256-entry table turns two codes into what they add, one ds_add_u64 per two bases (no
-//                       branch on the base: N and the IUPAC codes add 0).  At the end a block scan of the difference array gives
-//                       the depth (coverage + the htslib depth-cap check), and the tile is written out with 16-byte stores.
+//                       branch on the base: N and the IUPAC codes add 0).  A tile crowded with short reads (more than 512 in range)
+//                       gives a lane a read instead.  At the end a block scan of the difference array gives the depth (coverage +
+//                       the htslib depth-cap check), and the tile is written out with 16-byte stores.
 // HBM traffic: each read's packed bases once per tile it overlaps (4 bits / base), its CIGAR likewise, 16 B written per
 // position.  Bound: HBM (the counters never leave LDS).
 #include "rb_device.h"
 #include "rb_launch.h"
 #include <algorithm>
 
-#ifndef NF_TILE
-#define NF_TILE 4096
-#endif
+#define NF_TILE 4096 // positions per tile; with NF_THREADS it gives the 8 positions per thread that the counters' groups of 8 are built on
 #define NF_STAGE_DW (NF_TILE / 8 + 256) // dwords of packed bases staged per read and tile: the tile itself + 2048 inserted bases
-#ifndef NF_THREADS
 #define NF_THREADS 512
-#endif
 #define NF_PER_THREAD (NF_TILE / NF_THREADS) // positions per thread in the depth scan
 #define NF_WAVES (NF_THREADS / 64)
 #define NF_LANE_OPS 4u // reads with at most this many ops are walked by one lane each where a tile is crowded
@@ -51,6 +48,11 @@ struct __attribute__((aligned(16))) nf_read {
     uint64_t nib0; // index of the read's first base counted in 4-bit units from seq
     uint64_t pad1;
 };
+__device__ __forceinline__ nf_read nf_no_read() { // the record of no read: end = 0 takes no part, no ops
+    nf_read h;
+    h.pos = 0, h.end = 0, h.tid = -1, h.l_seq = 0, h.op_off = 0, h.n_ops = 0, h.pad0 = 0, h.nib0 = 0, h.pad1 = 0;
+    return h;
+}
 
 __device__ __forceinline__ uint64_t nf_key(int32_t tid, uint64_t pos32) { return ((uint64_t)(uint32_t)tid << 32) | (pos32 & 0xFFFFFFFFull); }
 
@@ -412,16 +414,18 @@ __device__ __forceinline__ uint32_t nf_swap_nibbles(uint32_t v) { // (two shifts
     return o;
 }
 
-// Three builds of the tile kernel (nf_tile_kind):
+// Three builds of the tile kernel (nf_tile_kind), told apart by two template flags and nothing else:
 //   <U8T, D8>   tiles with at most 127 reads in range -- the usual ones with long reads: byte counters, the coverage differences as signed
-//               bytes in the counters' own padding, staging buffers of 548 dwords: 40 KB of LDS, FOUR workgroups per CU (round 6); a
-//               workgroup per tile, launched over all tiles
+//               bytes in the counters' own padding, staging buffers of 548 dwords: 40 KB of LDS, four workgroups per CU; a workgroup
+//               per tile, launched over all tiles
 //   <U8T, !D8>  128 .. 255 reads in range: byte counters, the differences as 16-bit halves of a dword, staging buffers of 648 dwords: 51 KB,
-//               three per CU (round 2's byte build: 4.43 -> 3.6 ms on config 5 against the 16-bit layout)
+//               three per CU (byte counters against the 16-bit layout: 4.43 -> 3.6 ms on config 5)
 //   <!U8T>      more reads than that: 16-bit counters, 32-bit differences: 77 KB, two per CU; beyond 512 reads a lane per read
 // The last two walk lists of their tiles (rb_k_nf_tile_desc writes them); each build leaves the others' tiles alone.
 #define NF_CNT8_DW (10 * ((NF_TILE + 16) / 8))
-// -DNF_DIAG (a diagnostics variant, tools/nf_phases.py): every 64th tile's waves add the shader-clock length of their phases to p.blk[8 ..]
+#define NF_U8_WPE 8 // waves per SIMD the byte-counter build is compiled for: four workgroups of eight waves a CU
+#define NF_U8_SLACK_DW 28 // byte-counter tiles: dwords of staging beyond the tile's own 512 (224 inserted bases + alignment; more: the unstaged route)
+// -DNF_DIAG (the one diagnostics build, right results; tools/bench_nucfreq.py --phases reads it): every 64th tile's waves add the shader-clock length of their phases to p.blk[8 ..]
 #ifdef NF_DIAG
 #define NF_STAMP(k) const uint64_t nf_t##k = __builtin_amdgcn_s_memtime()
 #define NF_DECL(k) uint64_t nf_t##k = 0
@@ -432,18 +436,6 @@ __device__ __forceinline__ uint32_t nf_swap_nibbles(uint32_t v) { // (two shifts
 #define NF_DECL(k) do { } while (0)
 #define NF_SET(k) do { } while (0)
 #define NF_PHASE(slot, a, b) do { } while (0)
-#endif
-#ifndef NF_U8_WPE
-#define NF_U8_WPE 8 // waves per SIMD the byte-counter build is compiled for: four workgroups of eight waves a CU
-#endif
-#ifndef NF_U8_SLACK_DW
-#define NF_U8_SLACK_DW 28 // byte-counter tiles: dwords of staging beyond the tile's own 512 (224 inserted bases + alignment; more: the unstaged route)
-#endif
-#ifndef NF_PIPE
-#define NF_PIPE 1 // 0: the wave's reads strictly one after the other (rounds 1 - 5)
-#endif
-#ifndef NF_STOP
-#define NF_STOP 0 // diagnostics (timing only, wrong counts): 1 = no output written, 2 = no LDS atomics (bases staged and decoded, nothing added), 3 = no read touched, 5 = chunks scanned and landed but not counted (9: no bases fetched either, 10: fetched and dropped), 6 = every op's set-up but none of its groups, 7 = only the launch, 8 = no read touched and no depth scan
 #endif
 // (at most) 64 ops of one read against a tile, between their scan and the counting (nf_one_tile: chunk_scan / chunk_land / chunk_count)
 template <int IT>
@@ -458,6 +450,12 @@ struct nf_chunk { // (no implicit padding: the compiler copies a struct's paddin
     uint32_t pad[2];
     uint4 v[IT];
 };
+template <int IT>
+__device__ __forceinline__ nf_chunk<IT> nf_no_chunk() { // no op lays anything over the tile, nothing staged (v is not looked at)
+    nf_chunk<IT> k;
+    k.m = 0, k.wd_lo = 0, k.ia = 0, k.ib = 0, k.qa = 0, k.staged = 0, k.n_dw = 0, k.s = 0, k.pad[0] = k.pad[1] = 0;
+    return k;
+}
 template <bool U8T, bool D8>
 __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_t t) {
     // the thread's index through an opaque copy: what is derived from it (a dozen lane-times-constant addresses) is then computed per
@@ -473,14 +471,13 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
     constexpr uint32_t CNT_DW = ((U8T ? NF_CNT8_DW : NF_CNT_DW) + 3) / 4 * 4; // (zeroed 16 bytes at a time)
     __shared__ __attribute__((aligned(16))) uint32_t cnt[CNT_DW]; // per position: one dword of four byte counters / A | C << 16, G | T << 16
     __shared__ uint32_t lut[16];        // what a base code adds to its word: 1 4 = A G: 1; 2 8 = C T: 1 << 16; everything else 0 (nucfreq.rs:83-90)
+    // (lut8 is stored to and never read since lut16 took over in round 3; it stays because without it every LDS offset moves: to be timed on its own)
     __shared__ uint32_t lut8[16];       // U8 tiles: 1 2 4 8 = A C G T: 1 << 0, 8, 16, 24
-#ifndef NF_LUT_SINGLE
     __shared__ unsigned long long lut16[U8T ? 256 : 1]; // two bases at once: low nibble -> low dword, high nibble -> high dword
     if (U8T && tix < 256) {
         auto one = [](uint32_t n) -> unsigned long long { return n == 1 ? 1ull : n == 2 ? 0x100ull : n == 4 ? 0x10000ull : n == 8 ? 0x1000000ull : 0ull; };
         lut16[tix] = one(tix & 15u) | (one(tix >> 4) << 32);
     }
-#endif
     // +1 where a read starts covering, -1 where it stops; then the depth.  U8T (round 6): a signed BYTE per position, and the bytes live
     // in the counters' own padding -- a group of 8 positions is 10 dwords, 8 of counters and 2 that only keep the lanes of an atomic on
     // different banks: 8 bytes, one per position.  They are added as whole 32-bit integers (a borrow of a byte travels into the next one
@@ -513,24 +510,18 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
     if (tix == 0) blk_max = 0, blk_cov = 0;
     const nf_tdesc D = nf_uniform(Draw);
     if (D.u8 != (D8 ? 1u : U8T ? 2u : 0u)) return; // another build's, or nobody's
-#if NF_STOP == 7
-    if (D.n_pos != 0x7FFFFFFFu) return; // (timing only: what it costs to launch the tiles' workgroups)
-#endif
     nf_tile T;
     T.r = D.r, T.st = D.st, T.en = D.st + D.n_pos, T.out = D.out, T.tid = D.tid;
     nf_drop drop;
     drop.off = D.drop_off, drop.rlo = D.drop_rlo, drop.bits = p.drop_bits;
     const uint32_t n_pos = D.n_pos;
-#if NF_PIPE
     // the wave's reads (lo + wave + NF_WAVES j): lane j asks for read j's record now, before the tile is zeroed -- the first of the
     // dependent trips (tile -> records -> ops -> bases) runs under the zeroing and the barrier.  (Not for the crowded tiles: lane-per-read.)
     const bool nf_by_wave = U8T || D.hi - D.lo <= 8u * 64u;
     const uint32_t nw = nf_by_wave && D.hi > D.lo + (tix >> 6) ? (uint32_t)((D.hi - D.lo - (tix >> 6) + NF_WAVES - 1) / NF_WAVES) : 0u;
-    nf_read hv;
-    hv.pos = 0, hv.end = 0, hv.tid = -1, hv.l_seq = 0, hv.op_off = 0, hv.n_ops = 0, hv.pad0 = 0, hv.nib0 = 0, hv.pad1 = 0;
+    nf_read hv = nf_no_read();
     const uint64_t hv_i = D.lo + (tix >> 6) + (uint64_t)NF_WAVES * (tix & 63u);
     if ((tix & 63u) < nw) hv = p.hd[hv_i];
-#endif
     auto diff_add = [&](uint32_t i, int32_t delta) {
         if constexpr (D8) { // position i = byte (i + 8) & 7 of the two spare dwords of its group (i + 8) >> 3
             const uint32_t q = i + 8u;
@@ -540,6 +531,11 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
         } else {
             atomicAdd(&diff[i], delta);
         }
+    };
+    auto cover = [&](const nf_read &h) { // a read's stretch of the tile into the coverage differences (by the one lane that holds the read)
+        const uint64_t c0 = (uint64_t)h.pos > T.st ? (uint64_t)h.pos : T.st, c1 = (uint64_t)h.end < T.en ? (uint64_t)h.end : T.en;
+        diff_add((uint32_t)(c0 - T.st), 1);
+        diff_add((uint32_t)(c1 - T.st), -1);
     };
     // (the barrier that makes the zeroing everybody's sits in front of the first LDS atomic: behind the first requests of the wave's reads)
     const uint32_t wib = rb_first(tix >> 6);
@@ -556,7 +552,7 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
     //      chunk_land  the stretch arrives and is parked in the wave's LDS buffer in base order
     //      chunk_count every match-type op of the chunk: each lane takes 8 consecutive positions, table reads, LDS atomics
     auto chunk_scan = [&](const nf_read &h, const uint32_t w, uint32_t &R, uint32_t &Q, const uint64_t i) -> nf_chunk<STG_IT> {
-        nf_chunk<STG_IT> k;
+        nf_chunk<STG_IT> k = nf_no_chunk<STG_IT>();
         const int64_t pos = h.pos;
         const int64_t rel_st = (int64_t)T.st - pos, rel_en = (int64_t)T.en - pos; // the tile in read-relative reference offsets
         const uint32_t c = rb_opc(w), len = rb_len(w);
@@ -566,7 +562,6 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
         const uint32_t Q0 = Q;
         R += rb_readlane<uint32_t>(ir, 63);
         Q += rb_readlane<uint32_t>(iq, 63);
-        k.m = 0, k.wd_lo = 0, k.n_dw = 0, k.staged = 0, k.ia = 0, k.ib = 0, k.qa = 0, k.s = 0, k.pad[0] = k.pad[1] = 0;
         // A read of the tile's fetch has pos < T.en and pos + span > T.st with span < 2^31 (rb_k_nf_read_spans), so rel_st lies in
         // (-NF_TILE, 2^31), every op starts and ends below 2^31, and 32 bits hold all of it (rel_en only matters below a span; the wave-
         // uniform tests are 32-bit on purpose: a 64-bit ordered compare has no scalar instruction and lands on the vector ALU).  Behind
@@ -610,9 +605,6 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
             const uint64_t n_dw = ((nib0 + q_hi + 7u) >> 3) + 2u - (uint64_t)k.wd_lo; // (+ the second dword of the last group)
             const bool fits = (uint32_t)(n_dw >> 32) == 0u && (uint32_t)n_dw <= STG;
             k.staged = fits && q_hi > q_lo ? 1u : 0u;
-#if NF_STOP == 9
-            k.staged = 0u; // (timing only: no bases fetched)
-#endif
             k.n_dw = fits ? (int32_t)(uint32_t)n_dw : (int32_t)STG + 1;
             if (k.staged) {
 #pragma unroll
@@ -627,9 +619,6 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
     };
     auto chunk_land = [&](const nf_chunk<STG_IT> &k) {
         if (!k.staged) return;
-#if NF_STOP == 10
-        if (k.v[0].x != 0x12345678u || k.v[STG_IT - 1].w != 0x9ABCDEF0u) return; // (timing only: the bases fetched and dropped)
-#endif
 #pragma unroll
         for (int r = 0; r < STG_IT; r++)
             if (4 * lane + 256 * r < k.n_dw) // (kept in base order: BAM packs the first base of a byte into its high half)
@@ -641,33 +630,20 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
     auto chunk_count = [&](auto U8, const nf_read &h, const nf_chunk<STG_IT> &k) {
         const bool staged = k.staged != 0u;
         uint64_t m = k.m;
-#if NF_STOP == 5 || NF_STOP == 9 || NF_STOP == 10
-        if (m != 0x123456789ull) return; // (timing only: chunks scanned and landed, nothing counted)
-#endif
         // lane l takes the 8 positions [P, P + 8) of an 8-aligned group (P = tile index + 8 = P0 + 8 l, then 512 on per turn); their
         // bases are 8 consecutive 4-bit codes of the read: two dwords (nibbles already in base order), funnel-shifted to the group's
         // first base; x = the 8 codes with the bases outside [ia, ib) made code 0 (they add nothing)
         auto add_group = [&](const uint32_t x, uint32_t *const g32) {
-#if NF_STOP == 2
-            if (x == 0x12345678u) cnt[x & 1023u] = x; // (keeps x alive)
-            return;
-#endif
-            uint32_t inc[8]; // (the table reads first, all eight in flight, then the atomics)
-            if constexpr (decltype(U8)::value) {
+            if constexpr (decltype(U8)::value) { // (the table reads first, all in flight, then the atomics)
+                // (round 3: one 8-byte table read per TWO bases -- 256 entries, 2 KB -- instead of two 4-byte reads: 3.74 -> 3.57 ms per call, same box)
                 unsigned long long *g = reinterpret_cast<unsigned long long *>(g32);
-#ifndef NF_LUT_SINGLE // (round 3: one 8-byte table read per TWO bases -- 256 entries, 2 KB -- instead of two 4-byte reads: 3.74 -> 3.57 ms per call, same box)
                 unsigned long long inc2[4];
 #pragma unroll
                 for (int q = 0; q < 4; q++) inc2[q] = lut16[(x >> (8 * q)) & 255u];
 #pragma unroll
                 for (int q = 0; q < 4; q++) atomicAdd(g + q, inc2[q]);
-#else
-#pragma unroll
-                for (int q = 0; q < 8; q++) inc[q] = lut8[(x >> (4 * q)) & 15u];
-#pragma unroll
-                for (int q = 0; q < 4; q++) atomicAdd(g + q, (unsigned long long)inc[2 * q] | ((unsigned long long)inc[2 * q + 1] << 32));
-#endif
             } else {
+                uint32_t inc[8];
 #pragma unroll
                 for (int q = 0; q < 8; q++) inc[q] = lut[(x >> (4 * q)) & 15u];
 #pragma unroll
@@ -681,12 +657,6 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
             const int32_t ia = rb_readlane<int32_t>(k.ia, j), ib = rb_readlane<int32_t>(k.ib, j); // tile indices [ia, ib) of this op's bases
             const uint32_t qa = rb_readlane<uint32_t>(k.qa, j);                                   // bam_pileup1_t::qpos of the base at ia
             const int32_t sP0 = (ia + 8) & ~7;
-#if NF_STOP == 6
-            if (ia != 0x7FFFFFF0) { // (timing only: an op's set-up, none of its groups)
-                if (sP0 == 0x7FFFFFF1 + (int32_t)(qa & 1u) + ib) cnt[0] = 1u;
-                continue;
-            }
-#endif
             // what moves from turn to turn is kept as running values (no multiply, no shift inside the loop): lo4 / hi4 = four times the
             // number of positions the group starts before ia / ends behind ib (the masks' shift counts); the lane is in while hi4 < 32
             int32_t lo4 = 4 * (ia + 8 - sP0) - 32 * lane, hi4 = 4 * (sP0 - ib) + 32 * lane;
@@ -714,21 +684,11 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
         if (h.tid != T.tid || (uint64_t)h.pos >= T.en || (uint64_t)h.end <= T.st) return false;
         return !nf_dropped(drop, i);
     };
-    auto cover = [&](const nf_read &h) { // the read's stretch of the tile in the difference array
-        const uint64_t c0 = (uint64_t)h.pos > T.st ? (uint64_t)h.pos : T.st, c1 = (uint64_t)h.end < T.en ? (uint64_t)h.end : T.en;
-        if (lane == 0) {
-            diff_add((uint32_t)(c0 - T.st), 1);
-            diff_add((uint32_t)(c1 - T.st), -1);
-        }
-    };
-    // one read from start to end, the whole wave on it, chunk after chunk (w_first: its first 64 ops, already in registers): reads
-    // of more than 64 ops, and the reads the crowded tiles leave to the wave
+    // one read from start to end, the whole wave on it, chunk after chunk (w_first: its first 64 ops, already in registers): the reads
+    // the crowded tiles leave to the wave
     auto read_by_wave = [&](auto U8, const nf_read &h, uint32_t w_first, uint64_t i) {
-#if NF_STOP == 3
-        return;
-#endif
         if (!in_tile(h, i)) return;
-        cover(h);
+        if (lane == 0) cover(h);
         const uint64_t o0 = h.op_off, o1 = h.op_off + h.n_ops;
         const int64_t rel_en = (int64_t)T.en - (int64_t)h.pos;
         uint32_t R = 0, Q = 0;
@@ -748,14 +708,14 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
         //      reads with longer cigars one after the other with the whole wave ----
         for (uint64_t g = lo + 64u * wib; g < hi; g += 64u * NF_WAVES) {
             const uint64_t i = g + (uint64_t)lane;
-            nf_read h;
-            h.end = 0, h.n_ops = 0, h.op_off = 0, h.pos = 0, h.tid = -1, h.l_seq = 0, h.nib0 = 0;
+            nf_read h = nf_no_read();
             if (i < hi) h = p.hd[i];
             const bool overl = h.tid == T.tid && (uint64_t)h.pos < T.en && (uint64_t)h.end > T.st && !nf_dropped(drop, i);
             const bool simple = overl && h.n_ops <= NF_LANE_OPS;
             uint64_t cm = __ballot(overl && !simple);
             if (simple) {
                 const int64_t pos = h.pos;
+                // (cover(h) written out: called here, it changes the crowded build's device code -- held back)
                 const uint64_t c0 = (uint64_t)pos > T.st ? (uint64_t)pos : T.st, c1 = (uint64_t)h.end < T.en ? (uint64_t)h.end : T.en;
                 diff_add((uint32_t)(c0 - T.st), 1);
                 diff_add((uint32_t)(c1 - T.st), -1);
@@ -799,19 +759,15 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
             }
         }
     } else {
-#if NF_PIPE
         // ---- the wave's reads as a stream of CHUNKS (a read's ops, 64 at a time), three chunks under way at any time (round 6).
         //      The wave's reads are lo + wib + NF_WAVES j, j < nw <= 64: lane j fetched read j's record before the tile was zeroed
         //      (hv), so a record is a row of v_readlane away; the lanes have each entered their own read into the coverage
         //      differences, and `alive` says which reads the tile's fetch holds.  In a turn: the bases of chunk c (requested a turn
         //      ago) are parked in LDS; chunk c + 1 (ops requested a turn ago) is scanned and ITS bases requested; the ops of chunk
         //      c + 2 are requested; then chunk c is counted out of LDS.  Every trip to memory has a chunk's worth of work in front
-        //      of it -- before, a read's bases were waited for where they were requested: five reads a wave and tile, two
-        //      microseconds each. ----
-        bool mine = (uint32_t)lane < nw && in_tile(hv, hv_i);
-#if NF_STOP == 3 || NF_STOP == 8
-        mine = false;
-#endif
+        //      of it -- before (rounds 1 - 5: the wave's reads strictly one after the other, 3.45 - 3.48 -> 3.28 - 3.30 ms per call), a
+        //      read's bases were waited for where they were requested: five reads a wave and tile, two microseconds each. ----
+        const bool mine = (uint32_t)lane < nw && in_tile(hv, hv_i);
         const uint64_t alive = __ballot(mine);
         struct cursor { // a chunk to come: which read, where in its ops, the reference / read bases in front of it
             nf_read h;
@@ -843,21 +799,12 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
         auto ops_at = [&](const cursor &c) -> uint32_t {
             return c.o + (uint32_t)lane < c.h.n_ops ? p.ops[c.h.op_off + c.o + (uint32_t)lane] : RB_NULL_OP;
         };
-        auto empty = []() -> nf_chunk<STG_IT> {
-            nf_chunk<STG_IT> k;
-            k.m = 0, k.wd_lo = 0, k.ia = 0, k.ib = 0, k.qa = 0, k.staged = 0, k.n_dw = 0, k.s = 0, k.pad[0] = k.pad[1] = 0;
-            return k;
-        };
         cursor c_cur = read_at(~0ull);
         const uint32_t w_cur = ops_at(c_cur); // (the first read's ops: on their way while the workgroup meets at the barrier)
         __syncthreads();                      // (the zeroing is everybody's: LDS atomics from here on)
         NF_SET(1);
-        if (mine) { // (every lane its own read into the coverage differences: the two atomics of up to 64 reads in one go)
-            const uint64_t c0 = (uint64_t)hv.pos > T.st ? (uint64_t)hv.pos : T.st, c1 = (uint64_t)hv.end < T.en ? (uint64_t)hv.end : T.en;
-            diff_add((uint32_t)(c0 - T.st), 1);
-            diff_add((uint32_t)(c1 - T.st), -1);
-        }
-        nf_chunk<STG_IT> k_cur = empty();
+        if (mine) cover(hv); // (every lane its own read: the two atomics of up to 64 reads in one go)
+        nf_chunk<STG_IT> k_cur = nf_no_chunk<STG_IT>();
         if (c_cur.valid) k_cur = chunk_scan(c_cur.h, w_cur, c_cur.R, c_cur.Q, c_cur.i);
         cursor c_nxt = after(c_cur);
         uint32_t w_nxt = ops_at(c_nxt);
@@ -875,30 +822,6 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
         }
         NF_STAMP(3);
         NF_PHASE(2, 2, 3);
-#else
-        __syncthreads(); // (the zeroing)
-        NF_SET(1);
-        // ---- the wave's reads, one after the other.  Two loads run ahead of the work: the record of the read after next, and the
-        //      first 64 ops of the next read (whose record arrived one turn earlier) -- a read then starts with its ops in registers
-        //      instead of waiting for three dependent trips to memory ----
-        nf_read h_cur, h_nxt;
-        h_cur.end = 0, h_nxt.end = 0, h_cur.n_ops = 0, h_nxt.n_ops = 0, h_cur.op_off = 0, h_nxt.op_off = 0;
-        uint32_t w_cur = RB_NULL_OP;
-        if (lo + wib < hi) h_cur = p.hd[lo + wib];
-        if (lo + wib + NF_WAVES < hi) h_nxt = p.hd[lo + wib + NF_WAVES];
-        if ((uint32_t)lane < h_cur.n_ops) w_cur = p.ops[h_cur.op_off + (uint32_t)lane];
-        for (uint64_t i = lo + wib; i < hi; i += NF_WAVES) {
-            nf_read h_nn;
-            h_nn.end = 0, h_nn.n_ops = 0, h_nn.op_off = 0;
-            if (i + 2 * NF_WAVES < hi) h_nn = p.hd[i + 2 * NF_WAVES];
-            uint32_t w_nxt = RB_NULL_OP;
-            if ((uint32_t)lane < h_nxt.n_ops) w_nxt = p.ops[h_nxt.op_off + (uint32_t)lane];
-            const nf_read h = h_cur;
-            const uint32_t w_first = w_cur;
-            h_cur = h_nxt, h_nxt = h_nn, w_cur = w_nxt;
-            read_by_wave(std::integral_constant<bool, U8T>{}, h, w_first, i);
-        }
-#endif
     }
     NF_STAMP(3b);
     __syncthreads();
@@ -906,7 +829,6 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
     NF_PHASE(0, 0, 1);
     NF_PHASE(3, 3b, 4);
     // depth = prefix sum of the difference array: NF_PER_THREAD positions per thread
-#if NF_STOP != 8
     {
         const uint32_t b0 = tix * NF_PER_THREAD;
         int32_t d[NF_PER_THREAD], s = 0;
@@ -966,19 +888,13 @@ __device__ __forceinline__ void nf_one_tile(const rb_nf_params &p, const uint64_
         }
     }
     __syncthreads();
-#endif
     NF_STAMP(5);
     NF_PHASE(4, 4, 5);
-#if NF_STOP != 4 && !defined(NF_NO_CTR)
     if (tix == 0) {
         atomicMax((unsigned long long *)&p.counters->max_depth, (unsigned long long)blk_max);
         atomicAdd((unsigned long long *)&p.counters->n_covered, (unsigned long long)blk_cov);
     }
-#endif
     uint4 *__restrict__ out = reinterpret_cast<uint4 *>(p.counts + 4ull * T.out);
-#if NF_STOP == 1
-    if (blk_max != 0x7FFFFFFFu) return;
-#endif
     if constexpr (U8T) {
         static_assert(NF_PER_THREAD <= 8, "one byte of coverage flags per thread");
         for (uint32_t k = tix; k < n_pos; k += NF_THREADS) {

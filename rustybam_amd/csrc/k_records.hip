@@ -306,9 +306,8 @@ __global__ __launch_bounds__(256) void rb_k_scan_records(rb_scan_params p) {
     // instead of a 64-bit sum through twelve ds_bpermute; the op counts of I and D alone (the events of bamstats.rs:112-117: nothing asks
     // for the others); H and P, which only the unit total sees, as one sum; the flags by ballot.  18 wave sums where there were 9 through
     // the LDS crossbar and 9 by DPP: 14.4 -> 10.0 ms per 1e7 records of 500 ops with the first of these changes alone
-    // (tools/r05_scan_ab.sh, same box, rows equal); -DRB_SCAN_SHFL_SUMS is the old form.
+    // (tools/history/r05/r05_scan_ab.sh, same box, rows equal).
     uint64_t L[9];
-#ifndef RB_SCAN_SHFL_SUMS
     auto sum40 = [&](unsigned long long v) -> uint64_t {
         const uint32_t s_lo = rb_wave_sum_u32((uint32_t)v & 0xFFFFFu), s_hi = rb_wave_sum_u32((uint32_t)(v >> 20) & 0xFFFFFu);
         return (uint64_t)s_lo + ((uint64_t)s_hi << 20);
@@ -326,18 +325,6 @@ __global__ __launch_bounds__(256) void rb_k_scan_records(rb_scan_params p) {
     const uint32_t ins_events = rb_wave_sum_u32((uint32_t)(hist[RB_OP_I][lane] >> RB_LEN_BITS));
     const uint32_t del_events = rb_wave_sum_u32((uint32_t)(hist[RB_OP_D][lane] >> RB_LEN_BITS));
     bad = (__ballot(bad & 1u) ? 1u : 0u) | (__ballot(bad & 2u) ? 2u : 0u) | (__ballot(bad & 4u) ? 4u : 0u) | (__ballot(bad & 8u) ? 8u : 0u);
-#else
-    uint32_t C[9];
-#pragma unroll
-    for (int t = 0; t < 9; t++) {
-        const unsigned long long v = hist[t][lane];
-        L[t] = rb_wave_sum_u64(v & ((1ull << RB_LEN_BITS) - 1ull));
-        C[t] = rb_wave_sum_u32((uint32_t)(v >> RB_LEN_BITS));
-    }
-    const uint32_t ins_events = C[RB_OP_I];
-    const uint32_t del_events = C[RB_OP_D];
-    bad = rb_wave_or_u32(bad);
-#endif
     if (lane != 0) continue;
 
     rb_scan_finish(p, r, L, ins_events, del_events, bad, o0, o1, p.t_st[r], p.t_en[r], p.q_st[r], p.q_en[r], p.strand && p.strand[r] == (uint8_t)'-');
@@ -354,13 +341,8 @@ __global__ __launch_bounds__(256) void rb_k_scan_records(rb_scan_params p) {
 // fewer than 4, are listed for the kernel above (its list mode).  Same sums, same flags, same rows: rb_scan_finish is shared.
 // ------------------------------------------------------------------------------------------------------------------------------------
 #define RB_SQ_MAX 2048u
-#ifndef RB_SQ_DIAG
-#define RB_SQ_DIAG 0
-#endif
-#ifndef RB_SQ_BATCH
 #define RB_SQ_BATCH 4 // steps of a row whose loads are in flight together (same box, 1e7 records of 300 - 700 ops: 1 -> 4.96 ms, 2 -> 4.47, 3 - 5 -> 4.25 - 4.34,
                       // 8 -> 4.7 - 4.9, 12 -> 4.95, 16 -> 5.6: registers, i.e. wavefronts per SIMD, are worth more than loads per wavefront)
-#endif
 __global__ __launch_bounds__(256) void rb_k_scan_rows(rb_scan_params p, unsigned long long *n_long, uint32_t *long_list) {
     __shared__ unsigned long long hist_all[4][9][64];
     const int lane = rb_lane();
@@ -422,12 +404,8 @@ __global__ __launch_bounds__(256) void rb_k_scan_rows(rb_scan_params p, unsigned
                         const uint32_t w = raw[q], opc = w & 15u, len = w >> 4;
                         if (ok) {
                             if (opc <= 8u) {
-#if RB_SQ_DIAG == 1 // (diagnostics, timing only: no LDS add -- what the counters cost)
-                                v_big += len;
-#else
                                 __hip_atomic_fetch_add(&hist[opc][lane], (unsigned long long)len | (1ull << RB_LEN_BITS), __ATOMIC_RELAXED,
                                                        __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
                             } else {
                                 v_big |= 8u;
                                 // a continuation word: bits 28.. of the length of the op in front of it (no event of its own)

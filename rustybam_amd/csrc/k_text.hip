@@ -21,10 +21,6 @@
 #include "rb_device.h"
 #include "rb_launch.h"
 
-#ifndef RB_PARSE_STOP
-#define RB_PARSE_STOP 0 // diagnostics (timing only): 1 = the fill pass of the parser stops behind the values of a step, 2 = behind the ops in LDS
-#endif
-
 // op character -> code (MIDNSHP=X -> 0..8), 255 = not an op.  Branch-free: the nine characters lie in '=' (61) .. 'X' (88),
 // so the code is a nibble of a packed table indexed by c - 61 (15 = not an op).
 __device__ __forceinline__ uint32_t rb_op_code_of(uint32_t c) {
@@ -158,17 +154,6 @@ __global__ __launch_bounds__(256) void rb_k_parse_cigars(rb_parse_params p) {
 #pragma unroll
             for (int j = 0; j < 8; j++) mx = mx > slen[j] ? mx : slen[j];
             if (mx >= (1u << 28)) err |= 2u; // not representable in the packed form
-#if RB_PARSE_STOP == 1
-            { // (diagnostics: the step ends behind the values; a dependency on every one of them keeps them computed)
-                uint32_t chk = fixed_first;
-#pragma unroll
-                for (int j = 0; j < 8; j++) chk ^= slen[j];
-                if (chk == 0x9E3779B9u) err |= 8u;
-                const uint32_t tot_ = rb_wave_sum_u32(cnt);
-                out_base += tot_, total += tot_;
-                continue;
-            }
-#endif
             // the ops of this step go through LDS: every lane drops its (at most 8) ops at their rank -- absent slots go to a scrap
             // word -- and the wave then writes the step's ops out side by side
             const uint32_t incl0 = rb_wave_scan_incl(cnt);
@@ -191,12 +176,8 @@ __global__ __launch_bounds__(256) void rb_k_parse_cigars(rb_parse_params p) {
             const uint32_t step_total_f = rb_readlane<uint32_t>(incl0, 63);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-#if RB_PARSE_STOP != 2
             for (uint32_t k = (uint32_t)lane; k < step_total_f; k += 64u)
                 if (out_base + k < p.ops_cap) p.ops[out_base + k] = stg[k];
-#else
-            if (step_total_f == 0x7FFFFFFFu) p.ops[out_base] = stg[lane]; // (diagnostics: nothing leaves LDS)
-#endif
             __builtin_amdgcn_wave_barrier();
             out_base += step_total_f;
             total += step_total_f;
@@ -219,13 +200,6 @@ __device__ __forceinline__ uint32_t rb_ndigits(uint32_t v) {
     return 1u + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u) + (v >= 100000000u);
 }
 
-#ifndef RB_FMT_WORDS
-#define RB_FMT_WORDS 0 // 1: an op's text as one 8-byte LDS store instead of a byte store per digit -- bit-exact (133 tests), and 2 % SLOWER
-                       // (1.85 against 1.81 ms, profiles/r04_text_summary.md): kept as a switch, not the product
-#endif
-#ifndef RB_FMT_STOP
-#define RB_FMT_STOP 0 // diagnostics (timing only, wrong text): 1 = the fill pass stops behind the byte counts of a step, 2 = behind the digits in LDS
-#endif
 #define RB_FMT_STAGE (256 * 10 + 48) // bytes of text one step of 256 words can make (9 digits + the op character each; an op with a continuation word: 11 bytes for its two words) + the 16-byte phase + 16 bytes of slack in front
 // the four low decimal digits of x < 10000, least significant first, as one byte each of a dword: multiplications by constants that
 // fit 24 bits (v_mul_u32_u24: full rate; the per-digit x / 10 of round 2 was a v_mul_hi_u32 -- quarter rate -- per digit)
@@ -314,42 +288,11 @@ __global__ __launch_bounds__(256) void rb_k_format_cigars(rb_format_params p) {
         mine = nb[0] + nb[1] + nb[2] + nb[3];
         const uint32_t incl = rb_wave_scan_incl(mine);
         const uint32_t step_bytes = rb_readlane<uint32_t>(incl, 63);
-        if (FILL && RB_FMT_STOP != 1) {
+        if (FILL) {
             const uint32_t phase = (uint32_t)(out & 15u);
             uint32_t o = phase + (incl - mine); // place in the stage buffer: byte k of the buffer is byte (out - phase + k) of the text
-            // Round 4: where no op of the step has more than four digits (nearly every step), an op's text leaves for LDS as ONE
-            // 8-byte store that ENDS at the op's last byte: its digits and character in the top bytes, the text in front of it -- the
-            // lane's earlier ops, or the tail of the lane before -- in the bytes below.  Every byte a store carries is the byte that
-            // belongs there, so stores may overlap in any order.  (Rounds 2 - 3: one predicated byte store per digit.)
-            const bool small_ops = nb[0] <= 5u && nb[1] <= 5u && nb[2] <= 5u && nb[3] <= 5u;
-            if (RB_FMT_WORDS && __ballot(!small_ops) == 0ull) {
-                unsigned long long S = 0ull, W[4];
-                uint32_t e[4], cum[4], c_ = 0u;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t n_ = nb[q];
-                    const uint32_t d4 = rb_digits4(len[q]) | 0x30303030u; // digit j of the length in byte j
-                    const uint32_t ch = (uint32_t)(uint8_t)("MIDNSHP=X??????"[opc[q] < 9u ? opc[q] : 9u]);
-                    const uint32_t hi = __builtin_amdgcn_perm(ch, d4, 0x04000102u);   // bytes: digit 2, digit 1, digit 0, the character
-                    const unsigned long long T = ((unsigned long long)hi << 32) | (unsigned long long)(d4 & 0xFF000000u); // ... digit 3 below them
-                    const uint32_t sh = 8u * n_;
-                    const unsigned long long keep = ~0ull << ((64u - sh) & 63u);       // the top n_ bytes (n_ = 0: not used)
-                    S = n_ ? ((S >> sh) | (T & keep)) : S;
-                    W[q] = S;
-                    c_ += n_, o += n_;
-                    cum[q] = c_, e[q] = o;
-                }
-                // the tail of the lane in front (a lane that has an op is behind a lane with four: at least eight bytes, all its own)
-                const uint32_t p_lo = rb_prev_lane((uint32_t)S, 0u), p_hi = rb_prev_lane((uint32_t)(S >> 32), 0u);
-                const unsigned long long prevS = ((unsigned long long)p_hi << 32) | p_lo;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    if (nb[q]) {
-                        const unsigned long long w = W[q] | (cum[q] < 8u ? (prevS >> (8u * cum[q])) : 0ull);
-                        __builtin_memcpy(stg + e[q] - 8u, &w, 8); // (one ds_write_b64 at a byte address: gfx950 takes it)
-                    }
-                }
-            } else {
+            // one predicated byte store per digit.  (An op's text as one 8-byte LDS store that ends at the op's last byte, where no op of the
+            // step has more than four digits: bit-exact (133 tests), and 2 % SLOWER -- 1.85 against 1.81 ms, profiles/r04_text_summary.md.)
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 if (nb[q]) {
@@ -384,14 +327,13 @@ __global__ __launch_bounds__(256) void rb_k_format_cigars(rb_format_params p) {
                     o += nb[q];
                 }
             }
-            }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             const uint64_t cap_end = p.text_cap;
             const uint32_t end = phase + step_bytes;                 // buffer bytes [phase, end) are this step's
             const uint32_t a16 = (phase + 15u) & ~15u, b16 = end & ~15u; // whole 16-byte groups [a16, b16)
             uint8_t *__restrict__ dst = p.text + (out - phase);      // 16-byte aligned (text is, by contract)
-            if (RB_FMT_STOP != 2 && out + step_bytes <= cap_end) {
+            if (out + step_bytes <= cap_end) {
                 if (a16 < b16) {
                     for (uint32_t k = a16 + 16u * (uint32_t)lane; k < b16; k += 1024u)
                         *reinterpret_cast<uint4 *>(dst + k) = *reinterpret_cast<const uint4 *>(stg + k);

@@ -1,5 +1,5 @@
 #!/bin/bash
-# round 6, nucfreq: parity of the pipelined tile kernel (tests + soak), then same-box A/B against the serial loop (variants nf_old / nf_new)
+# nucfreq: parity of the tile kernel (tests + soak), then same-box A/B of the library variants named as arguments (tools/mkvariant.sh)
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/r06_nf

@@ -11,7 +11,10 @@ mkdir -p ../variants /tmp/rbvar_$name
 obj=${src%.hip}.o
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-value -Wno-unused-function -ffp-contract=off "$@" -c $src -o /tmp/rbvar_$name/$obj
 objs=""
-for o in capi.o k_records.o k_liftover.o k_liftover_list.o k_tile.o k_misc.o k_trim.o k_trim4.o k_trim_pass.o k_text.o k_nucfreq.o; do
+srcs=$(sed -n 's/^SRCS *= *//p' Makefile) # (the library's own list: a file added there is in every variant)
+[ -n "$srcs" ] || { echo "no SRCS line in $(pwd)/Makefile" >&2; exit 1; }
+for s in $srcs; do
+  o=${s%.hip}.o
   if [ "$o" = "$obj" ]; then objs="$objs /tmp/rbvar_$name/$obj"; else objs="$objs $o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../variants/$name.so $objs

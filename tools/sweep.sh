@@ -2,7 +2,8 @@
 # diagnostics (on the GPU box): one kernel file rebuilt under each set of -D flags as a library VARIANT (tools/mkvariant.sh: rustybam_amd/variants/,
 # never the product library) and timed through RB_VARIANT.
 #   tools/sweep.sh k_liftover.hip "-DA=1" "-DA=2 -DB"     the headline step (bench.py --placement-tries 1: kernel ms + output digest)
-#   tools/sweep.sh k_nucfreq.hip "-DNF_TILE=2048" ...     config 5 (tools/bench_nucfreq.py: ms per call)
+#   tools/sweep.sh k_nucfreq.hip "" "-DNF_DIAG"           config 5 (tools/bench_nucfreq.py: ms per call); the kernel files keep no timing switches
+#                                                         of their own: what is swept is a right-result flag like this one, or a local experiment's
 # BENCH_ARGS adds flags to the bench.
 cd "$(dirname "$0")/.."
 src=$1; shift
