@@ -170,24 +170,23 @@ __global__ __launch_bounds__(256) void rb_k_make_jobs(rb_lift_params p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// streaming kernel: the body is rb_stream.h, with the load ring at v80..v95 here (k_liftover_list.hip: the same body over a list of
-// records, ring at v88..v103)
+// streaming kernel: the body is rb_stream.h, with the load ring at v88..v103 (k_liftover_list.hip: the same body over a list of
+// records, the same ring)
 // ------------------------------------------------------------------------------------------------
-#define RB_RING_BASE 80
-#define RB_RING_TOP_N 95
-#define RB_SPILL_ROOM 0
-#define RB_WPE 5, 6
+#define RB_RING_BASE 88
+#define RB_RING_TOP_N 103
+#define RB_SPILL_ROOM 4
+#define RB_WPE 4, 5
 #include "rb_stream.h"
-// the builds of the kernel (an attribute cannot depend on a template parameter): liftover, break-paf in one walk, and the
-// diagnostics build of the liftover form
+// the builds of the kernel (an attribute cannot depend on a template parameter): liftover and its diagnostics build; break-paf in one
+// walk, which captures nothing and keeps the ring at v80 and five waves per SIMD, is k_liftover_brk.hip
 #define RB_STREAM_KERNEL(NAME, BRK, DIAG, ROOM)                                                                                   \
     __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RB_WPE), amdgpu_num_vgpr(RB_RING_BASE - (ROOM)))) void NAME(rb_lift_params p_) { \
         (void)p_; /* (read through the kernel-argument segment, see the top of rb_stream_record) */                                \
         rb_stream_record<BRK, DIAG>();                                                                                            \
     }
 RB_STREAM_KERNEL(rb_k_liftover_stream, false, false, RB_SPILL_ROOM)
-RB_STREAM_KERNEL(rb_k_liftover_stream_brk, true, false, RB_SPILL_ROOM)
-RB_STREAM_KERNEL(rb_k_liftover_stream_diag, false, true, 4)
+RB_STREAM_KERNEL(rb_k_liftover_stream_diag, false, true, 5)
 // (no diagnostics build of the break form: its spilled scalar registers land in the ring -- tools/check_ring.py --, and nothing asks for it)
 
 // ------------------------------------------------------------------------------------------------
@@ -1153,8 +1152,8 @@ extern "C" hipError_t rb_launch_liftover_stream(const rb_lift_params *p, hipStre
             return hipGetLastError();
         }
     }
-    if (p->brk_mode) hipLaunchKernelGGL(rb_k_liftover_stream_brk, dim3(blocks), dim3(256), 0, stream, *p);
-    else hipLaunchKernelGGL(rb_k_liftover_stream, dim3(blocks), dim3(256), 0, stream, *p);
+    if (p->brk_mode) return rb_launch_liftover_stream_brk(p, blocks, stream);
+    hipLaunchKernelGGL(rb_k_liftover_stream, dim3(blocks), dim3(256), 0, stream, *p);
     return hipGetLastError();
 }
 extern "C" hipError_t rb_launch_liftover_tail(const rb_lift_params *p, hipStream_t stream) {

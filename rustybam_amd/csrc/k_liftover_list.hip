@@ -1,9 +1,10 @@
 // k_liftover_list.hip -- the per-record clip kernel (rb_stream.h, k_liftover.hip) over a LIST of records: the records of the tiles the tile
 // kernel (k_tile.hip) handed back.  Workgroups that stay and take entry after entry.  A translation unit of its own because of its registers:
 // the loop around the record's body makes the compiler park spilled scalar registers in two more vector registers than the plain
-// kernels need, and it places them right behind its own allocation -- where the plain kernels keep their load ring (v80..v95,
+// kernels need, and it places them right behind its own allocation -- where the plain kernels kept their load ring at the time (v80..v95,
 // tools/check_ring.py found them at v80 v81).  Here the ring sits at v88..v103 and the compiler is held to 84 registers: four waves
-// per SIMD instead of five, on a path that sees the odd record.
+// per SIMD, on a path that sees the odd record.  (The plain kernels have their ring there too since the liftover build captures its
+// boundaries; this form does not capture -- rb_stream.h, CAP -- because with the capture its build reaches v90.)
 #include "rb_lift.h"
 #include "rb_launch.h"
 #define RB_RING_BASE 88

@@ -29,7 +29,7 @@ extern "C" hipError_t rb_launch_scan_records(const rb_scan_params *p, hipStream_
 extern "C" hipError_t rb_launch_scan_rows(const rb_scan_params *p, void *long_buf, hipStream_t stream);
 extern "C" hipError_t rb_launch_peek_norm(const rb_scan_params *p, hipStream_t stream);
 
-// ---- k_liftover.hip, k_liftover_list.hip, k_tile.hip: the clip kernels ----
+// ---- k_liftover.hip, k_liftover_brk.hip, k_liftover_list.hip, k_tile.hip: the clip kernels ----
 extern "C" hipError_t rb_launch_count_and_scan(const rb_lift_params *p, uint64_t *block_sums, bool do_count, hipStream_t stream);
 extern "C" hipError_t rb_launch_exclusive_scan(uint64_t *v, uint64_t n, uint64_t *block_sums, uint64_t *total_out, hipStream_t stream);
 extern "C" size_t rb_scan_block_sums_count(uint64_t n_rec);
@@ -37,6 +37,7 @@ extern "C" hipError_t rb_launch_make_jobs(const rb_lift_params *p, hipStream_t s
 extern "C" hipError_t rb_launch_liftover_stream(const rb_lift_params *p, hipStream_t stream);
 extern "C" hipError_t rb_launch_liftover_tail(const rb_lift_params *p, hipStream_t stream);
 extern "C" hipError_t rb_launch_liftover_stream_list(const rb_lift_params *p, hipStream_t stream);
+extern "C" hipError_t rb_launch_liftover_stream_brk(const rb_lift_params *p, unsigned blocks, hipStream_t stream); // k_liftover_brk.hip, called by rb_launch_liftover_stream
 extern "C" hipError_t rb_launch_liftover_tiles(const rb_lift_params *p, hipStream_t stream);
 extern "C" uint32_t rb_tile_max_ops(void);
 extern "C" uint32_t rb_tile_max_records(void);

@@ -247,19 +247,14 @@ __device__ __forceinline__ bool rb_ism(uint32_t v) { return rb_in(RB_MATCH_MASK,
 // inclusive prefixes of the last op with p_k true: one conditional move each.  No index comparisons, no six-way moves under an
 // exec mask per op (the round-2 form: 27 vector instructions per op, 430 per group).  The op in front of
 // the group is loaded with the group, not after the search has shown that it is needed.
-__device__ __forceinline__ rb_bres rb_resolve(const uint32_t *__restrict__ ops, uint32_t n, int32_t cidx, uint32_t cR, uint32_t cQ,
-                                              uint32_t cU, uint32_t D, bool is_start, int policy) {
+// rb_resolve_group: the search and the rules on a group that is already in registers -- g[] = ops cidx .. cidx + 7, pv = the op in
+// front of them (used only where the group's first op is f and f > 0) --; only the rare walks read ops[] again.  rb_resolve loads the
+// group from the record first; the stream kernel hands over what a lane captured while the step streamed the group (rb_stream.h).
+__device__ __forceinline__ rb_bres rb_resolve_group(const uint32_t *__restrict__ ops, uint32_t n, int32_t cidx, const uint32_t (&g)[8],
+                                                    uint32_t pv, uint32_t cR, uint32_t cQ, uint32_t cU, uint32_t D, bool is_start, int policy) {
     rb_bres o;
     o.st = RB_S_DEFER;
     o.op = o.part = o.R = o.Q = o.U = 0;
-    uint32_t g[RB_CP_OPS];
-    uint32_t pv;
-    {
-        const uint4 *q = reinterpret_cast<const uint4 *>(ops + cidx); // 16-byte aligned by construction
-        const uint4 a0 = q[0], a1 = q[1];
-        g[0] = a0.x; g[1] = a0.y; g[2] = a0.z; g[3] = a0.w; g[4] = a1.x; g[5] = a1.y; g[6] = a1.z; g[7] = a1.w;
-        pv = ops[cidx > 0 ? cidx - 1 : 0]; // the op in front of the group (used only where the group's first op is f and f > 0)
-    }
     uint32_t np = 0, fR = cR, fQ = cQ, fU = cU, fv = 0;
     {
         uint32_t R = cR, Q = cQ, U = cU;
@@ -360,6 +355,43 @@ __device__ __forceinline__ rb_bres rb_resolve(const uint32_t *__restrict__ ops, 
         return o;
     }
 }
+__device__ __forceinline__ rb_bres rb_resolve(const uint32_t *__restrict__ ops, uint32_t n, int32_t cidx, uint32_t cR, uint32_t cQ,
+                                              uint32_t cU, uint32_t D, bool is_start, int policy) {
+    uint32_t g[RB_CP_OPS];
+    const uint4 *q = reinterpret_cast<const uint4 *>(ops + cidx); // 16-byte aligned by construction
+    const uint4 a0 = q[0], a1 = q[1];
+    g[0] = a0.x; g[1] = a0.y; g[2] = a0.z; g[3] = a0.w; g[4] = a1.x; g[5] = a1.y; g[6] = a1.z; g[7] = a1.w;
+    const uint32_t pv = ops[cidx > 0 ? cidx - 1 : 0]; // the op in front of the group
+    return rb_resolve_group(ops, n, cidx, g, pv, cR, cQ, cU, D, is_start, policy);
+}
+// A checkpoint every 2 RB_CP_OPS ops (the stream kernel's liftover build, whose captured boundaries need none): the 8 ops behind it are
+// loaded from the record, and if they end at or in front of offset D the 8 after them take their place, with their index and prefixes
+// in cidx, cR, cQ, cU (a second trip, on a path that is rare: two groups at once cost the kernel eight registers).
+__device__ __forceinline__ void rb_load_group_wide(const uint32_t *__restrict__ ops, uint32_t n, int32_t &cidx, uint32_t &cR, uint32_t &cQ,
+                                                   uint32_t &cU, uint32_t D, uint32_t (&g)[8], uint32_t &pv) {
+    const uint4 *q = reinterpret_cast<const uint4 *>(ops + cidx); // 64-byte aligned by construction
+    {
+        const uint4 a0 = q[0], a1 = q[1];
+        g[0] = a0.x; g[1] = a0.y; g[2] = a0.z; g[3] = a0.w; g[4] = a1.x; g[5] = a1.y; g[6] = a1.z; g[7] = a1.w;
+        pv = ops[cidx > 0 ? cidx - 1 : 0];
+    }
+    uint32_t R = cR, Q = cQ, U = cU;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint32_t v = (uint32_t)(cidx + k) < n ? g[k] : 0u; // (also the negative indices of the aligned head)
+        const uint32_t len = rb_len(v);
+        R += len & (uint32_t)__builtin_amdgcn_sbfe((int)0xFFFDFFFDu, v, 1u);
+        Q += len & (uint32_t)__builtin_amdgcn_sbfe((int)0xFFF3FFF3u, v, 1u);
+        U += len;
+    }
+    if (R <= D) {
+        pv = g[7];
+        const uint4 a0 = q[2], a1 = q[3];
+        g[0] = a0.x; g[1] = a0.y; g[2] = a0.z; g[3] = a0.w; g[4] = a1.x; g[5] = a1.y; g[6] = a1.z; g[7] = a1.w;
+        cidx += 8, cR = R, cQ = Q, cU = U;
+    }
+}
+
 
 
 // ---- windows of one pass ---------------------------------------------------------------------------

@@ -1,12 +1,18 @@
 // rb_stream.h -- the per-record streaming clip kernel's body, rb_stream_record<BRK, DIAG, LIST> (see the head of k_liftover.hip for
-// what it does), with the load ring it keeps in vector registers the compiler cannot see.  Included once by each of its two users,
+// what it does), with the load ring it keeps in vector registers the compiler cannot see.  Included once by each of its three users,
 // which differ in where the ring sits and define, in front of the #include:
 //   RB_RING_BASE    first register of the ring; the compiler is held to the registers below it (amdgpu_num_vgpr)
 //   RB_RING_TOP_N   last register of the ring (RB_RING_BASE + 15)
 //   RB_SPILL_ROOM   registers between the compiler's allocation and the ring, for the VGPRs it parks spilled scalar registers in
 //   RB_WPE          waves per SIMD the register budget is cut for (amdgpu_waves_per_eu: "min, max")
-// k_liftover.hip: 80, 95, 0, (5, 6) -- the plain kernels; k_liftover_list.hip: 88, 103, 4, (4, 5) -- the list kernels.
-// tools/check_ring.py disassembles both and fails if the compiler names a register of the ring.
+// k_liftover.hip: 88, 103, 4, (4, 5) -- the liftover kernel; k_liftover_brk.hip: 80, 95, 0, (5, 6) -- break-paf; k_liftover_list.hip:
+// 88, 103, 4, (4, 5) -- the list kernels.
+// (the liftover kernel had the ring at v80 and five waves per SIMD until it began to capture its boundaries in the step: with the
+//  capture the compiler wants 81 registers and two more for its spilled scalars; round 4 measured four waves at +0.5 %)
+// tools/check_ring.py disassembles all three and fails if the compiler names a register of the ring.
+// Boundaries: a step that streams the chunk holding a clip's start or end offset leaves the chunk's 8 ops, the op in front and the
+// prefixes in an LDS entry of that boundary, and the resolution behind the segment reads the entry instead of loading the group from
+// the record a second time (by then out of L2: ~100 bytes fetched per boundary, a dependent trip with the ring drained).
 //
 // One configuration is built, the one rounds 2 - 5 arrived at (docs/history.md, profiles/r04_stream_summary.md); what lost, in a line each:
 //   a step of 4 ops per lane ("flat": one 16-byte load per lane, whole 128-byte lines per instruction, 6 % cheaper in the memory-mix
@@ -38,7 +44,6 @@
 #define RB_OPL 8                                   // ops per lane and step
 #define RB_GRP 2                                   // 16-byte groups per lane and step
 #define RB_STEP_SHIFT 9                            // log2 of the ops of a step
-#define RB_CP_PER_STEP ((64 * RB_OPL) / RB_CP_OPS) // one checkpoint per RB_CP_OPS ops: every lane leaves one
 #define RB_PF 2                                    // steps of stream loads in flight per wave (4 KiB)
 #define RB_SMAX 10                                 // steps whose checkpoints fit in LDS at once; whole turns of the load ring
 static_assert(RB_GRP * 4 == RB_OPL && (1 << RB_STEP_SHIFT) == 64 * RB_OPL && RB_CP_OPS == RB_OPL && RB_SMAX % RB_PF == 0, "the shape of a step");
@@ -60,9 +65,13 @@ static_assert(RB_RING_TOP_N == RB_RING_BASE + 8 * RB_PF - 1, "the ring is RB_PF 
 // (NOT all sixteen: a register named as clobbered is one the compiler may use for its own temporaries between two asm statements --
 //  tried, it did.  What keeps the compiler out of the ring is amdgpu_num_vgpr, with one gap: the VGPRs it spills scalar registers into
 //  are placed behind its own allocation, and one build of this kernel had them at v78 v79 v80.  tests/test_ring_registers.py
-//  disassembles both builds and fails if anything outside the asm statements names a register of the ring.)
+//  and tests/test_ring_registers_brk.py disassemble every build and fail if anything outside the asm statements names a register of the ring.)
 // registers OFF .. OFF + W of the ring, as the assembler reads them (it evaluates the sums)
 #define RB_RREG(OFF, W) "v[" RB_STR(RB_RING_BASE) "+" #OFF ":" RB_STR(RB_RING_BASE) "+" #OFF "+" #W "]"
+#define RB_RREG1(OFF) "v[" RB_STR(RB_RING_BASE) "+" #OFF "+1]" // the second register of the pair at OFF
+typedef uint32_t rb_u32x4 __attribute__((ext_vector_type(4)));
+// the LDS byte address of a __shared__ object, for the asm statements that write LDS from the ring
+__device__ __forceinline__ uint32_t rb_lds_addr(const void *q) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)q; }
 // RB_RING_CASE(ring, M): M(<the slot's registers>) for the ring slot `ring` (a compile-time constant)
 #define RB_RING_CASE(RING, M)                                                                                                   \
     if constexpr ((RING) == 0) { M(0, 2, 4, 6) } else { M(8, 10, 12, 14) }
@@ -84,9 +93,27 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
     // diagnostics (bench.py --debug-skip: phases of the kernel switched off, phase timers, clock stamps) only in the DIAG
     // instantiation: every tested bit is a wave-uniform boolean, i.e. two scalar registers held through the whole record
     const int dbg = DIAG ? p.debug_skip : 0;
-    // checkpoints: exclusive (R,Q,U) prefixes every RB_CP_OPS ops, SoA so that R can be binary-searched
-    __shared__ uint32_t cp_all[4][3][RB_SMAX * RB_CP_PER_STEP];
+    // checkpoints: exclusive (R,Q,U) prefixes every CPO ops, SoA so that R can be binary-searched.  The liftover build resolves from
+    // what the step captured (cap_all below) and searches the checkpoints only for the boundaries the capture did not take: it keeps one
+    // per 16 ops (every other lane leaves one; the fallback loads 16 ops and picks the half, rb_load_group_wide), which makes the room
+    // for the capture table.  The break build and the list form capture nothing and keep one per lane.
+    // (the list form, like break-paf, stays as it was: with the capture its build reaches v87 and parks its spilled scalars in v88 v89,
+    //  the first registers of its ring, which tests/test_ring_registers.py holds at v88..v103)
+    constexpr bool CAP = !BRK && !LIST;
+    constexpr uint32_t CPO = CAP ? 2u * RB_CP_OPS : (uint32_t)RB_CP_OPS, CPS = (64u * RB_OPL) / CPO; // ops per checkpoint, checkpoints per step
+    __shared__ uint32_t cp_all[4][3][RB_SMAX * CPS];
     __shared__ uint32_t wx_all[4][RB_HMAX + 1]; // window indices of one pass over a window list that is not sorted
+    // the capture table: entry b of a wave belongs to boundary b of the pass (lane b resolves it: b < 32 the start of clip b, else the
+    // end of clip b - 32) and holds what the lane that streamed the boundary's chunk had in registers: its 8 ops, {the op in front of
+    // them, the exclusive R, Q, U prefixes} -- 48 bytes --, and in cap_t the chunk's number in the segment
+    __shared__ uint4 cap_all[CAP ? 4 : 1][CAP ? 64 * 3 : 1];
+    __shared__ uint32_t cap_t[CAP ? 4 : 1][CAP ? 64 : 1];
+    // LDS per block: liftover 15,360 + 528 + 12,288 + 1,024 = 29,200 bytes, break-paf and the list form 30,720 + 528 + 16 + 4 = 31,268
+    static_assert(sizeof(cp_all) + sizeof(wx_all) + sizeof(cap_all) + sizeof(cap_t) == (CAP ? 29200u : 31268u), "LDS of a block");
+    { // a block is four waves, one per SIMD: the waves per SIMD the build is cut for (RB_WPE, the lower figure) are its blocks per CU
+        constexpr uint32_t wpe_[2] = {RB_WPE};
+        static_assert(wpe_[0] * (sizeof(cp_all) + sizeof(wx_all) + sizeof(cap_all) + sizeof(cap_t)) <= 163840u, "LDS of the blocks of a CU");
+    }
     const uint32_t wib = rb_first(threadIdx.x >> 6); // wave in block (told to the compiler as the wave-uniform value it is)
     uint64_t wave;
     if constexpr (LIST) {
@@ -216,6 +243,17 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
 #define RB_RING_NOSTORES                                                                                                        \
     _Pragma("unroll") for (int q_ = 0; q_ < RB_GRP * RB_MS; q_++)                                                               \
         asm volatile("s_mov_b64 exec, 0\n\tglobal_store_dword %0, %0, %1\n\ts_mov_b64 exec, %2" ::"v"(0u), "s"(gbase0), "s"(sv_exec) : "memory");
+    // the capture's asm statements (the ring's registers named literally, like the loads and stores): the slot's last op into a register
+    // of the compiler's; an entry of the capture table written from the slot; the last op of lane 63 into a scalar register
+#define RB_RING_LASTOP(A, B_, C_, D_) asm volatile("v_mov_b32 %0, " RB_RREG1(D_) "\n\ts_nop 1" : "=v"(lastw));
+#define RB_RING_CAPTURE(A, B_, C_, D_)                                                                                          \
+    asm volatile("ds_write_b128 %0, " RB_RREG(A, 3) "\n\tds_write_b128 %0, " RB_RREG(C_, 3) " offset:16\n\t"                    \
+                 "ds_write2_b32 %0, %1, %2 offset0:8 offset1:9\n\tds_write2_b32 %0, %3, %4 offset0:10 offset1:11\n\t"            \
+                 "ds_write_b32 %5, %6\n\ts_waitcnt lgkmcnt(0)"                                                                  \
+                 :                                                                                                              \
+                 : "v"(ea), "v"(pvw), "v"(cR), "v"(xQ), "v"(xU), "v"(ta), "v"(tq)                                               \
+                 : "memory");
+#define RB_RING_CARRY(A, B_, C_, D_) asm volatile("v_readlane_b32 %0, " RB_RREG1(D_) ", 63" : "=s"(v_carry));
     // The first pass of a record streams it from its first step: the ring's first loads go out HERE, in front of the pass's window loads
     // (a chain of dependent loads of its own), not behind them -- one memory latency per record instead of two in front of the first step.
     const bool preloaded = !(dbg & 4);
@@ -289,7 +327,9 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
         // minimum of code XOR previous code (0: two adjacent ops of one type), maximum of the per-lane length sums (2^25 and
         // more: the 64-lane scans could leave 32 bits; handed back like a zero length)
         uint32_t v_reg = 0xFFFFFFFFu, v_minw = 0xFFFFFFFFu, v_adj = 0xFFFFFFFFu, v_maxsu = 0u;
-        uint32_t v_carry = 0xFu;       // last op word of the previous step (code 15: equals nothing)
+        uint32_t v_carry = 0xFu;       // last op word of the previous step (code 15: equals nothing; none yet)
+        unsigned long long cap_mask = 0ull; // boundaries of this pass whose entry of the capture table is valid
+        unsigned long long cap_pend = 0ull; // ... whose offset is the first one of the next step (their clip ended on the last base of this one)
         unsigned long long v_utot = 0; // 64-bit sum of all lengths
         const bool streams = BRK || ((__ballot(need) != 0 || validate || (spec && any_inside)) && !(dbg & 4));
         // diagnostics (dbg & 128): the clock this kernel holds while it streams -- s_memtime counts shader cycles, s_memrealtime a
@@ -372,7 +412,6 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
                     }
                     if (validate_s) {
                         const uint32_t prevw = rb_prev_lane(c[RB_OPL - 1], v_carry); // previous lane's last op; lane 0: the previous step's
-                        v_carry = rb_readlane<uint32_t>(c[RB_OPL - 1], 63);
                         uint32_t rg[RB_OPL], x[RB_OPL];
 #pragma unroll
                         for (int q = 0; q < RB_OPL; q++) {
@@ -399,11 +438,13 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
                         su += len;
                     }
                     const uint32_t ir = rb_wave_scan_incl(sr), iq = rb_wave_scan_incl(sq), iu = rb_wave_scan_incl(su);
-                    { // a checkpoint every RB_CP_OPS ops: in front of every lane's chunk
-                        const uint32_t t = (st - seg0) * RB_CP_PER_STEP + (uint32_t)lane;
+                    // exclusive prefixes in front of the lane's chunk: the checkpoints, and what a captured boundary takes along
+                    const uint32_t xQ = Qb + iq - sq, xU = Ub + iu - su;
+                    if (!CAP || !(lane & 1)) { // a checkpoint every CPO ops
+                        const uint32_t t = (st - seg0) * CPS + ((uint32_t)lane >> (CAP ? 1 : 0));
                         cpR[t] = Rb + ir - sr;
-                        cpQ[t] = Qb + iq - sq;
-                        cpU[t] = Ub + iu - su;
+                        cpQ[t] = xQ;
+                        cpU[t] = xU;
                     }
                     const uint32_t R0 = Rb;
                     Rb += rb_readlane<uint32_t>(ir, 63);
@@ -472,12 +513,50 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
                         // outside the clip is never read, and the two end ops are rewritten with the clipped
                         // lengths once the boundaries are resolved.
                         const uint32_t cR = R0 + ir - sr, cE = R0 + ir;
+                        // Capture: the chunk that holds a clip's start offset / its end offset (cR <= D < cE) is the group the resolution
+                        // will search.  The lane that has it writes the boundary's entry (is / ie: the boundary's lane), under a mask that
+                        // is empty in most steps: its 8 ops straight from the ring, the op in front of them (the lane below's last op;
+                        // lane 0: the last op of the step before), its prefixes, the chunk's number in the segment.
+                        auto capture = [&](const bool hs, const uint32_t is, const bool he, const uint32_t ie) {
+                            if (rb_ballot(hs || he) != 0ull) {
+                                uint32_t lastw;
+                                RB_RING_CASE(ring, RB_RING_LASTOP)
+                                const uint32_t pvw = rb_prev_lane(lastw, v_carry);
+                                // (lane 0 of the step a later pass resumes at has no op in front: the fallback takes its boundary)
+                                const bool pv_ok = lane != 0 || st == 0u || v_carry != 0xFu;
+                                const uint32_t wv = threadIdx.x >> 6;
+                                const uint32_t tq = (st - seg0) * 64u + (uint32_t)lane;
+                                const bool ps = hs && pv_ok, pe = he && pv_ok;
+                                if (ps) {
+                                    const uint32_t ea = rb_lds_addr(&cap_all[0][0]) + (wv * 64u + is) * 48u, ta = rb_lds_addr(&cap_t[0][0]) + (wv * 64u + is) * 4u;
+                                    RB_RING_CASE(ring, RB_RING_CAPTURE)
+                                }
+                                if (pe) {
+                                    const uint32_t ea = rb_lds_addr(&cap_all[0][0]) + (wv * 64u + ie) * 48u, ta = rb_lds_addr(&cap_t[0][0]) + (wv * 64u + ie) * 4u;
+                                    RB_RING_CASE(ring, RB_RING_CAPTURE)
+                                }
+                                cap_mask |= (rb_ballot(ps) != 0ull ? 1ull << is : 0ull) | (rb_ballot(pe) != 0ull ? 1ull << ie : 0ull);
+                            }
+                        };
+                        if constexpr (CAP) {
+                            // boundaries of clips that ended on the last base of the step before: their offset is this step's first one,
+                            // held by the first chunk that is not empty
+                            while (cap_pend != 0ull) {
+                                const uint32_t bi = (uint32_t)__builtin_ctzll(cap_pend);
+                                cap_pend &= cap_pend - 1ull;
+                                capture(cR == R0 && cE != R0, bi, false, bi);
+                            }
+                        }
 #pragma unroll
                         for (int q = 0; q < RB_MS; q++) {
                             unsigned long long mk = 0ull;
                             for (;;) {
                                 mk |= rb_ballot(cR < c_de[q] && cE >= c_ds[q]);
+                                if constexpr (CAP) capture(c_ds[q] - cR < cE - cR, c_j[q] & 31u, c_de[q] - cR < cE - cR, 32u + (c_j[q] & 31u));
                                 if (c_de[q] > Rb) break; // the clip reaches past this step (or there is none): it stays the current one
+                                if constexpr (CAP) { // its last base is the step's last one: the chunk with its end offset is the next step's first
+                                    if (c_de[q] == Rb) cap_pend |= (1ull << (32u + (c_j[q] & 31u))) | (c_ds[q] == Rb ? 1ull << (c_j[q] & 31u) : 0ull);
+                                }
                                 c_j[q] += n_slots;       // it ends in this step: the class's next clip may begin in it
                                 clip_fetch(q);
                                 if (c_j[q] >= nb) break;
@@ -534,6 +613,11 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
 #undef RB_RING_STORE
                     }
                 }
+                // the last op of the step, for the adjacency check and the captures of the next one (in front of the slot's reload).  The raw
+                // word of lane 63, where the adjacency check used to carry its masked copy: they differ only when lane 63 lies past the
+                // record's end, and no step follows such a step.  (An SGPR written inside an asm: the compiler's hazard recogniser does not
+                // see the v_readlane, which is fine for VALU data -- never use v_carry as an address or a lane select.)
+                RB_RING_CASE(ring, RB_RING_CARRY)
                 RB_RING_LOAD(ring, st + RB_PF)
             };
             for (seg0 = seg_first * RB_SMAX; seg0 < n_steps; seg0 += RB_SMAX) {
@@ -551,7 +635,7 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
                 }
                 // ---- lane-parallel resolution of the boundaries that fall in this segment ----
                 const bool last_seg = seg1 == n_steps;
-                const uint32_t n_cp = (seg1 - seg0) * RB_CP_PER_STEP;
+                const uint32_t n_cp = (seg1 - seg0) * CPS;
                 const int32_t cp_idx0 = (int32_t)(seg0 << RB_STEP_SHIFT) - head; // op index of checkpoint 0
                 if constexpr (BRK) {
                     if (last_seg) { // liftover.rs:213-224: what lies behind the last long indel
@@ -577,13 +661,39 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
                             if (is_start) O.part = rb_part_pack(1u, lv), O.R = Rb - 1, O.Q = Qb - 1, O.U = Ub - 1;
                             else O.part = rb_part_pack(rb_len(lv), lv), O.R = Rb, O.Q = Qb, O.U = Ub;
                         } else {
-                            // last checkpoint with R <= D (R is non-decreasing)
-                            uint32_t lo_t = 0, hi_t = n_cp;
-                            while (hi_t - lo_t > 1) {
-                                const uint32_t mid = (lo_t + hi_t) >> 1;
-                                if (cpR[mid] <= D) lo_t = mid; else hi_t = mid;
+                            // the group of 8 ops that holds offset D, the op in front of it and the prefixes at its first op: from the
+                            // boundary's entry of the capture table, or -- a boundary no step captured: windows that are not sorted, a clip
+                            // that starts in front of the step in which it became its class's current one, a later pass's resume point --
+                            // from the last checkpoint with R <= D (R is non-decreasing) and the record
+                            uint32_t g[8], pv, gR, gQ, gU;
+                            int32_t gidx;
+                            bool captured = false;
+                            if constexpr (CAP) captured = ((cap_mask >> lane) & 1ull) != 0ull;
+                            if (captured) {
+                                const uint4 *e = &cap_all[wib][3 * lane];
+                                const uint4 e0 = e[0], e1 = e[1], e2 = e[2];
+                                g[0] = e0.x, g[1] = e0.y, g[2] = e0.z, g[3] = e0.w, g[4] = e1.x, g[5] = e1.y, g[6] = e1.z, g[7] = e1.w;
+                                pv = e2.x, gR = e2.y, gQ = e2.z, gU = e2.w;
+                                gidx = cp_idx0 + (int32_t)(cap_t[wib][lane] * RB_CP_OPS);
+                                if (dbg & 1024) atomicAdd(&p.counters->phase[1], 1u); // diagnostics: boundaries resolved from their entry
+                            } else {
+                                uint32_t lo_t = 0, hi_t = n_cp;
+                                while (hi_t - lo_t > 1) {
+                                    const uint32_t mid = (lo_t + hi_t) >> 1;
+                                    if (cpR[mid] <= D) lo_t = mid; else hi_t = mid;
+                                }
+                                gidx = cp_idx0 + (int32_t)(lo_t * CPO), gR = cpR[lo_t], gQ = cpQ[lo_t], gU = cpU[lo_t];
+                                if constexpr (CAP) {
+                                    rb_load_group_wide(rec_ops, n, gidx, gR, gQ, gU, D, g, pv);
+                                } else {
+                                    const uint4 *q = reinterpret_cast<const uint4 *>(rec_ops + gidx); // 16-byte aligned by construction
+                                    const uint4 a0 = q[0], a1 = q[1];
+                                    g[0] = a0.x, g[1] = a0.y, g[2] = a0.z, g[3] = a0.w, g[4] = a1.x, g[5] = a1.y, g[6] = a1.z, g[7] = a1.w;
+                                    pv = rec_ops[gidx > 0 ? gidx - 1 : 0];
+                                }
+                                if (dbg & 1024) atomicAdd(&p.counters->phase[0], 1u); // diagnostics: ... from the checkpoints and the record
                             }
-                            O = rb_resolve(rec_ops, n, cp_idx0 + (int32_t)lo_t * RB_CP_OPS, cpR[lo_t], cpQ[lo_t], cpU[lo_t], D, is_start, policy_);
+                            O = rb_resolve_group(rec_ops, n, gidx, g, pv, gR, gQ, gU, D, is_start, policy_);
                         }
                         need = false;
                     }
@@ -605,6 +715,9 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
 #undef RB_RING_LOAD
 #undef RB_RING_LOAD_ASM
 #undef RB_RING_NOSTORES
+#undef RB_RING_LASTOP
+#undef RB_RING_CAPTURE
+#undef RB_RING_CARRY
         }
         if (!streams && preloaded && jb == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (the ring's loads are out: nothing of them may be in flight when the registers are the compiler's again)
         if (dbg & 128) {

@@ -1,10 +1,10 @@
-"""Guard for the streaming clip kernel's load ring: VGPRs v80..v95 are reserved outside the compiler's allocation
-(rb_stream.h as k_liftover.hip includes it: amdgpu_num_vgpr(80), the ring named literally in inline asm).  Nothing in the language
+"""Guard for the streaming clip kernel's load ring: VGPRs v88..v103 are reserved outside the compiler's allocation
+(rb_stream.h as k_liftover.hip includes it: amdgpu_num_vgpr(84), the ring named literally in inline asm).  Nothing in the language
 guarantees that the compiler stays out of them, so this script compiles k_liftover.hip to assembly (hipcc cross-compiles without a GPU)
 and fails if any instruction outside the inline-asm blocks of rb_k_liftover_stream names a register in the ring -- a single register
-v80..v95 or ANY tuple v[a:b] whose range intersects it (v[78:81] as well as v[80:83]).  Run by the Makefile on every build of
+of the ring or ANY tuple v[a:b] whose range intersects it (v[86:89] as well as v[88:91]).  Run by the Makefile on every build of
 k_liftover.o and by tests/test_ring_registers.py.  `--list`: the same body over a list of records (k_liftover_list.hip), ring at
-v88..v103.  `--tile`: the tile kernel's ring (k_tile.hip, rb_k_liftover_tile*), v80..v95."""
+v88..v103.  `--brk`: the break-paf build (k_liftover_brk.hip), ring at v80..v95.  `--tile`: the tile kernel's ring (k_tile.hip, rb_k_liftover_tile*), v80..v95."""
 import os
 import re
 import subprocess
@@ -12,7 +12,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RING = (80, 95)  # k_liftover.hip and k_tile.hip
+RING = (80, 95)  # k_tile.hip, k_liftover_brk.hip
+STREAM_RING = (88, 103)  # k_liftover.hip
 LIST_RING = (88, 103)  # k_liftover_list.hip
 _SINGLE = re.compile(r"\bv(\d+)\b")
 _TUPLE = re.compile(r"\bv\[(\d+):(\d+)\]")
@@ -26,9 +27,9 @@ def ring_uses(line, ring=RING):
     return bad
 
 
-def check_assembly(text, expect_kernels=3, ring=RING, family="rb_k_liftover_stream"):
+def check_assembly(text, expect_kernels=2, ring=STREAM_RING, family="rb_k_liftover_stream"):
     """-> list of (kernel, line) offences; raises if the expected kernels are not in the assembly.
-    k_liftover.hip: liftover, break-paf, diagnostics; k_liftover_list.hip: the two list forms (ring at v88..v103); k_tile.hip (family rb_k_liftover_tile): liftover, break-paf."""
+    k_liftover.hip: liftover, diagnostics; k_liftover_brk.hip: break-paf (ring at v80..v95); k_liftover_list.hip: the two list forms (ring at v88..v103); k_tile.hip (family rb_k_liftover_tile): liftover, break-paf."""
     found, offences = 0, []
     for m in re.finditer(r"^(_Z\d+" + family + r"\w*):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M):
         found += 1
@@ -68,11 +69,17 @@ if __name__ == "__main__":
     args = sys.argv[1:]
     tile = "--tile" in args  # k_tile.hip instead of k_liftover.hip
     args = [a for a in args if a != "--tile"]
+    brk = "--brk" in args  # k_liftover_brk.hip: the break-paf build of the per-record kernel
+    args = [a for a in args if a != "--brk"]
     lst = "--list" in args  # k_liftover_list.hip: the list form of the per-record kernel
     args = [a for a in args if a != "--list"]
     if lst:
         text = compile_to_asm(hipcc, args, "k_liftover_list.hip")
         bad = check_assembly(text, 2, LIST_RING)
+        sp = spills(text)
+    elif brk:
+        text = compile_to_asm(hipcc, args, "k_liftover_brk.hip")
+        bad = check_assembly(text, 1, RING)
         sp = spills(text)
     elif tile:
         text = compile_to_asm(hipcc, args, "k_tile.hip")
