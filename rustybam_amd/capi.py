@@ -33,7 +33,7 @@ HIT_DT = np.dtype(
 PAIR_DT = np.dtype(
     [("split_idx", "<u8"), ("split_score", "<i4"), ("status", "<u4"), ("t_st", "<u8", 2), ("t_en", "<u8", 2),
      ("q_st", "<u8", 2), ("q_en", "<u8", 2), ("nmatch", "<u4", 2), ("aln_len", "<u4", 2), ("out_off", "<u8", 2),
-     ("out_n", "<u4", 2), ("_pad", "<u8")])
+     ("out_n", "<u4", 2), ("_pad", "<u4"), ("_row", "<u4")])  # (the diagnostic word's halves: _pad 1 = cut by a wave kernel, _row 1 = by the row kernel)
 TRIM_PASS_DT = np.dtype([("n_pairs", "<u8"), ("n_deferred", "<u8"), ("ops_end", "<u8"), ("bad_status", "<u4"), ("_pad", "<u4"), ("_reserved", "<u8", 4)])
 COUNTERS_DT = np.dtype(
     [("n_hits", "<u8"), ("out_ops_needed", "<u8"), ("out_ops_used", "<u8"), ("n_generic", "<u8"),

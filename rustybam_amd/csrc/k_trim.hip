@@ -696,9 +696,12 @@ __device__ void rb_tw_pair(const rb_trim_params &p, const uint64_t pi, uint32_t 
     };
     {
         const int64_t gl0 = G_st(L, La, Lb, lxa, lxb), gr0 = G_st(R, Ra, Rb, rxa, rxb), gr1 = G_en(R, Ra, Rb, rxa, rxb);
-        const int64_t rsum = gr1 - gr0; // f(0)
-        if (rsum > best) best = rsum;   // (index stays 0)
-        int64_t cb = INT64_MIN;         // best f over the candidates k > 0 of this lane; ties: the smaller k
+        // SP runs over the whole staged region in 32 bits and may have wrapped (scores of 2^20 over a few thousand query bases); a sum over
+        // the OVERLAP is a difference of two prefixes and fits the reference's i32 wherever the reference is defined (trim_overlap.rs:58-73
+        // adds in i32), so it is exact modulo 2^32: every f is cut to 32 bits before it is compared
+        const int64_t rsum = (int32_t)(gr1 - gr0); // f(0)
+        if (rsum > best) best = rsum;              // (index stays 0)
+        int64_t cb = INT64_MIN;                    // best f over the candidates k > 0 of this lane; ties: the smaller k
         uint64_t ck = 0;
         // a candidate is a position where one record's score changes; that record's own sum up to it comes straight from its
         // prefix arrays, only the other record is searched
@@ -706,7 +709,7 @@ __device__ void rb_tw_pair(const rb_trim_params &p, const uint64_t pi, uint32_t 
             if (pos <= st_ovl || pos > en_ovl) return;
             const int64_t g_other = rb_tw_G_lane(other, pos, ms, ds, is);
             const int64_t gl = own_is_left ? g_own : g_other, gr = own_is_left ? g_other : g_own;
-            const int64_t f = (gl - gl0) + (gr1 - gr);
+            const int64_t f = (int32_t)((gl - gl0) + (gr1 - gr));
             const uint64_t k = pos - st_ovl;
             if (f > cb || (f == cb && k < ck)) cb = f, ck = k;
         };
@@ -722,7 +725,7 @@ __device__ void rb_tw_pair(const rb_trim_params &p, const uint64_t pi, uint32_t 
                 // the score changes where the op starts, where its special last base starts (only if that base scores differently:
                 // a D / N run behind the op) and where the op ends -- which is where the next query op starts, so only the last op
                 // of the range looks at its end
-                const bool special = mi != (int64_t)len * own;
+                const bool special = (int32_t)mi != (int32_t)((int64_t)len * own); // (modulo 2^32, as SP is)
                 if (!v.minus) {
                     const uint64_t lo = v.q_st + Qi;
                     consider(lo, other, is_left, w0);

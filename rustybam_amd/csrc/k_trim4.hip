@@ -487,7 +487,7 @@ __device__ __forceinline__ void rb_q4_pair(const rb_trim_params &p, const uint64
         }
         if (inpl && st == RB_ST_OK) rb_pair_write_cuts(p.out_ops, cutL, cutR);
         w.status = st;
-        w._pad = 1; // (diagnostic: done by a wave kernel; the serial kernel leaves 0)
+        w._pad = 1ull | (1ull << 32); // (diagnostic: low half 1 = done by a wave kernel, the serial kernel leaves 0; high half 1 = by this row kernel)
         p.rows[pi] = w;
     }
 }

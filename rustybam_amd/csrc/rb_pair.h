@@ -11,7 +11,7 @@ __device__ __forceinline__ rb_pair_row rb_pair_row_empty() {
     w.split_idx = 0;
     w.split_score = 0;
     w.status = RB_ST_OK;
-    w._pad = 0; // (diagnostic: a staged form that cuts the pair leaves 1, the serial kernel 0)
+    w._pad = 0; // (diagnostic: low half -- a staged form that cuts the pair leaves 1, the serial kernel 0; high half -- the row kernel leaves 1)
     for (int s = 0; s < 2; s++) {
         w.t_st[s] = w.t_en[s] = w.q_st[s] = w.q_en[s] = 0;
         w.nmatch[s] = w.aln_len[s] = 0;

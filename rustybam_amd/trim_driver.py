@@ -234,7 +234,7 @@ class ResidentTrim:
                     raise RuntimeError(f"trim pair status {bad}: the reference panics")
                 if on_pass is not None:
                     on_pass(self.passes - 1, k, d_l, d_r, d_rows)
-                by_wave = (d_rows[: k * 128].view(torch.int64).view(k, 16)[:, 15] == 1).sum()  # (diagnostic word: 1 = wave-per-pair kernel; read at the end)
+                by_wave = ((d_rows[: k * 128].view(torch.int64).view(k, 16)[:, 15] & 0xFFFFFFFF) == 1).sum()  # (diagnostic word, low half: 1 = a wave kernel cut the pair in place; read at the end)
                 self._by_wave = by_wave if getattr(self, "_by_wave", None) is None else self._by_wave + by_wave
                 self.cursor = (end + 31) // 32 * 32
                 self.pairs_done += k

@@ -218,12 +218,33 @@ def test_pass_selection_on_the_device_equals_the_reference_scan(engine):
     """rb_dev_trim_select against the pair scan of Paf::overlapping_paf_recs restated in numpy (paf.rs:231-284): per query group the
     pair of largest overlap, ties to the first in scan order; contained flags; the count of deferred pairs; groups of one record,
     of a few, and big ones (the whole wave works on those), equal overlaps, contained records, touching (zero-overlap) spans"""
-    import torch
-    from rustybam_amd import capi
-    dev = torch.device("cuda", 0)
     rng = np.random.default_rng(99)
     sizes = [1, 2, 3, 4, 4, 5, 9, 47, 48, 49, 50, 130, 300] + [int(x) for x in rng.integers(1, 8, 400)]
     rng.shuffle(sizes)
+    _check_select(engine, rng, sizes)
+
+
+@pytest.mark.parametrize("q_off", [0, 2**32 - 1000, 2**40])
+def test_pass_selection_with_full_rows_and_far_coordinates(engine, q_off):
+    """the same with what the row kernel of rb_dev_trim_select (groups of up to 16 records, a row of 16 lanes each) was never given: groups
+    of 10 .. 16 records (every lane of a row at work), 17 and 18 (the first sizes of the thread-per-group kernel), four neighbouring groups
+    of 16, 1, 16, 2 records (one wavefront holds rows of different sizes), a group of 16 as the very last one, a group of 16 whose
+    candidate pairs all overlap by the same amount (the tie goes to the first pair in scan order, through the row's four rotate steps);
+    and query coordinates that straddle 2^32 (the halves of q_st / q_en travel apart through the row reads and rotates) or lie at 2^40"""
+    rng = np.random.default_rng(1234)
+    sizes = [1, 2, 3, 4, 4, 5, 9, 47, 48, 49, 50, 130, 300, 10, 12, 15, 16, 16, 17, 18, 33] + [int(x) for x in rng.integers(1, 8, 400)]
+    rng.shuffle(sizes)
+    sizes[200:200] = [16, 1, 16, 2]
+    sizes.append(16)
+    _check_select(engine, rng, sizes, q_off=q_off, chains=(200, len(sizes) - 1))
+
+
+def _check_select(engine, rng, sizes, q_off=0, chains=()):
+    """q_off: added to every query coordinate; chains: groups whose records are laid out as a chain, every record overlapping the next by
+    the same 50 bases and no other (all candidate overlaps of the group are equal), in an order that is not the scan order"""
+    import torch
+    from rustybam_amd import capi
+    dev = torch.device("cuda", 0)
     n = int(sum(sizes))
     grp_off = np.zeros(len(sizes) + 1, np.uint64)
     grp_off[1:] = np.cumsum(sizes)
@@ -231,7 +252,12 @@ def test_pass_selection_on_the_device_equals_the_reference_scan(engine):
     norm = np.zeros(n, capi.NORM_DT)
     q_st = rng.integers(0, 4000, n) // 50 * 50             # coarse grid: equal overlaps, exact containment and touching spans happen
     q_len = (rng.integers(1, 40, n)) * 50
-    norm["q_st"], norm["q_en"] = q_st, q_st + q_len
+    for g in chains:
+        recs = order[int(grp_off[g]):int(grp_off[g + 1])]
+        q_st[recs[rng.permutation(len(recs))]] = 1000 + 100 * np.arange(len(recs))
+        q_len[recs] = 150
+    q_st = [int(x) + q_off for x in q_st]  # (Python ints: the reference below never leaves them)
+    norm["q_st"], norm["q_en"] = q_st, [a + int(b) for a, b in zip(q_st, q_len)]
     norm["n_ops"] = rng.integers(1, 900, n)
 
     def want():
@@ -253,7 +279,7 @@ def test_pass_selection_on_the_device_equals_the_reference_scan(engine):
                     else:
                         cnt += 1
                         if best is None or ov > best[0]:
-                            best = (ov, a, b) if norm["q_st"][a] <= norm["q_st"][b] else (ov, b, a)
+                            best = (ov, a, b) if int(norm["q_st"][a]) <= int(norm["q_st"][b]) else (ov, b, a)
             if best:
                 pairs.append((best[1], best[2]))
                 deferred += cnt - 1
