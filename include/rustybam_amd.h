@@ -121,7 +121,11 @@ enum { RB_BSEARCH_MODERN = 0 /* rustc >= 1.82 (and < 1.52) */, RB_BSEARCH_LEGACY
         * returns RB_E_INVALID (rb_ctx_last_error names the record) before any clip kernel runs if [op_off[r] + first_op, + n_ops) is not
         * inside [0, batch->n_ops).  That check waits for the stream once.  Norm rows that are stale but whose extents stay inside the
         * batch are not caught: keeping them current is the caller's part. */
-       RB_LIFT_OP_STARTS = 1 << 20 };
+       RB_LIFT_OP_STARTS = 1 << 20,
+       /* RB_LIFT_QBED (rb_host_liftover_text and rb_host_liftover_largest_text ONLY; rb_host_break_text returns RB_E_INVALID with it,
+        * and no rb_dev_* entry point knows it -- the wrappers take the bit out of the policy before they call one): liftover --qbed, the
+        * windows are in QUERY coordinates.  See rb_host_liftover_text below. */
+       RB_LIFT_QBED = 1 << 21 };
 
 /* rb_norm_row.flags / rb_reduce_row.flags */
 enum {
@@ -349,8 +353,12 @@ int rb_dev_break(rb_ctx *ctx, const rb_plan *plan, const rb_batch_view *batch, c
                  uint32_t *out_ops, uint64_t out_cap, rb_counters *counters);
 
 /* ---- invert ----------------------------------------------------------------------------------- *
- * out_ops[op_off[r] .. op_off[r+1]) = I<->D swapped, order reversed when strand[r] == '-'.
- * (The header swap t<->q is a host-side field swap.) */
+ * out_ops[op_off[r] .. op_off[r+1]) = I<->D swapped, order reversed when strand[r] == '-' (an op and its RB_OP_CONT word
+ * keep their order).  (The header swap t<->q is a host-side field swap.)  Where out_ops may lie:
+ *   - fully outside [batch->ops, batch->ops + batch->n_ops): the batch is left as it is, the result goes to out_ops;
+ *   - out_ops == batch->ops: IN PLACE, every record is swapped where it lies and the batch's original CIGARs are gone after the
+ *     call (a batch the size of the device's memory needs no second array); calling it twice restores the batch;
+ *   - inside that range but not equal to batch->ops: RB_E_INVALID (rb_ctx_last_error says so), no kernel runs. */
 int rb_dev_swap(rb_ctx *ctx, const rb_batch_view *batch, uint32_t *out_ops);
 
 /* ---- trim-paf: one pass of independent (left, right) overlap pairs ------------------------------ *
@@ -461,6 +469,15 @@ void rb_host_free(void *p);
  *     is computed), scanned (reduce_out / norm_out, either may be NULL), lifted over the windows in descriptor mode, and the
  *     clipped CIGAR of every hit row is printed on the device: row k's text is row_text[row_text_off[k] .. [k + 1]) (empty
  *     for rows whose status is not RB_ST_OK).  rows / row_text_off / row_text are malloc'ed (rb_host_free).
+ *     With RB_LIFT_QBED in bsearch_policy (liftover --qbed, liftover.rs:139-148 in front of the same route): the caller passes the records
+ *     as read from the file -- t_st, t_en, q_st, q_en, strand unswapped, cig_off / cig_end as above -- and only contig is different: it
+ *     is the caller's interning of the records' QUERY names, the names w_contig refers to.  Then, in this order: the CIGARs are parsed;
+ *     the records AS READ are scanned for reduce_out (Paf::from_file's check_integrity, paf.rs:70, is the original record's: a record
+ *     whose target span disagrees with its CIGAR reports RB_ST_PANIC_INTEGRITY_T -- also when its query span disagrees too -- where a
+ *     scan of the swapped record would report _Q for a target span that alone is off, and the I / D counters would change places); rb_dev_swap swaps the parsed ops in place (paf.rs:1050-1065); the batch with its t and q columns exchanged is scanned
+ *     again for norm_out (the swapped record's remove_trailing_indels: first_op, lead_ops, trail_ops count ops of the SWAPPED CIGAR);
+ *     liftover, --largest and the printing run as without the flag on that batch.  Hit rows are in the swapped frame: t_st / t_en are
+ *     positions on the file's query sequence, q_st / q_en on its target, and the row text is a clip of the swapped CIGAR.
  * rb_host_liftover_largest_text: the same for liftover --largest.  win_key [n_win] and inside_key (the key of the empty id "", which a record
  *     read from a file has) are keys below n_keys (n_keys < 2^32 - 1).  The hit rows stay on the device; rb_dev_largest picks one per key,
  *     and only those rows are downloaded, given format items and printed: rows / row_text_off / row_text come back with n_sel entries in

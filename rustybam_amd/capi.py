@@ -425,9 +425,29 @@ class Engine:
         self.L.rb_host_free(out)
         return rows, o
 
-    def swap(self, ops, op_off, strand):
+    def dev_swap(self, view, out_ptr):
+        """rb_dev_swap on device addresses; out_ptr == view.ops swaps every record where it lies.  Enqueues on the context's stream.
+        -> the return code (RB_E_INVALID = -1 for an out_ptr that overlaps the ops without being equal to them): the caller checks it"""
+        return int(self.L.rb_dev_swap(self.ctx, C.byref(view), C.c_void_p(out_ptr)))
+
+    def swap(self, ops, op_off, strand, in_place=False):
         ops, op_off, s = _arr(ops, np.uint32), _arr(op_off, np.uint64), _arr(strand, np.uint8)
         n = len(op_off) - 1
+        if in_place:  # upload, rb_dev_swap with out_ops == ops, download
+            buf = np.concatenate([ops, np.zeros(4, np.uint32)])
+            bufs = [self.dev_alloc(max(a.nbytes, 256)) for a in (buf, op_off, s)]
+            try:
+                for d, a in zip(bufs, (buf, op_off, s)):
+                    if a.nbytes:
+                        self._chk(self.L.rb_dev_upload(self.ctx, C.c_void_p(d), _p(a), C.c_size_t(a.nbytes)), "rb_dev_upload")
+                view = self.batch_view(n, int(op_off[n]) if n else 0, bufs[0], bufs[1], 0, 0, 0, 0, bufs[2], 0)
+                self._chk(self.dev_swap(view, bufs[0]), "rb_dev_swap")
+                self._chk(self.L.rb_dev_download(self.ctx, _p(buf), C.c_void_p(bufs[0]), C.c_size_t(buf.nbytes)), "rb_dev_download")
+            finally:
+                self.sync()
+                for d in bufs:
+                    self.dev_free(d)
+            return buf[:len(ops)]
         out = np.zeros(len(ops) + 4, np.uint32)
         src = np.concatenate([ops, np.zeros(4, np.uint32)])
         self._chk(self.L.rb_host_swap(self.ctx, C.c_uint64(n), _p(src), _p(op_off), _p(s), _p(out)), "rb_host_swap")

@@ -1124,6 +1124,13 @@ extern "C" int rb_dev_swap(rb_ctx *ctx, const rb_batch_view *b, uint32_t *out_op
     p.op_off = b->op_off;
     p.strand = b->strand;
     p.out_ops = out_ops;
+    if (out_ops == b->ops) { // in place
+        HIPCHK(ctx, rb_launch_swap_inplace(&p, ctx->stream));
+        return RB_OK;
+    }
+    // (rb_k_swap reads a record's words while other lanes write them: an output that shares words with the input is only right when it IS the input)
+    if (out_ops < b->ops + b->n_ops && b->ops < out_ops + b->n_ops)
+        return fail(ctx, RB_E_INVALID, "rb_dev_swap: out_ops overlaps the batch's ops without being equal to them (in place: out_ops == batch->ops)");
     HIPCHK(ctx, rb_launch_swap(&p, ctx->stream));
     return RB_OK;
 }
@@ -1643,6 +1650,10 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
                           rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off,
                           uint8_t **row_text, rb_counters *counters, const largest_text *lg = nullptr) {
     if (!ctx || (n_rec && (!cig_off || !cig_end || !cig_status))) return RB_E_INVALID;
+    // liftover --qbed: the wrappers' own bit, taken out before anything reaches rb_dev_liftover
+    const bool qbed = (policy & RB_LIFT_QBED) != 0;
+    policy &= ~RB_LIFT_QBED;
+    if (qbed && (is_break || scan_only)) return fail(ctx, RB_E_INVALID, "RB_LIFT_QBED: only rb_host_liftover_text and rb_host_liftover_largest_text take it");
     if (lg) *lg->declined = 0;
     if (n_rec == 0) { // an empty file: no rows, no text
         if (rows) *rows = nullptr;
@@ -1716,7 +1727,17 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
     rb_reduce_row *d_red = nullptr;
     if ((rc = b.alloc(n_rec, &d_norm))) return rc;
     if (reduce_out && (rc = b.alloc(n_rec, &d_red))) return rc;
-    if ((rc = rb_dev_scan_records(ctx, &b.v, d_red, d_norm))) return rc;
+    if (qbed) {
+        // Paf::from_file's check_integrity (paf.rs:70) is the record's as read: reduce rows first, from the unswapped batch.  Then the ops
+        // are swapped where they lie (the descriptors of the clip index this array), the t and q columns change places, and the scan for
+        // the norm rows -- aligned_pairs' remove_trailing_indels -- sees the swapped record.
+        if (reduce_out && (rc = rb_dev_scan_records(ctx, &b.v, d_red, nullptr))) return rc;
+        if ((rc = rb_dev_swap(ctx, &b.v, d_ops))) return rc;
+        std::swap(b.v.t_st, b.v.q_st), std::swap(b.v.t_en, b.v.q_en);
+        if ((rc = rb_dev_scan_records(ctx, &b.v, nullptr, d_norm))) return rc;
+    } else if ((rc = rb_dev_scan_records(ctx, &b.v, d_red, d_norm))) {
+        return rc;
+    }
     if (norm_out && (rc = rb_dev_download(ctx, norm_out, d_norm, n_rec * sizeof(rb_norm_row)))) return rc;
     if (reduce_out && (rc = rb_dev_download(ctx, reduce_out, d_red, n_rec * sizeof(rb_reduce_row)))) return rc;
     rb_lap("scan_records + rows D2H", tl);

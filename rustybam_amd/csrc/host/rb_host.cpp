@@ -282,6 +282,19 @@ static void panic_on(uint32_t status, const char *what, size_t i) {
     if (status >= RB_ST_PANIC_NOTFOUND) throw Panic(std::string(what) + ": record " + std::to_string(i + 1) + " has status " + std::to_string(status));
 }
 
+// cigar_swap_target_query (paf.rs:1050-1065) on the host: I <-> D, reversed on '-' with an op and its continuation word kept in order
+static void cigar_swap(std::vector<uint32_t> &cig, bool minus) {
+    if (minus) {
+        std::reverse(cig.begin(), cig.end());
+        for (size_t i = 0; i + 1 < cig.size(); i++)
+            if ((cig[i] & 15u) == RB_OP_CONT && (cig[i + 1] & 15u) != RB_OP_CONT) std::swap(cig[i], cig[i + 1]), i++;
+    }
+    for (uint32_t &v : cig) {
+        const uint32_t opc = v & 15u;
+        if (opc == RB_OP_I) v = (v & ~15u) | RB_OP_D;
+        else if (opc == RB_OP_D) v = (v & ~15u) | RB_OP_I;
+    }
+}
 // the record after remove_trailing_indels: id gains _TO.<lead>.<trail> (paf.rs:726-732)
 // the last `count` words of a cigar, last OP first (the order remove_trailing_indels pops them in, paf.rs:704-723); an op and its
 // continuation word stay together
@@ -993,9 +1006,11 @@ struct TextFile {
     std::vector<uint8_t> strand;
     std::vector<uint32_t> contig;
     std::unordered_map<std::string_view, uint32_t> contig_id; // dense ids in order of first appearance (canonical contig order)
+    bool qbed = false; // liftover --qbed: the records are lifted swapped (paf.rs:1068-1094), so a record's contig is its QUERY name
     std::string_view name(size_t off, size_t n) const { return std::string_view(all.data() + off, n); }
     // false = a line needs the general parser (two cg tags)
-    bool load(const std::string &paf_path, const std::pair<uint64_t, uint64_t> *range = nullptr) {
+    bool load(const std::string &paf_path, const std::pair<uint64_t, uint64_t> *range = nullptr, bool qbed_ = false) {
+        qbed = qbed_;
         double tl = now_s();
         all = read_text(paf_path, false, range);
         text_bytes = all.size();
@@ -1042,7 +1057,8 @@ struct TextFile {
             const HeaderOnly &h = recs[i];
             cig_off[i] = h.cg, cig_end[i] = h.cg + h.cg_n;
             t_st[i] = h.t_st, t_en[i] = h.t_en, q_st[i] = h.q_st, q_en[i] = h.q_en, strand[i] = (uint8_t)h.strand;
-            const std::string_view nm = name(h.t_name, h.t_name_n);
+            // (first appearance order of the swapped records' target names is the canonical contig order, liftover.rs:151)
+            const std::string_view nm = qbed ? name(h.q_name, h.q_name_n) : name(h.t_name, h.t_name_n);
             auto it = contig_id.find(nm);
             if (it == contig_id.end()) it = contig_id.emplace(nm, (uint32_t)contig_id.size()).first;
             contig[i] = it->second;
@@ -1072,11 +1088,13 @@ struct TextFile {
             if (red[i].status != RB_ST_OK) throw Panic("check_integrity: record " + std::to_string(i + 1) + " status " + std::to_string(red[i].status));
         return true;
     }
-    // "_TO.<lead>.<trail>" of a record whose end indels were stripped (paf.rs:726-732), parsed from its own text (rare)
+    // "_TO.<lead>.<trail>" of a record whose end indels were stripped (paf.rs:726-732), parsed from its own text (rare); under --qbed the
+    // norm row counts ops of the swapped CIGAR (paf.rs:1050-1065: I <-> D, reversed on '-')
     std::string stripped_suffix(uint32_t r, const rb_norm_row &nr) const {
         if (!(nr.flags & RB_F_STRIPPED)) return std::string();
         std::vector<uint32_t> cig;
         parse_cigar(all.data() + recs[r].cg, recs[r].cg_n, cig);
+        if (qbed) cigar_swap(cig, recs[r].strand == '-');
         std::vector<uint32_t> lead(cig.begin(), cig.begin() + nr.lead_ops);
         return "_TO." + cigar_to_string(lead) + "." + cigar_to_string(popped_trail(cig, nr.trail_ops));
     }
@@ -1128,8 +1146,10 @@ struct TextRows { // results of rb_host_liftover_text / rb_host_break_text (free
     ~TextRows() { rb_host_free(rows), rb_host_free(toff), rb_host_free(text); }
 };
 // `println!("{}", rec)` for every Some(rec): header columns from the file text and the hit rows, CIGAR text from the device
+// qbed: the Display of the swapped record -- the line's target columns in front with the row's q_st / q_en (the hit rows are in the swapped
+// frame), then its query columns with the row's t_st / t_en
 std::vector<std::string> assemble_lines(const TextFile &f, const std::vector<rb_norm_row> &norm, const TextRows &R, const std::vector<Region> *rgns,
-                                        RunMarks *marks = nullptr) {
+                                        RunMarks *marks = nullptr, bool qbed = false) {
     for (uint64_t k = 0; k < R.n_rows; k++)
         if (R.rows[k].status >= RB_ST_PANIC_NOTFOUND) throw Panic("Problem getting index in cigar: record " + std::to_string(R.rows[k].rec + 1));
     const unsigned TO = parallel_chunk_count((size_t)R.n_rows);
@@ -1151,9 +1171,16 @@ std::vector<std::string> assemble_lines(const TextFile &f, const std::vector<rb_
             if (h.status != RB_ST_OK) continue;
             const HeaderOnly &s = f.recs[h.rec];
             if (marks && ((*marks)[t].empty() || (*marks)[t].back().first != f.contig[h.rec])) (*marks)[t].emplace_back(f.contig[h.rec], o.size());
-            o.append(f.all.data() + s.q_name, s.q_name_n); o += '\t'; num(s.q_len); o += '\t'; num(h.q_st); o += '\t'; num(h.q_en); o += '\t';
-            o += s.strand; o += '\t'; o.append(f.all.data() + s.t_name, s.t_name_n); o += '\t'; num(s.t_len); o += '\t'; num(h.t_st); o += '\t';
-            num(h.t_en); o += '\t'; num(h.nmatch); o += '\t'; num(h.aln_len); o += '\t'; num(s.mapq); o += "\tid:Z:";
+            if (qbed) {
+                o.append(f.all.data() + s.t_name, s.t_name_n); o += '\t'; num(s.t_len); o += '\t'; num(h.q_st); o += '\t'; num(h.q_en); o += '\t';
+                o += s.strand; o += '\t'; o.append(f.all.data() + s.q_name, s.q_name_n); o += '\t'; num(s.q_len); o += '\t'; num(h.t_st); o += '\t';
+                num(h.t_en);
+            } else {
+                o.append(f.all.data() + s.q_name, s.q_name_n); o += '\t'; num(s.q_len); o += '\t'; num(h.q_st); o += '\t'; num(h.q_en); o += '\t';
+                o += s.strand; o += '\t'; o.append(f.all.data() + s.t_name, s.t_name_n); o += '\t'; num(s.t_len); o += '\t'; num(h.t_st); o += '\t';
+                num(h.t_en);
+            }
+            o += '\t'; num(h.nmatch); o += '\t'; num(h.aln_len); o += '\t'; num(s.mapq); o += "\tid:Z:";
             if (rgns && !(h.flags & RB_HIT_INSIDE)) o += (*rgns)[h.win].id;
             else o += f.stripped_suffix(h.rec, norm[h.rec]); // (a record read from a file has an empty id of its own)
             o += "\tcg:Z:";
@@ -1166,11 +1193,14 @@ std::vector<std::string> assemble_lines(const TextFile &f, const std::vector<rb_
 } // namespace
 
 // largest: main.rs:200-208 on the device (rb_host_liftover_largest_text) -- the rows that come back are the one record per id, in id order
+// qbed: main.rs:186-214 with --qbed (liftover.rs:139-148) -- RB_LIFT_QBED: the wrapper swaps the parsed CIGARs in place on the device and
+// lifts the swapped records; contigs are the records' query names, and the lines are the swapped records' (assemble_lines)
 static bool lift_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text, TextRuns *runs,
-                           bool largest) {
+                           bool largest, bool qbed) {
     // (one-shot command: the gigabytes behind these two are left to the end of the process instead of being unmapped piece by piece)
     TextFile &f = *new TextFile;
-    if (!f.load(paf_path)) return false; // the caller takes the general path
+    if (!f.load(paf_path, nullptr, qbed)) return false; // the caller takes the general path
+    const int policy = eng.bsearch_policy | (qbed ? RB_LIFT_QBED : 0);
     double tl = now_s();
     const size_t n = f.recs.size();
     if (runs) { // the records' contigs by first appearance (before windows on other names get ids of their own below)
@@ -1201,33 +1231,34 @@ static bool lift_file_text(Engine &eng, const std::string &paf_path, const std::
         for (size_t i = 0; i < rgns.size(); i++) win_key[i] = (uint32_t)(std::lower_bound(ids.begin(), ids.end(), std::string_view(rgns[i].id)) - ids.begin());
         eng.check(rb_host_liftover_largest_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(),
                                                 f.t_st.data(), f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(),
-                                                w_contig.data(), w_st.data(), w_en.data(), eng.bsearch_policy, cig_status.data(), red.data(),
+                                                w_contig.data(), w_st.data(), w_en.data(), policy, cig_status.data(), red.data(),
                                                 norm.data(), &R.rows, &R.n_rows, &R.toff, &R.text, &cnt, win_key.data(), ids.size(), 0u, &declined),
                   "rb_host_liftover_largest_text");
         lap("rb_host_liftover_largest_text", tl);
     } else {
         eng.check(rb_host_liftover_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
                                         f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(), w_contig.data(),
-                                        w_st.data(), w_en.data(), eng.bsearch_policy, cig_status.data(), red.data(), norm.data(), &R.rows,
+                                        w_st.data(), w_en.data(), policy, cig_status.data(), red.data(), norm.data(), &R.rows,
                                         &R.n_rows, &R.toff, &R.text, &cnt),
                   "rb_host_liftover_text");
         lap("rb_host_liftover_text", tl);
     }
-    if (!f.check_loaded(cig_status, red)) return false;
+    if (!f.check_loaded(cig_status, red)) return false; // (qbed: the reduce rows are the records' as read, the norm rows the swapped records')
     for (size_t i = 0; i < n; i++) panic_on(norm[i].status, "aligned_pairs", i); // liftover.rs:119-121
     if (declined) return false; // a stripped record inside a window, or a hit row that panics: the record route knows its id / replays the panic
     RunMarks marks;
-    out_text = assemble_lines(f, norm, R, &rgns, runs ? &marks : nullptr);
+    out_text = assemble_lines(f, norm, R, &rgns, runs ? &marks : nullptr, qbed);
     if (runs) marks_to_runs(marks, out_text, *runs);
     lap("assemble lines", tl);
     return true;
 }
 
-bool liftover_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text, TextRuns *runs) {
-    return lift_file_text(eng, paf_path, rgns, out_text, runs, false);
+bool liftover_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text, TextRuns *runs,
+                        bool qbed) {
+    return lift_file_text(eng, paf_path, rgns, out_text, runs, false, qbed);
 }
-bool liftover_largest_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text) {
-    return lift_file_text(eng, paf_path, rgns, out_text, nullptr, true);
+bool liftover_largest_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text, bool qbed) {
+    return lift_file_text(eng, paf_path, rgns, out_text, nullptr, true, qbed);
 }
 
 // main.rs:271-281, text in -> text out
@@ -1684,15 +1715,14 @@ bool invert_file_text(Engine &eng, const std::string &paf_path, std::vector<std:
     }
     if (!f.check_loaded(cig_status, red)) return false; // the panics of Paf::from_file, in its order
     lap("  text -> ops, scan (device)", tl);
-    uint32_t *d_swapped = (uint32_t *)D.take(eng, (size_t)v.n_ops * 4 + 256);
-    eng.check(rb_dev_swap(ctx, &v, d_swapped), "rb_dev_swap");
+    eng.check(rb_dev_swap(ctx, &v, d_ops), "rb_dev_swap"); // in place: the scan above was the last reader of the CIGARs as read
     std::vector<uint32_t> count(n);
     for (size_t i = 0; i < n; i++) count[i] = (uint32_t)(op_off[i + 1] - op_off[i]);
     const uint32_t *d_count = (const uint32_t *)up(count.data(), n * 4);
     uint64_t *d_toff = (uint64_t *)D.take(eng, (n + 2) * 8);
     const uint64_t text_cap = 11 * v.n_ops + 16;
     uint8_t *d_out = (uint8_t *)D.take(eng, text_cap);
-    eng.check(rb_dev_format_cigars(ctx, d_swapped, nullptr, n, d_opoff, d_count, nullptr, nullptr, d_toff, d_out, text_cap, d_scr), "rb_dev_format_cigars");
+    eng.check(rb_dev_format_cigars(ctx, d_ops, nullptr, n, d_opoff, d_count, nullptr, nullptr, d_toff, d_out, text_cap, d_scr), "rb_dev_format_cigars");
     std::vector<uint64_t> &toff = *new std::vector<uint64_t>(n + 1);
     eng.check(rb_dev_download(ctx, toff.data(), d_toff, (n + 1) * 8), "rb_dev_download");
     std::vector<uint8_t> &text = *new std::vector<uint8_t>((size_t)toff[n] + 1);

@@ -102,14 +102,17 @@ std::vector<PafRecord> trim_paf_by_rgns(Engine &eng, const std::vector<Region> &
 // the same, printed: every Some(rec) as `println!("{}", rec)` would, without materialising the records
 std::vector<std::string> trim_paf_by_rgns_text(Engine &eng, const std::vector<Region> &rgns, const std::vector<PafRecord> &paf_recs, bool invert_query,
                                                TextRuns *runs = nullptr);
-// main.rs:186-214 without --qbed / --largest, text in -> text out: the CIGAR text is parsed and printed on the device
-// (rb_host_liftover_text); false = the file needs the general path (a line with two cg tags), nothing was produced
+// main.rs:186-214 without --largest, text in -> text out: the CIGAR text is parsed and printed on the device
+// (rb_host_liftover_text); false = the file needs the general path (a line with two cg tags), nothing was produced.
+// qbed (liftover.rs:139-148): the records are swapped first -- the parsed CIGARs in place on the device (RB_LIFT_QBED), the columns when
+// the lines are put together; contigs (runs) are then the records' query names
 bool liftover_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text,
-                        TextRuns *runs = nullptr);
-// main.rs:186-214 with --largest (no --qbed), text in -> text out: the hit rows never leave the device, rb_dev_largest keeps the last record of
+                        TextRuns *runs = nullptr, bool qbed = false);
+// main.rs:186-214 with --largest, text in -> text out: the hit rows never leave the device, rb_dev_largest keeps the last record of
 // largest target span per id (main.rs:200-208) and only those records are printed, in id order (rb_host_liftover_largest_text); false = take
 // the record route (two cg tags, a stripped record that lies inside a window, a hit row that panics), nothing was produced
-bool liftover_largest_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text);
+bool liftover_largest_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text,
+                                bool qbed = false);
 // the same two routes as a pipeline over chunks of a big plain file (a few host threads, each with its own context on `device`):
 // the sink receives the chunks' outputs in file order while later chunks are still being read / clipped / printed.  A chunk's text
 // is contig-major within the chunk (runs); false = not applicable or a line needs the general parser (pipeline_started(): the

@@ -1002,10 +1002,10 @@ int main(int argc, char **argv) {
                 lap("liftover (text to text, pipelined)", tl);
                 done(0);
             }
-            if (!largest && !qbed && text_path) { // text in -> text out, CIGAR text handled on the device
+            if (!largest && text_path) { // text in -> text out, CIGAR text handled on the device (--qbed: swapped there too)
                 std::vector<std::string> text;
-                if (rb::liftover_file_text(eng, paf_path, rgns, text, g_worker.on ? &runs : nullptr)) {
-                    lap("liftover (text to text)", tl);
+                if (rb::liftover_file_text(eng, paf_path, rgns, text, g_worker.on ? &runs : nullptr, qbed)) {
+                    lap(qbed ? "liftover --qbed (text to text)" : "liftover (text to text)", tl);
                     Output o = with_runs(text);
                     emit(o);
                     fflush(stdout);
@@ -1013,10 +1013,10 @@ int main(int argc, char **argv) {
                     done(0);
                 }
             }
-            if (largest && !qbed && text_path && !g_worker.on) { // the same with main.rs:200-208 on the device: only one record per id is printed
+            if (largest && text_path && !g_worker.on) { // the same with main.rs:200-208 on the device: only one record per id is printed
                 std::vector<std::string> text;
-                if (rb::liftover_largest_file_text(eng, paf_path, rgns, text)) {
-                    lap("liftover --largest (text to text)", tl);
+                if (rb::liftover_largest_file_text(eng, paf_path, rgns, text, qbed)) {
+                    lap(qbed ? "liftover --qbed --largest (text to text)" : "liftover --largest (text to text)", tl);
                     emit(text);
                     fflush(stdout);
                     lap("write", tl);

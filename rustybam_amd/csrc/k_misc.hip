@@ -243,6 +243,10 @@ extern "C" hipError_t rb_launch_break_place(const rb_break_params *p, hipStream_
 // ------------------------------------------------------------------------------------------------
 // invert: cigar_swap_target_query (paf.rs:1050-1065): I <-> D, reversed when the strand is '-'
 // ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t rb_swap_flip(uint32_t v) { // I <-> D
+    const uint32_t opc = rb_opc(v);
+    return opc == RB_OP_I ? (v & ~15u) | RB_OP_D : opc == RB_OP_D ? (v & ~15u) | RB_OP_I : v;
+}
 __global__ __launch_bounds__(256) void rb_k_swap(rb_swap_params p) {
     const uint64_t wave = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (wave >= p.n_rec) return;
@@ -258,15 +262,124 @@ __global__ __launch_bounds__(256) void rb_k_swap(rb_swap_params p) {
                 v = p.ops[o0 + src + 1];
             }
         }
-        const uint32_t opc = rb_opc(v);
-        if (opc == RB_OP_I) v = (v & ~15u) | RB_OP_D;
-        else if (opc == RB_OP_D) v = (v & ~15u) | RB_OP_I;
-        p.out_ops[o0 + j] = v;
+        p.out_ops[o0 + j] = rb_swap_flip(v);
     }
 }
 extern "C" hipError_t rb_launch_swap(const rb_swap_params *p, hipStream_t stream) {
     if (p->n_rec == 0) return hipSuccess;
     hipLaunchKernelGGL(rb_k_swap, dim3((unsigned)((p->n_rec + 3) / 4)), dim3(256), 0, stream, *p);
+    return hipGetLastError();
+}
+
+// The same where the ops lie (out_ops == ops; p.out_ops is not read).  One wavefront per record.
+// '+': every word is rewritten with I <-> D.
+// '-': R[j] = w[n - 1 - j] is the plain reversal; the result is R with every (continuation, owner) pair put back in order, which is what
+//      rb_k_swap reads at j - 1 .. j + 1 of its source:  out[j] = R[j] is a continuation ? (R[j + 1] an owner ? R[j + 1] : R[j])
+//                                                                                        : (R[j - 1] a continuation ? R[j - 1] : R[j]).
+//      The record is reversed from its two ends towards the middle.  A turn takes the 256 words at [a, a + 256) and their mirror
+//      [n - a - 256, n - a): lane l loads words a + 4l .. + 3 and their mirror n - a - 4l - 4 .. + 3 (16 bytes each: one global_load_dwordx4
+//      where the address is 16-byte aligned, and the same instruction on a 4-byte aligned address where the record's start is not), so the
+//      lane that loaded a word is the lane that stores its mirror image and the words themselves never change lanes.  What crosses lanes is
+//      the one neighbour R[j - 1] / R[j + 1] at each end of a lane's four words (two shuffles per side).  At the ends of the TURN that
+//      neighbour lies in another turn's words:
+//        inner side: words no turn has stored to yet -- loaded with the turn's other loads;
+//        outer side: words the turn before has overwritten -- the wave carries the two it needs (the last word of the front block, the
+//                    first of the back block) in registers from that turn.  Nothing is read from memory after it has been written.
+//      Every load of a turn has returned (s_waitcnt vmcnt(0)) before its first store is issued.  What is left in the middle, fewer than
+//      512 words, is one last turn of the same shape in dwords: lane l holds R[a + l + 64 i], i < 8.
+// As rb_k_swap (and the ABI: RB_OP_CONT "always directly behind its owner"), the rule knows ONE continuation word per owner: of two
+// continuation words in a row only the one next to the owner changes places with it, and a continuation word at the record's start, which
+// has no owner, stays a continuation word where the reversal puts it.  Neither is a valid CIGAR; both kernels treat them alike.
+struct __attribute__((packed, aligned(4))) rb_swap_w4 {
+    uint32_t x, y, z, w;
+};
+// out[j] from R[j - 1], R[j], R[j + 1]
+__device__ __forceinline__ uint32_t rb_swap_pick(uint32_t prev, bool has_prev, uint32_t v, uint32_t next, bool has_next) {
+    if (rb_opc(v) == RB_OP_CONT) {
+        if (has_next && rb_opc(next) != RB_OP_CONT) v = next;
+    } else if (has_prev && rb_opc(prev) == RB_OP_CONT) {
+        v = prev;
+    }
+    return rb_swap_flip(v);
+}
+__global__ __launch_bounds__(256) void rb_k_swap_inplace(rb_swap_params p) {
+    const uint64_t wave = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (wave >= p.n_rec) return;
+    const uint64_t o0 = p.op_off[wave], n = p.op_off[wave + 1] - o0;
+    uint32_t *w = const_cast<uint32_t *>(p.ops) + o0;
+    const int lane = rb_lane();
+    if (p.strand[wave] != (uint8_t)'-') {
+        uint64_t j = 0;
+        for (; j + 256 <= n; j += 256) {
+            rb_swap_w4 *q = reinterpret_cast<rb_swap_w4 *>(w + j + 4 * lane);
+            rb_swap_w4 v = *q;
+            v.x = rb_swap_flip(v.x), v.y = rb_swap_flip(v.y), v.z = rb_swap_flip(v.z), v.w = rb_swap_flip(v.w);
+            *q = v;
+        }
+        for (j += lane; j < n; j += 64) w[j] = rb_swap_flip(w[j]);
+        return;
+    }
+    uint64_t a = 0;             // words done at each end
+    uint32_t cf = 0, cb = 0;    // as they were before the turn in front of this one stored: w[a - 1], w[n - a]
+    for (; n - 2 * a >= 512; a += 256) {
+        rb_swap_w4 *fp = reinterpret_cast<rb_swap_w4 *>(w + a + 4 * lane), *bp = reinterpret_cast<rb_swap_w4 *>(w + (n - a - 4 * lane - 4));
+        const rb_swap_w4 f = *fp, b = *bp;
+        // the inner neighbours (n - 2a >= 512: both lie in [a + 255, n - a - 256], which this turn has not stored to yet)
+        const uint32_t f_in = lane == 63 ? w[a + 256] : 0u, b_in = lane == 63 ? w[n - a - 257] : 0u;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const bool outer = lane > 0 || a > 0; // the word beyond the outer end of the lane's four exists
+        // front block: R[a + 4l + k] = w[n - 1 - a - 4l - k] = b.w, b.z, b.y, b.x
+        uint32_t prev = __shfl_up(b.x, 1, 64), next = __shfl_down(b.w, 1, 64);
+        if (lane == 0) prev = cb;
+        if (lane == 63) next = b_in;
+        rb_swap_w4 o;
+        o.x = rb_swap_pick(prev, outer, b.w, b.z, true);
+        o.y = rb_swap_pick(b.w, true, b.z, b.y, true);
+        o.z = rb_swap_pick(b.z, true, b.y, b.x, true);
+        o.w = rb_swap_pick(b.y, true, b.x, next, true);
+        // back block: R[n - a - 4l - 4 + k] = w[a + 4l + 3 - k] = f.w, f.z, f.y, f.x; R beyond its top is w[a + 4l - 1]
+        prev = __shfl_down(f.x, 1, 64), next = __shfl_up(f.w, 1, 64);
+        if (lane == 63) prev = f_in;
+        if (lane == 0) next = cf;
+        rb_swap_w4 m;
+        m.x = rb_swap_pick(prev, true, f.w, f.z, true);
+        m.y = rb_swap_pick(f.w, true, f.z, f.y, true);
+        m.z = rb_swap_pick(f.z, true, f.y, f.x, true);
+        m.w = rb_swap_pick(f.y, true, f.x, next, outer);
+        cf = rb_readlane<uint32_t>(f.w, 63), cb = rb_readlane<uint32_t>(b.x, 63);
+        *fp = o;
+        *bp = m;
+    }
+    // the middle: m < 512 words at [a, a + m), reversed onto themselves
+    const uint32_t m = (uint32_t)(n - 2 * a);
+    uint32_t v[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t q = (uint32_t)lane + 64u * i;
+        v[i] = q < m ? w[a + (m - 1 - q)] : 0u;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    uint32_t out[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t q = (uint32_t)lane + 64u * i;
+        uint32_t prev = __shfl_up(v[i], 1, 64), next = __shfl_down(v[i], 1, 64);
+        const uint32_t wrap_prev = i > 0 ? rb_readlane<uint32_t>(v[i > 0 ? i - 1 : 0], 63) : cb;
+        const uint32_t wrap_next = i < 7 ? rb_readlane<uint32_t>(v[i < 7 ? i + 1 : 7], 0) : 0u;
+        if (lane == 0) prev = wrap_prev;
+        if (lane == 63) next = wrap_next;
+        if (q + 1 == m) next = cf; // R[a + m] = w[a - 1]
+        out[i] = rb_swap_pick(prev, q > 0 || a > 0, v[i], next, q + 1 < m || a > 0);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t q = (uint32_t)lane + 64u * i;
+        if (q < m) w[a + q] = out[i];
+    }
+}
+extern "C" hipError_t rb_launch_swap_inplace(const rb_swap_params *p, hipStream_t stream) {
+    if (p->n_rec == 0) return hipSuccess;
+    hipLaunchKernelGGL(rb_k_swap_inplace, dim3((unsigned)((p->n_rec + 3) / 4)), dim3(256), 0, stream, *p);
     return hipGetLastError();
 }
 

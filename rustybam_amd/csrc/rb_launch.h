@@ -68,7 +68,7 @@ struct rb_break_params {
     const uint32_t *list;
     const unsigned long long *n_list;
 };
-struct rb_swap_params {
+struct rb_swap_params { // rb_k_swap: ops -> out_ops (disjoint arrays); rb_k_swap_inplace: ops rewritten where they lie, out_ops not read
     uint64_t n_rec;
     const uint32_t *ops;
     const uint64_t *op_off;
@@ -95,6 +95,7 @@ struct rb_compact_params {
 extern "C" hipError_t rb_launch_break_pieces(const rb_break_params *p, hipStream_t stream);
 extern "C" hipError_t rb_launch_break_place(const rb_break_params *p, hipStream_t stream);
 extern "C" hipError_t rb_launch_swap(const rb_swap_params *p, hipStream_t stream);
+extern "C" hipError_t rb_launch_swap_inplace(const rb_swap_params *p, hipStream_t stream);
 extern "C" hipError_t rb_launch_starts_check(const uint64_t *op_off, const rb_norm_row *norm, uint64_t n_rec, uint64_t n_ops, unsigned long long *bad,
                                              hipStream_t stream);
 extern "C" hipError_t rb_launch_synth(uint64_t seed, uint64_t first_record, uint64_t n_rec, const uint64_t *op_off, uint32_t *ops, hipStream_t stream);
