@@ -183,7 +183,8 @@ typedef struct rb_pair_row { /* trim-paf: one (left, right) overlap pair, 128 by
 } rb_pair_row;
 
 typedef struct rb_counters { /* device-written job summary, 64 bytes */
-    uint64_t n_hits;             /* rows the job wants to write                                  */
+    uint64_t n_hits;             /* rows the job wants to write: EXACT also when the call overflowed (it is the total of the hit scan,
+                                    which does not depend on rows_cap or out_cap) -- except with brk_scratch_short, see there */
     uint64_t out_ops_needed;     /* upper bound of out_ops[] capacity that makes the job fit      */
     uint64_t out_ops_used;       /* highest op index written + 1                                  */
     uint64_t n_generic;          /* hits routed to the generic kernel                             */
@@ -191,7 +192,10 @@ typedef struct rb_counters { /* device-written job summary, 64 bytes */
     uint32_t phase[5];           /* diagnostics (debug_skip & 32): shader-clock sums per phase of the clip kernel, units of 16 cycles;
                                     without debug_skip: phase[3] = tiles of short records the call ran (0: none), phase[4] = records of
                                     those tiles that the tile kernel handed back to the per-record kernel (informational) */
-    uint32_t brk_scratch_short;  /* RB_BREAK_ONE_WALK only: != 0: a scratch-row cursor ran out before the rows did; n_hits then asks for more */
+    uint32_t brk_scratch_short;  /* RB_BREAK_ONE_WALK only: != 0: a scratch-row cursor ran out before the rows did (the scratch rows are shared out
+                                    evenly among up to 256 cursors, the records are not); overflow is set, and n_hits is then NOT the row count but a
+                                    rows_cap to try next -- above both the true count and the rows_cap of this call, a quarter and 1024 more each time.
+                                    A caller that follows it gets there in a few calls (rb_host_break allows itself six) */
     uint32_t redo_two_walk;      /* always 0: kept for the layout (RB_BREAK_ONE_WALK declines records one by one inside the call) */
 } rb_counters;
 
@@ -322,7 +326,16 @@ uint64_t rb_plan_out_capacity(const rb_plan *plan, int for_break);
  * t_en > st && t_st < en, in canonical order, writes one rb_hit_row and the clipped cigar.
  *   rows      [rows_cap]      out_ops [out_cap]      counters [1]      workspace [rb_plan_workspace_bytes]
  * On capacity overflow counters->overflow != 0 and counters say what is needed; the caller
- * enlarges and calls again (the host wrapper below does that). */
+ * enlarges and calls again (the host wrapper below does that).  In full (tests/test_gpu_capacity.py):
+ *   - the call returns RB_OK all the same, and writes nothing at or behind rows[rows_cap], out_ops[out_cap] and the end of the workspace:
+ *     no slack is needed behind any of the three (rows_cap >= 1; the workspace is sized for the rows_cap of the call);
+ *   - the rows and clips an overflowed call did write are incomplete and not specified;
+ *   - n_hits is the exact number of rows, and a call with rows_cap = max(rows_cap, n_hits) and out_cap = max(out_cap, out_ops_needed),
+ *     nothing added, does not overflow -- one-walk break-paf apart, which may ask again (rb_counters.brk_scratch_short);
+ *   - out_ops_needed is an upper bound, not the least capacity that works (a call may fit into less): the slots the window lists ask
+ *     for, and every arena behind them as large as the fullest one got, plus 1024 ops each -- clips without a slot are dealt to the
+ *     arenas in the order they turn up, which may differ a little from call to call, and that room takes it up;
+ *   - RB_LIFT_DESCRIPTORS: an out_cap below 4 * rows_cap + 1024 is refused with RB_E_CAPACITY before anything is written or enqueued. */
 int rb_dev_liftover(rb_ctx *ctx, const rb_plan *plan, const rb_batch_view *batch, const rb_norm_row *norm_rows,
                     int bsearch_policy, void *workspace, rb_hit_row *rows, uint64_t rows_cap, uint32_t *out_ops,
                     uint64_t out_cap, rb_counters *counters);
@@ -456,14 +469,22 @@ void rb_host_free(void *p);
  *     status    [n_rec] OUT  RB_TEXT_OK / RB_TEXT_BAD (the reference panics: "Unable to parse cigar string.") /
  *               RB_TEXT_TOO_LONG (a length >= 2^28 cannot be packed; the reference would go on)
  *     scratch   rb_text_scratch_bytes(n_rec) bytes
+ *     TRUNCATION: the call returns RB_OK whatever ops_cap is, and op_off and status are exact whatever it is: the caller detects a
+ *               short ops[] by op_off[n_rec] > ops_cap.  Nothing is written at or behind ops[ops_cap]; ops[0 .. ops_cap) are then the
+ *               first ops_cap ops of the full result.
  * rb_dev_format_cigars  <- impl Display for CigarString inside impl Display for PafRecord   paf.rs:923-944
  *     item i prints ops[first[i] .. first[i] + count[i]) as <len><op>...; first_len / last_len (arrays or NULL,
  *     0 = keep) replace the length of the first / last op -- the clip descriptors of RB_LIFT_DESCRIPTORS:
  *     {first kept op, op count, first length, last length}; a one-op item with both prints first + last - len.
  *     ops_alt   optional second source array: an item whose first[] has bit 63 set takes its ops from ops_alt[]
  *               (clips the generic kernel copied out live in out_ops[], descriptor clips point into the batch)
- *     text_off  [n_items + 1] OUT exclusive prefix of bytes;  text OUT (NULL: sizes only), capacity text_cap
+ *     text_off  [n_items + 1] OUT exclusive prefix of bytes;  text OUT (NULL: sizes only; 16-byte aligned), capacity text_cap
  *               (11 bytes per op suffice)
+ *     TRUNCATION: the call returns RB_OK whatever text_cap is, and text_off is exact whatever it is: the caller detects a short text[]
+ *               by text_off[n_items] > text_cap.  Nothing is written at or behind text[text_cap].  Below it every item that ends at or
+ *               in front of the last 16-byte boundary <= text_cap is printed whole; of the other items any byte may be missing (text is
+ *               stored in steps of up to 255 ops, and a step that would end behind text_cap is left out whole), and a byte that is
+ *               there is the right one.  Nothing else about the content is specified (tests/test_gpu_capacity.py).
  * rb_host_liftover_text: liftover from CIGAR text to CIGAR text.  text holds the records' `cg:Z:` values at
  *     [cig_off[r], cig_end[r]); they are parsed on the device (cig_status[r] = RB_TEXT_*; if any is not OK nothing else
  *     is computed), scanned (reduce_out / norm_out, either may be NULL), lifted over the windows in descriptor mode, and the

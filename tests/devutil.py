@@ -1,5 +1,7 @@
 """Device-pointer level plumbing for the -m gpu tests: a batch resident in HBM (torch tensors), rb_dev_liftover / rb_dev_break
 with the output-sizing loop, rb_dev_digest_rows.  Torch is memory and streams only; every compute call goes through the C ABI."""
+import ctypes as C
+
 import numpy as np
 
 import rustybam_amd
@@ -81,18 +83,13 @@ class DevBatch:
             out_cap = max(out_cap, 4 * rows_cap + 65536)
         try:
             for _ in range(8):
-                ws = torch.empty(eng.plan_workspace_bytes(plan, rows_cap), dtype=torch.uint8, device=dev)
-                rows = torch.full(((rows_cap + 1) * 64,), 0xEE, dtype=torch.uint8, device=dev)
-                out = torch.empty(out_cap + 64, dtype=torch.int32, device=dev)
-                torch.cuda.synchronize()
-                if max_size is not None:
-                    eng.dev_break(plan, self.view, self.d_norm.data_ptr(), max_size, policy, ws.data_ptr(), rows.data_ptr(), rows_cap, out.data_ptr(),
-                                  out_cap, self.d_cnt.data_ptr())
-                else:
-                    eng.dev_liftover(plan, self.view, self.d_norm.data_ptr(), policy, ws.data_ptr(), rows.data_ptr(), rows_cap, out.data_ptr(), out_cap,
-                                     self.d_cnt.data_ptr())
-                torch.cuda.synchronize()
-                cnt = self.d_cnt.cpu().numpy().view(rustybam_amd.COUNTERS_DT)[0].copy()
+                # one call with a row and 64 ops of room behind what it is told it has: nothing may touch them, nor what lies behind the workspace
+                o = self.run_once(windows, policy, max_size, rows_cap, out_cap, alloc_rows=rows_cap + 1, alloc_out=out_cap + 64, plan=plan, fill_out=False, scan=False)
+                eng._chk(o.rc, "rb_dev_break" if max_size is not None else "rb_dev_liftover")
+                assert o.rows_tail_ok, f"a row was written at or behind rows[rows_cap = {rows_cap}]"
+                assert o.out_tail_ok, f"an op was written at or behind out_ops[out_cap = {out_cap}]"
+                assert o.ws_tail_ok, "bytes behind the workspace were written"
+                rows, out, ws, cnt = o.rows, o.out, o.ws, o.cnt
                 if cnt["redo_two_walk"]:  # RB_BREAK_ONE_WALK declined the batch: the caller decides what to do about it
                     self.last = (rows, out, ws)
                     return rows[:0].view(torch.int32).view(0, 16), out, cnt
@@ -104,10 +101,61 @@ class DevBatch:
                 out_cap = max(out_cap * 2, int(int(cnt["out_ops_needed"]) * 1.25) + 4096)
                 if policy & rustybam_amd.LIFT_DESCRIPTORS:
                     out_cap = max(out_cap, 4 * rows_cap + 65536)
-                del ws, rows, out
+                del ws, rows, out, o
             raise AssertionError("could not size the outputs")
         finally:
             eng.plan_destroy(plan)
+
+    def run_once(self, windows, policy, max_size, rows_cap, out_cap, alloc_rows=None, alloc_out=None, plan=None, fill_out=True, scan=True):
+        """Exactly ONE rb_dev_liftover (max_size None) / rb_dev_break call that is TOLD rows_cap rows and out_cap ops, on buffers that are
+        larger than that and hold a sentinel: rows = alloc_rows * 64 bytes of 0xEE (default rows_cap + 1 rows), out = alloc_out words of
+        0xEEEEEEEE (default out_cap + 64), the workspace rb_plan_workspace_bytes(plan, rows_cap) bytes with at least 4096 bytes of 0xEE behind
+        them (more when alloc_rows asks for a workspace as large as the one a call with that many rows takes).  A store the call makes
+        past what it was told lands in memory the caller owns and shows in the three flags of the result:
+          rows_tail_ok  every byte of rows at or behind rows_cap * 64 still holds the sentinel
+          out_tail_ok   every word of out at or behind out_cap still does
+          ws_tail_ok    every byte behind the workspace still does
+        Also: rc (the call's return value, not raised), cnt (the counters as the call left them; what d_cnt held before if rc != 0), rows /
+        out / ws (the tensors), rows_cap, out_cap, ws_bytes.  fill_out=False fills only the tail of out (the sizing loop of run(): cheap
+        on a large batch); scan=False: the norm rows are already there.  No retry, no assertion: the caller looks."""
+        from types import SimpleNamespace
+        torch, eng, dev = self.torch, self.eng, self.dev
+        rows_cap, out_cap = int(rows_cap), int(out_cap)
+        alloc_rows = max(int(alloc_rows) if alloc_rows is not None else 0, rows_cap + 1)
+        alloc_out = max(int(alloc_out) if alloc_out is not None else 0, out_cap + 64)
+        if scan and not (policy & rustybam_amd.LIFT_FUSED_SCAN) and not getattr(self, "norm_ready", False):
+            torch.cuda.synchronize()
+            eng.dev_scan_records(self.view, 0, self.d_norm.data_ptr())
+        own_plan = plan is None
+        if own_plan:
+            plan = eng.plan_create(self.op_off_host, self.contig_host, *(windows if windows is not None else (None, None, None)))
+        try:
+            ws_bytes = eng.plan_workspace_bytes(plan, rows_cap)
+            ws = torch.empty(max(ws_bytes, eng.plan_workspace_bytes(plan, alloc_rows)) + 4096, dtype=torch.uint8, device=dev)
+            ws[ws_bytes:] = 0xEE
+            rows = torch.full((alloc_rows * 64,), 0xEE, dtype=torch.uint8, device=dev)
+            if fill_out:
+                out = torch.full((alloc_out,), -0x11111112, dtype=torch.int32, device=dev)  # 0xEEEEEEEE
+            else:
+                out = torch.empty(alloc_out, dtype=torch.int32, device=dev)
+                out[out_cap:] = -0x11111112
+            torch.cuda.synchronize()  # the engine runs on its own stream: torch's fills must have landed before it starts
+            L, cp = eng.L, C.c_void_p
+            if max_size is not None:
+                rc = L.rb_dev_break(eng.ctx, plan, C.byref(self.view), cp(self.d_norm.data_ptr()), C.c_uint32(max_size), C.c_int(policy), cp(ws.data_ptr()),
+                                    cp(rows.data_ptr()), C.c_uint64(rows_cap), cp(out.data_ptr()), C.c_uint64(out_cap), cp(self.d_cnt.data_ptr()))
+            else:
+                rc = L.rb_dev_liftover(eng.ctx, plan, C.byref(self.view), cp(self.d_norm.data_ptr()), C.c_int(policy), cp(ws.data_ptr()), cp(rows.data_ptr()),
+                                       C.c_uint64(rows_cap), cp(out.data_ptr()), C.c_uint64(out_cap), cp(self.d_cnt.data_ptr()))
+            torch.cuda.synchronize()
+            cnt = self.d_cnt.cpu().numpy().view(rustybam_amd.COUNTERS_DT)[0].copy()
+            return SimpleNamespace(rc=int(rc), cnt=cnt, rows=rows, out=out, ws=ws, rows_cap=rows_cap, out_cap=out_cap, ws_bytes=ws_bytes,
+                                   rows_tail_ok=bool((rows[rows_cap * 64:] == 0xEE).all().item()),
+                                   out_tail_ok=bool((out[out_cap:] == -0x11111112).all().item()),
+                                   ws_tail_ok=bool((ws[ws_bytes:] == 0xEE).all().item()))
+        finally:
+            if own_plan:
+                eng.plan_destroy(plan)
 
     def digest(self, rows, out, row_base=0, rec_base=0):
         torch = self.torch
