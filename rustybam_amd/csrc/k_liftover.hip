@@ -9,11 +9,11 @@
 //   rb_k_scan_*         exclusive scan of the counts -> first row of every record (canonical order)
 //   rb_k_make_jobs      one thread per schedule slot: a 64-byte job descriptor, so that a wave starts on its record
 //                       after ONE load instead of a chain of dependent ones
-//   rb_k_liftover_stream  ONE WAVEFRONT PER RECORD (its body: rb_stream.h).  The record's packed ops stream from HBM once (32 contiguous
-//                       bytes per lane, 2 KiB per step, two steps in flight in a register ring the compiler cannot
-//                       see); per lane the reference / query / unit lengths of 8 ops are summed (op class -> mask
-//                       with one v_bfe_i32), three 6-step DPP prefix scans give the running offsets, every
-//                       lane leaves a checkpoint in LDS; window boundaries are resolved lane-parallel against
+//   rb_k_liftover_stream  ONE WAVEFRONT PER RECORD (its body: rb_stream.h).  The record's packed ops stream from HBM once (2 KiB per
+//                       step, lane l the 16-byte groups l and l + 64 of it, two steps in flight in a register ring the compiler
+//                       cannot see); per lane the reference / query / unit lengths of each group's 4 ops are summed (op class ->
+//                       mask with one v_bfe_i32), 6-step DPP prefix scans give the running offsets, every second or
+//                       fourth lane leaves a checkpoint for each half of the step in LDS; window boundaries are resolved lane-parallel against
 //                       the checkpoints (lane j: start of window j, lane j + 32: its end).  Clips are emitted FROM
 //                       THE LOAD RING while the record streams: output slot k mirrors the input's op positions
 //                       (out_ops[k * slot_stride + 32 r + position]), clip j of a record goes to slot j mod n_slots,

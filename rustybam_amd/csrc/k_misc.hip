@@ -518,7 +518,7 @@ extern "C" hipError_t rb_launch_compact_clips(const rb_compact_params *p, hipStr
 
 // ------------------------------------------------------------------------------------------------
 // rb_dev_box_probe: what THIS box moves at the clip kernel's memory mix, without the clip kernel's instructions.  Every wave owns a
-// 20 KiB stretch of `src` (a 5120-op record) and walks it in ten 2 KiB steps in the clip kernel's shape -- 32 contiguous bytes per lane as
+// 20 KiB stretch of `src` (a 5120-op record) and walks it in ten 2 KiB steps in the shape the clip kernel had until it went flat -- 32 contiguous bytes per lane as
 // two 16-byte loads --, storing every step into slot 0 and every fifth one into slot 1 as well (about 1.2 bytes written per byte read:
 // config 3's ratio).  Around the loop the wave stamps s_memtime (shader cycles) and s_memrealtime (100 MHz): the clock the chip holds
 // under this memory load comes out with the time (bench.py's `box` block; tools/st_probe.hip is the stand-alone form of it).
@@ -527,7 +527,7 @@ typedef uint32_t rb_bp_u32x4 __attribute__((ext_vector_type(4)));
 // SCATTER: wave w takes stretch (w mod 4096) * (n / 4096) + w / 4096 -- the waves that run at the same time are then spread over the
 // whole array, 5 MB apart, as the clip kernel's are (its records run longest first, i.e. in no memory order), instead of side by side.
 // FLAT (scatter code 2 / 3): lane l takes bytes [16 l, 16 l + 16) and [1024 + 16 l, ...) of a 2 KiB step -- every instruction covers 1 KiB of
-// whole lines -- instead of the clip kernel's 32 contiguous bytes per lane: what the other load shape would be worth on these buffers.
+// whole lines -- instead of 32 contiguous bytes per lane: the clip kernel's shape since profiles/stream_flat_summary.md.
 template <bool SCATTER, bool FLAT = false>
 __global__ __launch_bounds__(256) void rb_k_box_probe(const char *__restrict__ src, char *__restrict__ d0, char *__restrict__ d1, uint64_t n_stretch,
                                                       uint32_t *stamps /* [3]: sum of cycles >> 6, sum of 10 ns ticks, stamped waves */,

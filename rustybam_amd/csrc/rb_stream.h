@@ -15,8 +15,11 @@
 // the record a second time (by then out of L2: ~100 bytes fetched per boundary, a dependent trip with the ring drained).
 //
 // One configuration is built, the one rounds 2 - 5 arrived at (docs/history.md, profiles/r04_stream_summary.md); what lost, in a line each:
-//   a step of 4 ops per lane ("flat": one 16-byte load per lane, whole 128-byte lines per instruction, 6 % cheaper in the memory-mix
-//     probe): 2 % (11.81 against 12.07 ms) for twice the steps -- twice the wave scans and scalar bookkeeping per op --, ring at v96;
+//   a lane's 8 ops as 32 contiguous bytes, where every load and store instruction touches all sixteen 128-byte lines of the step and
+//     moves half of each: liftover 9.29 against 9.08 ms a step (kernel 9.08 against 8.87 ms), break-paf 8.04 against 7.75 ms, three runs
+//     each in alternation (profiles/stream_flat_summary.md).  The step is flat in all three users: lane l holds the 4-op groups l and
+//     l + 64 of the step, and every instruction covers 1 KiB of whole lines (the memory-mix probe prices the shapes at 7.62 and 7.19 ms);
+//   half-sized flat steps of 4 ops per lane: 2 % (11.81 against 12.07 ms) for twice the wave scans and scalar bookkeeping per op, ring at v96;
 //   three steps in flight instead of two (ring at v96, four waves per SIMD instead of five), segments of 12 steps: nothing;
 //   non-temporal stores of the stream: 2 ms longer; non-temporal loads: 5 - 17 % slower; a touch load of a later wave's job: nothing;
 //   a separate interior ("fast") step: 84 vector registers, the ring at v96, 9.81 against 9.74 ms on one box;
@@ -40,7 +43,7 @@
         t_prev = t_now;                                                                                              \
     }
 
-// A step is 512 ops: two 16-byte loads of 32 contiguous bytes per lane.
+// A step is 512 ops: two 16-byte loads per lane, 256 ops apart (lane l: ops 4 l .. 4 l + 3 of each half of the step).
 #define RB_OPL 8                                   // ops per lane and step
 #define RB_GRP 2                                   // 16-byte groups per lane and step
 #define RB_STEP_SHIFT 9                            // log2 of the ops of a step
@@ -51,7 +54,7 @@ static_assert(RB_GRP * 4 == RB_OPL && (1 << RB_STEP_SHIFT) == 64 * RB_OPL && RB_
 // exec mask: they move nothing but they count, tools/vmcnt_probe.hip, which keeps every s_waitcnt immediate exact)
 #define RB_STEP_VMEM (RB_GRP * RB_MS + RB_GRP)
 #define RB_RING_WAIT ((RB_PF - 1) * RB_STEP_VMEM) // all but the youngest of them: the loads of the step being taken have landed
-// the speculative stores of a step are widened to whole granules of 64 bytes (two lanes), see the stores of a step
+// the speculative stores of a step are widened to whole granules of 64 bytes (four lanes of one half), see the stores of a step
 #define RB_GRAN 16
 
 // The load ring lives in VGPRs the compiler does not know: it allocates v0 .. v(RB_RING_BASE - 1) (amdgpu_num_vgpr), the ring is
@@ -95,17 +98,18 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
     const int dbg = DIAG ? p.debug_skip : 0;
     // checkpoints: exclusive (R,Q,U) prefixes every CPO ops, SoA so that R can be binary-searched.  The liftover build resolves from
     // what the step captured (cap_all below) and searches the checkpoints only for the boundaries the capture did not take: it keeps one
-    // per 16 ops (every other lane leaves one; the fallback loads 16 ops and picks the half, rb_load_group_wide), which makes the room
-    // for the capture table.  The break build and the list form capture nothing and keep one per lane.
-    // (the list form, like break-paf, stays as it was: with the capture its build reaches v87 and parks its spilled scalars in v88 v89,
+    // per 16 ops (every fourth lane of a half leaves one; the fallback loads 16 ops and picks the half, rb_load_group_wide), which makes
+    // the room for the capture table.  The break build and the list form capture nothing and keep one per 8 ops (every second lane).
+    // (the list form, like break-paf, captures nothing: with the capture its build reaches v87 and parks its spilled scalars in v88 v89,
     //  the first registers of its ring, which tests/test_ring_registers.py holds at v88..v103)
     constexpr bool CAP = !BRK && !LIST;
     constexpr uint32_t CPO = CAP ? 2u * RB_CP_OPS : (uint32_t)RB_CP_OPS, CPS = (64u * RB_OPL) / CPO; // ops per checkpoint, checkpoints per step
     __shared__ uint32_t cp_all[4][3][RB_SMAX * CPS];
     __shared__ uint32_t wx_all[4][RB_HMAX + 1]; // window indices of one pass over a window list that is not sorted
     // the capture table: entry b of a wave belongs to boundary b of the pass (lane b resolves it: b < 32 the start of clip b, else the
-    // end of clip b - 32) and holds what the lane that streamed the boundary's chunk had in registers: its 8 ops, {the op in front of
-    // them, the exclusive R, Q, U prefixes} -- 48 bytes --, and in cap_t the chunk's number in the segment
+    // end of clip b - 32) and holds what the lane pair that streamed the boundary's chunk had in registers: its 8 ops (aligned to 8: the
+    // groups of lanes l & ~1 and l | 1 of one half), {the op in front of them, the exclusive R, Q, U prefixes at the first of them} -- 48
+    // bytes --, and in cap_t the chunk's number in the segment, in units of 8 ops
     __shared__ uint4 cap_all[CAP ? 4 : 1][CAP ? 64 * 3 : 1];
     __shared__ uint32_t cap_t[CAP ? 4 : 1][CAP ? 64 : 1];
     // LDS per block: liftover 15,360 + 528 + 12,288 + 1,024 = 29,200 bytes, break-paf and the list form 30,720 + 528 + 16 + 4 = 31,268
@@ -187,7 +191,6 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
     const uint32_t *__restrict__ gbase0 = p.ops + g0;
     const uint32_t first_boff = (uint32_t)head * 4u;                          // byte offset (from g0) of the record's first op
     const uint32_t last_boff = (uint32_t)(((gend - 1u) & ~3ull) - g0) * 4u;   // ... of the last 16-byte group that holds an op of it
-    const uint32_t last_cboff = last_boff & ~(4u * RB_OPL - 1u);              // ... of the chunk (RB_OPL ops, one lane) with that group
 
     // ---- where clips go.  Output copy ("slot") k of the batch mirrors the input positions: the op at coordinate c of this
     //      record (c counted from g0, the first op of the record's first 128-byte line) lives at
@@ -219,25 +222,29 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
     uint32_t resume_seg = 0, resume_R = 0, resume_Q = 0, resume_U = 0;
     unsigned long long sv_exec;
     asm volatile("s_mov_b64 %0, exec" : "=s"(sv_exec));
-    const uint32_t lane_boff = (uint32_t)lane * (4u * RB_OPL);
+    const uint32_t lane_boff = (uint32_t)lane * 16u; // of the lane's group A in the step; group B lies 1024 bytes behind
     // (chunks past the record's end are not loaded: lanes behind the last chunk re-read it, and the loads of steps
     //  behind the last one run with an empty exec mask)
-#define RB_RING_LOAD_ASM(A, B_, C_, D_)                                                                                         \
+    // (the clamp is made per group -- the second group's address is the first one's plus 1024 only while neither is clamped --, so
+    //  each load has an address register of its own where the stores, which are not clamped, use offset:1024)
+#define RB_RING_LOAD_ASM(A, B_, C_, D_)                                                                                    \
     asm volatile("s_mov_b64 exec, %[lm]\n\t"                                                                                    \
          "global_load_dwordx4 " RB_RREG(A, 3) ", %[o], %[sb]\n\t"                                                       \
-         "global_load_dwordx4 " RB_RREG(C_, 3) ", %[o], %[sb] offset:16\n\t"                                            \
+         "global_load_dwordx4 " RB_RREG(C_, 3) ", %[o2], %[sb]\n\t"                                                     \
          "s_mov_b64 exec, %[sv]"                                                                                        \
          :                                                                                                              \
-         : [o] "v"(lo_), [sb] "s"(gb_), [lm] "s"(lm_), [sv] "s"(sv_)                                                    \
+         : [o] "v"(lo_), [o2] "v"(lo2_), [sb] "s"(gb_), [lm] "s"(lm_), [sv] "s"(sv_)                                    \
          : "memory", RB_RING_TOP);
 #define RB_RING_LOAD(RING, STP)                                                                                                 \
     {                                                                                                                           \
         const uint32_t stp_ = (STP);                                                                                            \
         uint32_t lo_ = (stp_ << (RB_STEP_SHIFT + 2)) + lane_boff;                                                               \
-        lo_ = lo_ < last_cboff ? lo_ : last_cboff;                                                                              \
         const uint32_t *const gb_ = gbase0; /* (named copies: a generic lambda does not capture what only an asm operand uses) */ \
         const unsigned long long sv_ = sv_exec;                                                                                 \
         const unsigned long long lm_ = stp_ < n_steps ? sv_ : 0ull;                                                             \
+        uint32_t lo2_ = lo_ + 1024u;                                                                                            \
+        lo_ = lo_ < last_boff ? lo_ : last_boff;                                                                                \
+        lo2_ = lo2_ < last_boff ? lo2_ : last_boff;                                                                             \
         RB_RING_CASE(RING, RB_RING_LOAD_ASM)                                                                                    \
     }
 #define RB_RING_NOSTORES                                                                                                        \
@@ -246,13 +253,18 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
     // the capture's asm statements (the ring's registers named literally, like the loads and stores): the slot's last op into a register
     // of the compiler's; an entry of the capture table written from the slot; the last op of lane 63 into a scalar register
 #define RB_RING_LASTOP(A, B_, C_, D_) asm volatile("v_mov_b32 %0, " RB_RREG1(D_) "\n\ts_nop 1" : "=v"(lastw));
-#define RB_RING_CAPTURE(A, B_, C_, D_)                                                                                          \
-    asm volatile("ds_write_b128 %0, " RB_RREG(A, 3) "\n\tds_write_b128 %0, " RB_RREG(C_, 3) " offset:16\n\t"                    \
-                 "ds_write2_b32 %0, %1, %2 offset0:8 offset1:9\n\tds_write2_b32 %0, %3, %4 offset0:10 offset1:11\n\t"            \
-                 "ds_write_b32 %5, %6\n\ts_waitcnt lgkmcnt(0)"                                                                  \
+    // (group A's last op; an entry's 16 bytes of ops from each lane of the pair, the rest from the even lane)
+#define RB_RING_LASTOP_A(A, B_, C_, D_) asm volatile("v_mov_b32 %0, " RB_RREG1(B_) "\n\ts_nop 1" : "=v"(lastw_a));
+#define RB_RING_CAPTURE_FLAT(G)                                                                                                 \
+    asm volatile("s_mov_b64 exec, %[mp]\n\tds_write_b128 %[ea], " G "\n\ts_mov_b64 exec, %[me]\n\t"                            \
+                 "ds_write2_b32 %[ea], %[pv], %[xr] offset0:8 offset1:9\n\tds_write2_b32 %[ea], %[xq], %[xu] offset0:10 offset1:11\n\t" \
+                 "ds_write_b32 %[ta], %[tq]\n\ts_mov_b64 exec, %[sv]\n\ts_waitcnt lgkmcnt(0)"                                  \
                  :                                                                                                              \
-                 : "v"(ea), "v"(pvw), "v"(cR), "v"(xQ), "v"(xU), "v"(ta), "v"(tq)                                               \
+                 : [ea] "v"(ea), [pv] "v"(pv_), [xr] "v"(xr_), [xq] "v"(xq_), [xu] "v"(xu_), [ta] "v"(ta), [tq] "v"(tq_),        \
+                   [mp] "s"(mp_), [me] "s"(me_), [sv] "s"(sv_p)                                                                 \
                  : "memory");
+#define RB_RING_CAPTURE_A(A, B_, C_, D_) RB_RING_CAPTURE_FLAT(RB_RREG(A, 3))
+#define RB_RING_CAPTURE_B(A, B_, C_, D_) RB_RING_CAPTURE_FLAT(RB_RREG(C_, 3))
 #define RB_RING_CARRY(A, B_, C_, D_) asm volatile("v_readlane_b32 %0, " RB_RREG1(D_) ", 63" : "=s"(v_carry));
     // The first pass of a record streams it from its first step: the ring's first loads go out HERE, in front of the pass's window loads
     // (a chain of dependent loads of its own), not behind them -- one memory latency per record instead of two in front of the first step.
@@ -390,33 +402,38 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
                  : "n"(RB_RING_WAIT));
                 RB_RING_CASE(ring, RB_RING_TAKE)
 #undef RB_RING_TAKE
-                unsigned long long msk[RB_MS];
+                unsigned long long msk[RB_MS], mskb[RB_MS]; // lanes whose group A / group B may hold ops of the slot's clips
 #pragma unroll
-                for (int q = 0; q < RB_MS; q++) msk[q] = 0ull;
+                for (int q = 0; q < RB_MS; q++) msk[q] = mskb[q] = 0ull;
                 if (st < seg1) { // (no break: the ring must be in the same state on every path)
-                    const uint32_t w_all[8] = {(uint32_t)a0, (uint32_t)(a0 >> 32), (uint32_t)a1, (uint32_t)(a1 >> 32),
-                                               (uint32_t)a2, (uint32_t)(a2 >> 32), (uint32_t)a3, (uint32_t)(a3 >> 32)};
-                    uint32_t w[RB_OPL], c[RB_OPL]; // the lane's ops; what the verification looks at
+                    static_assert(RB_OPL == 8, "two groups of four ops");
+                    // the lane's ops: w[0..3] group A (ops 4 l .. of the step's first half), w[4..7] group B (the same of its second half)
+                    uint32_t w[RB_OPL] = {(uint32_t)a0, (uint32_t)(a0 >> 32), (uint32_t)a1, (uint32_t)(a1 >> 32),
+                                          (uint32_t)a2, (uint32_t)(a2 >> 32), (uint32_t)a3, (uint32_t)(a3 >> 32)};
+                    uint32_t c[RB_OPL]; // what the verification looks at
 #pragma unroll
-                    for (int q = 0; q < RB_OPL; q++) w[q] = c[q] = w_all[q];
+                    for (int q = 0; q < RB_OPL; q++) c[q] = w[q];
                     if (edge) {
                         // ops of the neighbouring records: zero for the sums (a 0-length M); for the verification an I / D of length
-                        // 1 by position parity -- regular, alternating, and never equal to the match op a normalised record ends on
-                        const int32_t idx0 = (int32_t)(st << RB_STEP_SHIFT) + lane * RB_OPL - head;
+                        // 1 by position parity -- regular, alternating, and never equal to the match op a normalised record ends on.
+                        // Each group by its own index.
+                        const int32_t idx0 = (int32_t)(st << RB_STEP_SHIFT) + lane * 4 - head;
 #pragma unroll
                         for (int q = 0; q < RB_OPL; q++) {
-                            const bool ok = (uint32_t)(idx0 + q) < n; // (also the negative head indices)
+                            const bool ok = (uint32_t)(idx0 + (q & 3) + (q >> 2) * 256) < n;
                             c[q] = ok ? w[q] : ((q & 1) ? 0x12u : 0x11u);
                             w[q] = ok ? w[q] : 0u;
                         }
                     }
                     if (validate_s) {
-                        const uint32_t prevw = rb_prev_lane(c[RB_OPL - 1], v_carry); // previous lane's last op; lane 0: the previous step's
+                        // the op in front of a group: the lane below's last op of the same half; lane 0 of B: lane 63's last op of A; lane 0
+                        // of A: the last op of the step before
+                        const uint32_t prev_a = rb_prev_lane(c[3], v_carry), prev_b = rb_prev_lane(c[7], rb_readlane<uint32_t>(c[3], 63));
                         uint32_t rg[RB_OPL], x[RB_OPL];
 #pragma unroll
                         for (int q = 0; q < RB_OPL; q++) {
                             rg[q] = (uint32_t)__builtin_amdgcn_sbfe((int)0x018F018Fu, c[q], 1u); // M I D N = X
-                            x[q] = (c[q] ^ (q ? c[q - 1] : prevw)) & 15u;
+                            x[q] = (c[q] ^ (q == 0 ? prev_a : (q == 4 ? prev_b : c[q - 1]))) & 15u;
                         }
                         auto min3 = [](uint32_t a, uint32_t b, uint32_t d) { const uint32_t t = a < b ? a : b; return t < d ? t : d; };
 #pragma unroll
@@ -426,79 +443,95 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
                             v_adj = min3(v_adj, x[q], x[q + 1]);
                         }
                     }
-                    // per-lane sums of the reference / query / unit lengths of 8 ops; regular records hold only
+                    // per-lane sums of the reference / query / unit lengths of each group's 4 ops; regular records hold only
                     // M I D N = X, so "consumes the reference" = not I and "consumes the query" = not D / N: one
-                    // v_bfe_i32 per class turns the op code (low bits of the word) into an all-ones / zero mask
-                    uint32_t sr = 0, sq = 0, su = 0;
+                    // v_bfe_i32 per class turns the op code (low bits of the word) into an all-ones / zero mask.
+                    // A's sums are scanned across the wave, B's on top of A's totals.
+                    uint32_t sr = 0, sq = 0, su = 0, srb = 0, sqb = 0, sub = 0;
 #pragma unroll
-                    for (int q = 0; q < RB_OPL; q++) {
-                        const uint32_t len = rb_len(w[q]);
+                    for (int q = 0; q < 4; q++) {
+                        const uint32_t len = rb_len(w[q]), lenb = rb_len(w[4 + q]);
                         sr += len & (uint32_t)__builtin_amdgcn_sbfe((int)0xFFFDFFFDu, w[q], 1u);
                         sq += len & (uint32_t)__builtin_amdgcn_sbfe((int)0xFFF3FFF3u, w[q], 1u); // not D, not N
                         su += len;
-                    }
-                    const uint32_t ir = rb_wave_scan_incl(sr), iq = rb_wave_scan_incl(sq), iu = rb_wave_scan_incl(su);
-                    // exclusive prefixes in front of the lane's chunk: the checkpoints, and what a captured boundary takes along
-                    const uint32_t xQ = Qb + iq - sq, xU = Ub + iu - su;
-                    if (!CAP || !(lane & 1)) { // a checkpoint every CPO ops
-                        const uint32_t t = (st - seg0) * CPS + ((uint32_t)lane >> (CAP ? 1 : 0));
-                        cpR[t] = Rb + ir - sr;
-                        cpQ[t] = xQ;
-                        cpU[t] = xU;
+                        srb += lenb & (uint32_t)__builtin_amdgcn_sbfe((int)0xFFFDFFFDu, w[4 + q], 1u);
+                        sqb += lenb & (uint32_t)__builtin_amdgcn_sbfe((int)0xFFF3FFF3u, w[4 + q], 1u);
+                        sub += lenb;
                     }
                     const uint32_t R0 = Rb;
-                    Rb += rb_readlane<uint32_t>(ir, 63);
-                    Qb += rb_readlane<uint32_t>(iq, 63);
-                    Ub += rb_readlane<uint32_t>(iu, 63);
+                    const uint32_t ir = rb_wave_scan_incl(sr), iq = rb_wave_scan_incl(sq), iu = rb_wave_scan_incl(su);
+                    const uint32_t irb = rb_wave_scan_incl(srb) + rb_readlane<uint32_t>(ir, 63), iqb = rb_wave_scan_incl(sqb) + rb_readlane<uint32_t>(iq, 63),
+                                   iub = rb_wave_scan_incl(sub) + rb_readlane<uint32_t>(iu, 63);
+                    // exclusive prefixes in front of each group: the checkpoints, and what a captured boundary takes along
+                    const uint32_t cR = R0 + ir - sr, cE = R0 + ir, xQ = Qb + iq - sq, xU = Ub + iu - su;
+                    const uint32_t cRb = R0 + irb - srb, cEb = R0 + irb, xQb = Qb + iqb - sqb, xUb = Ub + iub - sub;
+                    constexpr uint32_t LPC = CPO / 4u; // lanes of a half per checkpoint
+                    if (((uint32_t)lane & (LPC - 1u)) == 0u) { // a checkpoint every CPO ops, in op order: half A's, then half B's
+                        const uint32_t t = (st - seg0) * CPS + (uint32_t)lane / LPC;
+                        cpR[t] = cR, cpQ[t] = xQ, cpU[t] = xU;
+                        cpR[t + CPS / 2u] = cRb, cpQ[t + CPS / 2u] = xQb, cpU[t + CPS / 2u] = xUb;
+                    }
+                    Rb += rb_readlane<uint32_t>(irb, 63); // (A + B: B's sums are scanned on top of A's totals)
+                    Qb += rb_readlane<uint32_t>(iqb, 63);
+                    Ub += rb_readlane<uint32_t>(iub, 63);
                     if (validate_s) {
-                        v_maxsu = v_maxsu > su ? v_maxsu : su;
-                        v_utot += rb_readlane<uint32_t>(iu, 63);
+                        // (the guard stays what it was, the sum of 8 ops aligned to 8: a lane's group and its pair lane's, quad_perm [1 0 3 2])
+                        const uint32_t pa = su + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)su, 0xB1, 0xf, 0xf, false);
+                        const uint32_t pb = sub + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sub, 0xB1, 0xf, 0xf, false);
+                        const uint32_t sm = pa > pb ? pa : pb;
+                        v_maxsu = v_maxsu > sm ? v_maxsu : sm;
+                        v_utot += rb_readlane<uint32_t>(iub, 63);
                     }
                     if constexpr (BRK) {
                         // long indels among my 8 ops (ops of the neighbouring records are zero words here: an M of length 0).  They are
-                        // rare -- one step in six has one -- and are taken one by one, in op order, with wave-uniform arithmetic
-                        bool lane_big = false;
+                        // rare -- one step in six has one -- and are taken one by one, in op order (the lanes of half A, then those of
+                        // half B), with wave-uniform arithmetic
+                        bool big_a = false, big_b = false;
 #pragma unroll
-                        for (int q = 0; q < RB_OPL; q++) {
-                            const uint32_t cq = w[q] & 15u;
-                            lane_big |= (cq == RB_OP_I || cq == RB_OP_D) && rb_len(w[q]) > brk_max_;
+                        for (int q = 0; q < 4; q++) {
+                            const uint32_t ca = w[q] & 15u, cb = w[4 + q] & 15u;
+                            big_a |= (ca == RB_OP_I || ca == RB_OP_D) && rb_len(w[q]) > brk_max_;
+                            big_b |= (cb == RB_OP_I || cb == RB_OP_D) && rb_len(w[4 + q]) > brk_max_;
                         }
-                        unsigned long long cm = __ballot(lane_big);
-                        const bool had_big = cm != 0ull;
-                        const uint32_t lane_r0 = R0 + ir - sr; // reference offset of my first op
-                        while (cm) {
-                            const int l = __builtin_ctzll(cm);
-                            cm &= cm - 1ull;
-                            uint32_t rx = rb_readlane<uint32_t>(lane_r0, l);
+                        const unsigned long long cm_a = __ballot(big_a), cm_b = __ballot(big_b);
+                        const bool had_big = (cm_a | cm_b) != 0ull;
+                        rb_static_for<2>([&](auto half_c) {
+                            constexpr int hb = decltype(half_c)::value;
+                            unsigned long long cm = hb ? cm_b : cm_a;
+                            while (cm) {
+                                const int l = __builtin_ctzll(cm);
+                                cm &= cm - 1ull;
+                                uint32_t rx = rb_readlane<uint32_t>(hb ? cRb : cR, l); // reference offset of the group's first op
 #pragma unroll
-                            for (int q = 0; q < RB_OPL; q++) {
-                                const uint32_t wq = rb_readlane<uint32_t>(w[q], l);
-                                const uint32_t cq = wq & 15u, lq = rb_len(wq);
-                                const uint32_t rlq = cq == RB_OP_I ? 0u : lq; // (regular records: M I D N = X)
-                                if ((cq == RB_OP_I || cq == RB_OP_D) && lq > brk_max_) {
-                                    if (rx > brk_pre) { // liftover.rs:191: the piece in front of the indel, if it holds reference bases
-                                        const uint32_t li = brk_cnt - brk_j0; // (its lane in this pass; wraps far above 32 for earlier pieces)
-                                        if (li < 32u) {
-                                            D = (uint32_t)lane == 32u + li ? rx : D;
-                                            brk_def |= 1ull << (32u + li);
+                                for (int q = 0; q < 4; q++) {
+                                    const uint32_t wq = rb_readlane<uint32_t>(w[4 * hb + q], l);
+                                    const uint32_t cq = wq & 15u, lq = rb_len(wq);
+                                    const uint32_t rlq = cq == RB_OP_I ? 0u : lq; // (regular records: M I D N = X)
+                                    if ((cq == RB_OP_I || cq == RB_OP_D) && lq > brk_max_) {
+                                        if (rx > brk_pre) { // liftover.rs:191: the piece in front of the indel, if it holds reference bases
+                                            const uint32_t li = brk_cnt - brk_j0; // (its lane in this pass; wraps far above 32 for earlier pieces)
+                                            if (li < 32u) {
+                                                D = (uint32_t)lane == 32u + li ? rx : D;
+                                                brk_def |= 1ull << (32u + li);
+                                            }
+                                            brk_cnt++;
+                                            if (brk_cnt == brk_j0 + 32u) // the next pass's first piece opens in this segment: it resumes here
+                                                next_seg = seg0 / RB_SMAX, next_R = Rseg, next_Q = Qseg, next_U = Useg, brk_nx_cnt = brk_seg_cnt, brk_nx_pre = brk_seg_pre;
                                         }
-                                        brk_cnt++;
-                                        if (brk_cnt == brk_j0 + 32u) // the next pass's first piece opens in this segment: it resumes here
-                                            next_seg = seg0 / RB_SMAX, next_R = Rseg, next_Q = Qseg, next_U = Useg, brk_nx_cnt = brk_seg_cnt, brk_nx_pre = brk_seg_pre;
-                                    }
-                                    brk_pre = rx + rlq; // :203-206
-                                    {
-                                        const uint32_t li = brk_cnt - brk_j0;
-                                        if (li < 32u) { // the next piece opens here (its lanes are rewritten if it turns out empty)
-                                            D = (uint32_t)lane == li ? brk_pre + 1u : ((uint32_t)lane == 32u + li ? 0xFFFFFFFFu : D);
-                                            brk_def |= 1ull << li;
-                                            brk_def &= ~(1ull << (32u + li));
+                                        brk_pre = rx + rlq; // :203-206
+                                        {
+                                            const uint32_t li = brk_cnt - brk_j0;
+                                            if (li < 32u) { // the next piece opens here (its lanes are rewritten if it turns out empty)
+                                                D = (uint32_t)lane == li ? brk_pre + 1u : ((uint32_t)lane == 32u + li ? 0xFFFFFFFFu : D);
+                                                brk_def |= 1ull << li;
+                                                brk_def &= ~(1ull << (32u + li));
+                                            }
                                         }
                                     }
+                                    rx += rlq;
                                 }
-                                rx += rlq;
                             }
-                        }
+                        });
                         nb = brk_cnt < brk_j0 ? 0u : (brk_cnt - brk_j0 + 1u < 32u ? brk_cnt - brk_j0 + 1u : 32u);
                         if (had_big) { // pieces were closed / opened: the classes' current clips are read again
 #pragma unroll
@@ -506,62 +539,74 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
                         }
                     }
                     if (spec_s) {
-                        // Which of this lane's 8 ops a clip keeps is not known yet (boundaries are resolved per segment),
-                        // but which 8-op chunks can hold ops of clip j is: those whose reference span [cR, cE) reaches
-                        // from the clip's first base (D_start - 1) to its last one (D_end - 1); walking to the next /
-                        // previous match op only shrinks a clip.  Those chunks are stored as they are -- what lies
-                        // outside the clip is never read, and the two end ops are rewritten with the clipped
-                        // lengths once the boundaries are resolved.
-                        const uint32_t cR = R0 + ir - sr, cE = R0 + ir;
-                        // Capture: the chunk that holds a clip's start offset / its end offset (cR <= D < cE) is the group the resolution
-                        // will search.  The lane that has it writes the boundary's entry (is / ie: the boundary's lane), under a mask that
-                        // is empty in most steps: its 8 ops straight from the ring, the op in front of them (the lane below's last op;
-                        // lane 0: the last op of the step before), its prefixes, the chunk's number in the segment.
-                        auto capture = [&](const bool hs, const uint32_t is, const bool he, const uint32_t ie) {
-                            if (rb_ballot(hs || he) != 0ull) {
-                                uint32_t lastw;
+                        // Which of a group's 4 ops a clip keeps is not known yet (boundaries are resolved per segment), but which
+                        // groups can hold ops of clip j is: those whose reference span [cR, cE) reaches from the clip's first base
+                        // (D_start - 1) to its last one (D_end - 1); walking to the next / previous match op only shrinks a clip.
+                        // Those groups are stored as they are -- what lies outside the clip is never read, and the two end ops are
+                        // rewritten with the clipped lengths once the boundaries are resolved.
+                        // Capture: the group that holds a clip's start offset / its end offset (cR <= D < cE; at most one lane of one
+                        // half) is in the 8 ops the resolution will search: the groups of the lane pair (l & ~1, l | 1) of that half.
+                        // Under a mask that is empty in most steps both lanes write their 16 bytes of the boundary's entry (is / ie: the
+                        // boundary's lane) straight from the ring, the even lane the op in front of its group, its prefixes and the
+                        // chunk's number in the segment.
+                        auto capture = [&](const bool hs, const bool hsb, const uint32_t is, const bool he, const bool heb, const uint32_t ie) {
+                            const unsigned long long bs = rb_ballot(hs), bsb = rb_ballot(hsb), be = rb_ballot(he), beb = rb_ballot(heb);
+                            if ((bs | bsb | be | beb) != 0ull) {
+                                uint32_t lastw_a, lastw;
+                                RB_RING_CASE(ring, RB_RING_LASTOP_A)
                                 RB_RING_CASE(ring, RB_RING_LASTOP)
-                                const uint32_t pvw = rb_prev_lane(lastw, v_carry);
-                                // (lane 0 of the step a later pass resumes at has no op in front: the fallback takes its boundary)
-                                const bool pv_ok = lane != 0 || st == 0u || v_carry != 0xFu;
+                                const uint32_t pv_a = rb_prev_lane(lastw_a, v_carry), pv_b = rb_prev_lane(lastw, rb_readlane<uint32_t>(lastw_a, 63));
+                                // (lane 0 of the step a later pass resumes at has no op in front: the fallback takes the boundaries of its pair)
+                                const bool pv_ok = st == 0u || v_carry != 0xFu;
+                                auto pair = [](unsigned long long m) { m = (m | (m >> 1)) & 0x5555555555555555ull; return m | (m << 1); };
+                                const unsigned long long ps = pair(bs) & (pv_ok ? ~0ull : ~3ull), pe = pair(be) & (pv_ok ? ~0ull : ~3ull), psb = pair(bsb), peb = pair(beb);
                                 const uint32_t wv = threadIdx.x >> 6;
-                                const uint32_t tq = (st - seg0) * 64u + (uint32_t)lane;
-                                const bool ps = hs && pv_ok, pe = he && pv_ok;
-                                if (ps) {
-                                    const uint32_t ea = rb_lds_addr(&cap_all[0][0]) + (wv * 64u + is) * 48u, ta = rb_lds_addr(&cap_t[0][0]) + (wv * 64u + is) * 4u;
-                                    RB_RING_CASE(ring, RB_RING_CAPTURE)
-                                }
-                                if (pe) {
-                                    const uint32_t ea = rb_lds_addr(&cap_all[0][0]) + (wv * 64u + ie) * 48u, ta = rb_lds_addr(&cap_t[0][0]) + (wv * 64u + ie) * 4u;
-                                    RB_RING_CASE(ring, RB_RING_CAPTURE)
-                                }
-                                cap_mask |= (rb_ballot(ps) != 0ull ? 1ull << is : 0ull) | (rb_ballot(pe) != 0ull ? 1ull << ie : 0ull);
+                                const uint32_t tq_a = (st - seg0) * 64u + ((uint32_t)lane >> 1), tq_b = tq_a + 32u;
+                                const uint32_t odd = ((uint32_t)lane & 1u) * 16u;
+                                const unsigned long long sv_c = sv_exec;
+                                auto put = [&](const uint32_t bi, const unsigned long long ma, const unsigned long long mb) {
+                                    const unsigned long long sv_p = sv_c; // (named copies, see RB_RING_LOAD)
+                                    const uint32_t ea = rb_lds_addr(&cap_all[0][0]) + (wv * 64u + bi) * 48u + odd, ta = rb_lds_addr(&cap_t[0][0]) + (wv * 64u + bi) * 4u;
+                                    if (ma != 0ull) {
+                                        const unsigned long long mp_ = ma, me_ = ma & 0x5555555555555555ull;
+                                        const uint32_t pv_ = pv_a, xr_ = cR, xq_ = xQ, xu_ = xU, tq_ = tq_a;
+                                        RB_RING_CASE(ring, RB_RING_CAPTURE_A)
+                                    } else if (mb != 0ull) {
+                                        const unsigned long long mp_ = mb, me_ = mb & 0x5555555555555555ull;
+                                        const uint32_t pv_ = pv_b, xr_ = cRb, xq_ = xQb, xu_ = xUb, tq_ = tq_b;
+                                        RB_RING_CASE(ring, RB_RING_CAPTURE_B)
+                                    }
+                                };
+                                put(is, ps, psb);
+                                put(ie, pe, peb);
+                                cap_mask |= ((ps | psb) != 0ull ? 1ull << is : 0ull) | ((pe | peb) != 0ull ? 1ull << ie : 0ull);
                             }
                         };
+                        // boundaries of clips that ended on the last base of the step before: their offset is this step's first one,
+                        // held by the first chunk of half A that is not empty
                         if constexpr (CAP) {
-                            // boundaries of clips that ended on the last base of the step before: their offset is this step's first one,
-                            // held by the first chunk that is not empty
                             while (cap_pend != 0ull) {
                                 const uint32_t bi = (uint32_t)__builtin_ctzll(cap_pend);
                                 cap_pend &= cap_pend - 1ull;
-                                capture(cR == R0 && cE != R0, bi, false, bi);
+                                capture(cR == R0 && cE != R0, false, bi, false, false, bi);
                             }
                         }
 #pragma unroll
                         for (int q = 0; q < RB_MS; q++) {
-                            unsigned long long mk = 0ull;
+                            unsigned long long mk = 0ull, mkb = 0ull;
                             for (;;) {
                                 mk |= rb_ballot(cR < c_de[q] && cE >= c_ds[q]);
-                                if constexpr (CAP) capture(c_ds[q] - cR < cE - cR, c_j[q] & 31u, c_de[q] - cR < cE - cR, 32u + (c_j[q] & 31u));
+                                mkb |= rb_ballot(cRb < c_de[q] && cEb >= c_ds[q]);
+                                if constexpr (CAP)
+                                    capture(c_ds[q] - cR < cE - cR, c_ds[q] - cRb < cEb - cRb, c_j[q] & 31u, c_de[q] - cR < cE - cR, c_de[q] - cRb < cEb - cRb, 32u + (c_j[q] & 31u));
                                 if (c_de[q] > Rb) break; // the clip reaches past this step (or there is none): it stays the current one
-                                if constexpr (CAP) { // its last base is the step's last one: the chunk with its end offset is the next step's first
-                                    if (c_de[q] == Rb) cap_pend |= (1ull << (32u + (c_j[q] & 31u))) | (c_ds[q] == Rb ? 1ull << (c_j[q] & 31u) : 0ull);
-                                }
+                                // its last base is the step's last one: the chunk with its end offset is the next step's first
+                                if (CAP && c_de[q] == Rb) cap_pend |= (1ull << (32u + (c_j[q] & 31u))) | (c_ds[q] == Rb ? 1ull << (c_j[q] & 31u) : 0ull);
                                 c_j[q] += n_slots;       // it ends in this step: the class's next clip may begin in it
                                 clip_fetch(q);
                                 if (c_j[q] >= nb) break;
                             }
-                            msk[q] = mk;
+                            msk[q] = mk, mskb[q] = mkb;
                         }
                     }
                 }
@@ -570,32 +615,35 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
                     const uint32_t so = (st << (RB_STEP_SHIFT + 2)) + lane_boff;
                     const unsigned long long sv_st = sv_exec;
                     unsigned long long v0 = sv_st, v1 = sv_st;
+                    constexpr uint32_t so1 = 1024u, co1 = 256u; // the lane's group B behind its group A: bytes, ops
                     if (edge) { // groups in front of the record's first and behind its last one are not this record's to write
                         v0 = rb_ballot(so + 16u > first_boff && so <= last_boff);
-                        v1 = rb_ballot(so + 32u > first_boff && so + 16u <= last_boff);
+                        v1 = rb_ballot(so + so1 + 16u > first_boff && so + so1 <= last_boff);
                     }
 #pragma unroll
                     for (int q = 0; q < RB_MS; q++) {
-                        unsigned long long m0 = msk[q] & v0, m1 = msk[q] & v1;
-                        if (later_s && msk[q] != 0ull) { // later passes stay clear of the end ops earlier passes have patched
-                            const uint32_t c0 = (st << RB_STEP_SHIFT) + (uint32_t)lane * (uint32_t)RB_OPL;
+                        const unsigned long long msk1 = mskb[q];
+                        unsigned long long m0 = msk[q] & v0, m1 = msk1 & v1;
+                        if (later_s && (msk[q] | msk1) != 0ull) { // later passes stay clear of the end ops earlier passes have patched
+                            const uint32_t c0 = (st << RB_STEP_SHIFT) + (uint32_t)lane * 4u;
                             m0 &= rb_ballot(c0 >= carry[q]);
-                            m1 &= rb_ballot(c0 + 4u >= carry[q]);
+                            m1 &= rb_ballot(c0 + co1 >= carry[q]);
                         }
-                        // The stores are widened to whole granules of 64 bytes (RB_GRAN ops, two lanes): a lane in front of a clip's first chunk
+                        // The stores are widened to whole granules of 64 bytes (RB_GRAN ops, four lanes of one half): a lane in front of a clip's first group
                         // or behind its last one, in the same granule, stores what it loaded too (the record's own neighbouring ops; a slot's
                         // lines are this record's alone and nobody reads a slot outside a clip), and no two clips of a slot may share a granule
                         // instead of a 16-byte group.  Fewer lines written in part: -0.6 % on a fast box, -1.7 % on a slow one (r04_ab7, r04_hs8;
                         // a launch that writes no partial line at all is 5 % / 11 % shorter, profiles/r04_stream_summary.md).
-                        if constexpr (!BRK) { // break-paf's pieces lie op to op: its groups stay 16 bytes
-                            unsigned long long q4 = (m0 | m1);
-                            q4 = (q4 | (q4 >> 1)) & 0x5555555555555555ull;
-                            q4 |= q4 << 1;
-                            const unsigned long long keep0 = m0 | ~msk[q], keep1 = m1 | ~msk[q]; // (what the edge / carry filters took away stays away)
-                            // (a line of a slot belongs to one record -- slot_row0 --: lanes in front of the record's first op or behind its last
-                            //  one, in a granule that holds an op of a clip, write what they loaded: a neighbour's ops, nobody's to read)
-                            m0 = q4 & keep0;
-                            m1 = q4 & keep1;
+                        if constexpr (!BRK) { // the granule is four lanes of one half (break-paf's pieces lie op to op: its groups stay 16 bytes)
+                            auto gran = [](unsigned long long m) {
+                                m |= m >> 1;
+                                m = (m | (m >> 2)) & 0x1111111111111111ull;
+                                m |= m << 1;
+                                return m | (m << 2);
+                            };
+                            const unsigned long long keep0 = m0 | ~msk[q], keep1 = m1 | ~msk1; // (what the edge / carry filters took away stays away)
+                            m0 = gran(m0) & keep0;
+                            m1 = gran(m1) & keep1;
                         }
                         if (dbg & 64) m0 = m1 = 0ull; // diagnostics: everything but the stores themselves
                         const uint32_t *sb = out_ops_ + slot_row0 + (uint64_t)q * slot_stride_;
@@ -604,10 +652,10 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
     asm volatile("s_mov_b64 exec, %[m0]\n\t"                                                                                    \
                  "global_store_dwordx4 %[o], " RB_RREG(A, 3) ", %[sb]\n\t"                                                      \
                  "s_mov_b64 exec, %[m1]\n\t"                                                                                    \
-                 "global_store_dwordx4 %[o], " RB_RREG(C_, 3) ", %[sb] offset:16\n\t"                                           \
+                 "global_store_dwordx4 %[o], " RB_RREG(C_, 3) ", %[sb] offset:%[o1]\n\t"                                        \
                  "s_mov_b64 exec, %[sv]"                                                                                        \
                  :                                                                                                              \
-                 : [m0] "s"(m0), [m1] "s"(m1), [o] "v"(so), [sb] "s"(sb), [sv] "s"(sv_st)                                       \
+                 : [m0] "s"(m0), [m1] "s"(m1), [o] "v"(so), [sb] "s"(sb), [sv] "s"(sv_st), [o1] "n"(so1)                        \
                  : "memory");
                         RB_RING_CASE(ring, RB_RING_STORE)
 #undef RB_RING_STORE
@@ -714,9 +762,12 @@ __device__ __forceinline__ void rb_stream_record(const uint64_t list_wave = 0) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #undef RB_RING_LOAD
 #undef RB_RING_LOAD_ASM
+#undef RB_RING_LASTOP_A
+#undef RB_RING_CAPTURE_FLAT
 #undef RB_RING_NOSTORES
 #undef RB_RING_LASTOP
-#undef RB_RING_CAPTURE
+#undef RB_RING_CAPTURE_A
+#undef RB_RING_CAPTURE_B
 #undef RB_RING_CARRY
         }
         if (!streams && preloaded && jb == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (the ring's loads are out: nothing of them may be in flight when the registers are the compiler's again)
