@@ -21,6 +21,9 @@
  *                            (the pass / recursion driver Paf::overlapping_paf_recs, paf.rs:210-305, stays on the host)
  *   rb_dev_nucfreq        <- nucfreq::nucfreq / region_nucfreq            nucfreq.rs:61-95, :111-125
  *   rb_dev_largest        <- liftover --largest: sort_by id, group_by id, max_by_key     main.rs:200-208
+ *   rb_dev_stats_rows     <- bamstats::stats_from_paf / add_stats_from_cigar              bamstats.rs:91-105, :107-154
+ *                            + PafRecord::check_integrity (paf.rs:825-857) of every record that trim_paf_by_rgns /
+ *                            break_paf_on_indels returned (the second command of `rb liftover .. | rb stats --paf`)
  *
  * Conventions
  *   - Plain C types only.  Every `rb_dev_*` pointer argument is a DEVICE pointer (HBM) owned by
@@ -358,6 +361,30 @@ size_t rb_largest_scratch_bytes(uint64_t n_keys);
 int rb_dev_largest(rb_ctx *ctx, const rb_hit_row *rows, uint64_t n_rows, const uint32_t *win_key, const uint32_t *rec_key,
                    uint64_t n_keys, uint64_t *sel, uint64_t *out, void *scratch);
 
+/* ---- stats of the hit rows (`rb liftover .. | rb stats --paf` without the text in between) ------- *
+ * <- bamstats::stats_from_paf (bamstats.rs:91-105, add_stats_from_cigar :107-154) + check_integrity (paf.rs:825-857) of every record
+ *    that rb_dev_liftover / rb_dev_break produced, where its clip lies.
+ * For a row k with status RB_ST_OK, stats[k] is what rb_dev_scan_records would write as the reduce row of a record that has the clip's
+ * ops as its CIGAR and rows[k].t_st / t_en / q_st / q_en as its coordinates: t_bases, q_bases, nmatch, aln_len, the seven u32 counters
+ * (diff = X + M, matches = M), the three f32 ratios (100.0f * (float)equal, divided by the u32 sum cast to float: NaN for a clip without
+ * = X M I D, which no clip kernel writes: a clip starts on a match op), status = RB_ST_OK, or RB_ST_PANIC_INTEGRITY_T / _Q when the sums
+ * disagree with the row's spans (RB_ST_PANIC_OVERFLOW when all lengths together pass 2^32 - 1) -- what Paf::from_file of the second
+ * command would panic on; rows the clip kernels wrote never have it, so it is a self-check --, flags = RB_F_HAS_M or 0.
+ * For a row whose status is not RB_ST_OK, stats[k] is all zero except status = rows[k].status.
+ * Where the clip is:  without RB_HIT_DESCRIPTOR out_ops[out_off .. out_off + out_n).  With it d = out_ops + out_off and the ops are
+ *   batch->ops[batch->op_off[rec] + d[0] ..][d[1]]; for rows without RB_HIT_INSIDE the first length is replaced by d[2] and the last by
+ *   d[3] (0 = keep), a one-op clip with both takes d[2] + d[3] - len (= aln_len); RB_HIT_INSIDE rows keep all lengths (d[2], d[3] are not
+ *   looked at).  batch->op_off[rec] is used as a START only, never op_off[rec + 1]: a batch in RB_LIFT_OP_STARTS form works.  Both forms
+ *   may occur in one call (in descriptor mode the generic kernel's rows carry real ops).  Of `batch` only ops and op_off are read.
+ * Op codes: all nine, with the scan's classes; a continuation word adds payload << 28 to its owner's class and is no event; other codes
+ *   above 8 count as rb_dev_scan_records counts them (in aln_len alone).  Sums are 64 bits wide: a single `=` of 3e9 bases is legal.
+ * MEMORY: the call reads the rows, whole 16-byte granules that hold at least one word of a clip or of a descriptor, op_off[rec] of
+ *   descriptor rows, and nothing else; out_ops and batch->ops must be 16-byte aligned and readable up to the next multiple of four words
+ *   behind the last clip (the batch's "next multiple of 32 ops" rule covers batch->ops).  It writes stats[0 .. n_rows) and nothing else.
+ * Enqueues on the context's stream, does not synchronise.  n_rows == 0 is valid.  Two calls on the same rows write the same bytes. */
+int rb_dev_stats_rows(rb_ctx *ctx, const rb_batch_view *batch, const rb_hit_row *rows, uint64_t n_rows, const uint32_t *out_ops,
+                      rb_reduce_row *stats /* [n_rows] OUT */);
+
 /* ---- break-paf -------------------------------------------------------------------------------- *
  * Pieces between indels longer than max_size, record order then piece order; same row shape,
  * rb_hit_row.win = piece ordinal among the candidate windows of the record. */
@@ -535,6 +562,25 @@ int rb_host_break_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_
                        const uint8_t *strand, uint32_t max_size, int bsearch_policy, uint8_t *cig_status, rb_reduce_row *reduce_out,
                        rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off, uint8_t **row_text,
                        rb_counters *counters);
+/* the same two without any text out (`rb liftover --stats`, `rb break-paf --stats`: what `.. | rb stats --paf` prints needs no CIGAR text):
+ * parse, scan, clip in descriptor mode, rb_dev_stats_rows on the rows and clips where they lie, then rows and stats to the host.
+ * rb_dev_format_cigars does not run.  Arguments as rb_host_liftover_text / rb_host_break_text up to n_rows; *stats [*n_rows] (malloc'ed,
+ * rb_host_free) takes the place of row_text_off / row_text: the reduce row of row k's clip, as rb_dev_stats_rows defines it.
+ * RB_LIFT_QBED works as in rb_host_liftover_text: rows, clips and therefore stats are in the swapped frame (I and D have changed places,
+ * as they have in the text the plain command prints). */
+int rb_host_liftover_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
+                                const uint8_t *strand, const uint32_t *contig, uint64_t n_win, const uint32_t *w_contig, const uint64_t *w_st,
+                                const uint64_t *w_en, int bsearch_policy, uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out,
+                                rb_hit_row **rows, uint64_t *n_rows, rb_reduce_row **stats, rb_counters *counters);
+int rb_host_break_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                             const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
+                             const uint8_t *strand, uint32_t max_size, int bsearch_policy, uint8_t *cig_status, rb_reduce_row *reduce_out,
+                             rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, rb_reduce_row **stats, rb_counters *counters);
+/* rb_dev_stats_rows on host arrays (the rows and clips of rb_host_liftover / rb_host_break, whose out_ops are dense and whose rows never
+ * carry RB_HIT_DESCRIPTOR; descriptor rows work too, through ops / op_off): uploads, runs, downloads.  stats [n_rows] caller-allocated. */
+int rb_host_stats_rows(rb_ctx *ctx, uint64_t n_rec, const uint32_t *ops, const uint64_t *op_off, const rb_hit_row *rows, uint64_t n_rows,
+                       const uint32_t *out_ops, uint64_t n_out, rb_reduce_row *stats);
 int rb_host_scan_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end,
                       const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand,
                       uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out);

@@ -313,6 +313,38 @@ class Engine:
                                       C.c_void_p(out_ptr), C.c_uint64(out_cap), C.c_void_p(counters_ptr)),
                   "rb_dev_break")
 
+    def dev_stats_rows(self, view, rows_ptr, n_rows, out_ptr, stats_ptr):
+        """rb_dev_stats_rows on device addresses: one reduce row (REDUCE_DT) per hit row, from the clip where it lies (plain ops in out_ops, or a
+        descriptor into the batch of `view`); enqueues on the context's stream"""
+        self._chk(self.L.rb_dev_stats_rows(self.ctx, C.byref(view), C.c_void_p(rows_ptr or 0), C.c_uint64(n_rows), C.c_void_p(out_ptr or 0),
+                                           C.c_void_p(stats_ptr or 0)), "rb_dev_stats_rows")
+
+    def stats_rows(self, ops, op_off, rows, out_ops):
+        """rb_dev_stats_rows on host arrays (ops / op_off: the batch descriptor rows point into, op_off a table of starts; rows: HIT_DT;
+        out_ops: what the rows' out_off index): uploads, runs, downloads -> REDUCE_DT [len(rows)]"""
+        rows = _arr(rows, HIT_DT)
+
+        def padded(a):  # readable up to the next multiple of four words
+            a = _arr(a, np.uint32)
+            return np.concatenate([a, np.zeros(-len(a) % 4 + 4, np.uint32)])
+        ops, out_ops, op_off = padded(ops), padded(out_ops), _arr(op_off, np.uint64)
+        stats = np.zeros(len(rows), REDUCE_DT)
+        bufs = []
+        try:
+            for a in (ops, op_off, rows, out_ops, stats):
+                bufs.append(self.dev_alloc(max(a.nbytes, 256)))
+                if a.nbytes and a is not stats:
+                    self._chk(self.L.rb_dev_upload(self.ctx, C.c_void_p(bufs[-1]), _p(a), C.c_size_t(a.nbytes)), "rb_dev_upload")
+            view = self.batch_view(max(len(op_off) - 1, 0), len(ops), bufs[0], bufs[1], 0, 0, 0, 0, 0, 0)
+            self.dev_stats_rows(view, bufs[2], len(rows), bufs[3], bufs[4])
+            if stats.nbytes:
+                self._chk(self.L.rb_dev_download(self.ctx, _p(stats), C.c_void_p(bufs[4]), C.c_size_t(stats.nbytes)), "rb_dev_download")
+            return stats
+        finally:
+            self.sync()
+            for b in bufs:
+                self.dev_free(b)
+
     def largest_scratch_bytes(self, n_keys):
         f = self.L.rb_largest_scratch_bytes
         f.restype = C.c_size_t

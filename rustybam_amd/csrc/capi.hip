@@ -1643,18 +1643,21 @@ struct largest_text {
 };
 // text in -> text out around the clip kernels; scan_only stops after the record scan (rb_host_scan_text).  lg: liftover --largest -- the hit
 // rows stay on the device, rb_dev_largest picks one per key, and only those rows come back, get format items and are printed
+// stats (rb_host_liftover_stats_text, rb_host_break_stats_text): no text out -- rb_dev_stats_rows runs on the rows and clips where the clip
+// kernels left them, and the rows come back with one reduce row each; row_text_off / row_text are not used
 static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool scan_only, uint64_t n_rec, const uint8_t *text,
                           uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en,
                           const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand, const uint32_t *contig, uint64_t n_win,
                           const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en, int policy, uint8_t *cig_status,
                           rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off,
-                          uint8_t **row_text, rb_counters *counters, const largest_text *lg = nullptr) {
-    if (!ctx || (n_rec && (!cig_off || !cig_end || !cig_status))) return RB_E_INVALID;
+                          uint8_t **row_text, rb_counters *counters, const largest_text *lg = nullptr, rb_reduce_row **stats = nullptr) {
+    if (!ctx || (n_rec && (!cig_off || !cig_end || !cig_status)) || (stats && (lg || scan_only))) return RB_E_INVALID;
     // liftover --qbed: the wrappers' own bit, taken out before anything reaches rb_dev_liftover
     const bool qbed = (policy & RB_LIFT_QBED) != 0;
     policy &= ~RB_LIFT_QBED;
     if (qbed && (is_break || scan_only)) return fail(ctx, RB_E_INVALID, "RB_LIFT_QBED: only rb_host_liftover_text and rb_host_liftover_largest_text take it");
     if (lg) *lg->declined = 0;
+    if (stats) *stats = nullptr;
     if (n_rec == 0) { // an empty file: no rows, no text
         if (rows) *rows = nullptr;
         if (n_rows) *n_rows = 0;
@@ -1670,6 +1673,7 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
     uint64_t n_dummy = 0, *off_dummy = nullptr;
     uint8_t *text_dummy = nullptr;
     if (scan_only) rows = &rows_dummy, n_rows = &n_dummy, row_text_off = &off_dummy, row_text = &text_dummy;
+    if (stats) row_text_off = &off_dummy, row_text = &text_dummy;
     if (!rows || !n_rows || !row_text_off || !row_text) return RB_E_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     *rows = nullptr;
@@ -1779,6 +1783,28 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
         d_take = d_srows, d_take_desc = d_sdesc;
         rb_lap("largest + gather", tl);
     }
+    if (stats) { // ---- the stats of every row's clip where it lies; rows and stats to the host, no text ----
+        rb_reduce_row *d_stats = nullptr;
+        if (!rc) rc = b.alloc((size_t)nr + 1, &d_stats);
+        if (!rc) rc = rb_dev_stats_rows(ctx, &b.v, d_rows, nr, d_out, d_stats);
+        if (!rc) {
+            *rows = (rb_hit_row *)malloc((size_t)(nr + 1) * sizeof(rb_hit_row));
+            *stats = (rb_reduce_row *)malloc((size_t)(nr + 1) * sizeof(rb_reduce_row));
+            if (!*rows || !*stats) rc = fail(ctx, RB_E_NOMEM, "malloc(rows)");
+        }
+        if (!rc && nr) rc = rb_dev_download(ctx, *rows, d_rows, (size_t)nr * sizeof(rb_hit_row));
+        if (!rc && nr) rc = rb_dev_download(ctx, *stats, d_stats, (size_t)nr * sizeof(rb_reduce_row));
+        rb_lap("stats rows + rows D2H", tl);
+        if (!rc) {
+            *n_rows = nr;
+            if (counters) *counters = hc;
+        } else {
+            free(*rows);
+            free(*stats);
+            *rows = nullptr, *stats = nullptr;
+        }
+        return rc;
+    }
     // ---- rows to the host, clip items back to the device, text out ----
     std::vector<uint32_t> desc;
     uint64_t *d_first = nullptr, *d_toff = nullptr;
@@ -1877,6 +1903,25 @@ extern "C" int rb_host_break_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *te
                                   uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters) {
     return host_lift_text(ctx, true, max_size, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, nullptr, 0,
                           nullptr, nullptr, nullptr, policy, cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, counters);
+}
+extern "C" int rb_host_liftover_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                           const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
+                                           const uint64_t *q_en, const uint8_t *strand, const uint32_t *contig, uint64_t n_win,
+                                           const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en, int policy, uint8_t *cig_status,
+                                           rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows,
+                                           rb_reduce_row **stats, rb_counters *counters) {
+    if (!stats) return RB_E_INVALID;
+    return host_lift_text(ctx, false, 0, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig, n_win,
+                          w_contig, w_st, w_en, policy, cig_status, reduce_out, norm_out, rows, n_rows, nullptr, nullptr, counters, nullptr, stats);
+}
+extern "C" int rb_host_break_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                        const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
+                                        const uint64_t *q_en, const uint8_t *strand, uint32_t max_size, int policy, uint8_t *cig_status,
+                                        rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows,
+                                        rb_reduce_row **stats, rb_counters *counters) {
+    if (!stats) return RB_E_INVALID;
+    return host_lift_text(ctx, true, max_size, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, nullptr, 0,
+                          nullptr, nullptr, nullptr, policy, cig_status, reduce_out, norm_out, rows, n_rows, nullptr, nullptr, counters, nullptr, stats);
 }
 extern "C" int rb_host_scan_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
                                  const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
@@ -2002,6 +2047,41 @@ extern "C" int rb_dev_digest_rows(rb_ctx *ctx, const rb_batch_view *batch, const
     p.digest = (unsigned long long *)digest;
     HIPCHK(ctx, rb_launch_digest_rows(&p, ctx->stream));
     return RB_OK;
+}
+
+// ---- stats of every hit row's clip where it lies (k_hitstats.hip) ------------------------------------
+extern "C" int rb_dev_stats_rows(rb_ctx *ctx, const rb_batch_view *batch, const rb_hit_row *rows, uint64_t n_rows, const uint32_t *out_ops,
+                                 rb_reduce_row *stats) {
+    if (!ctx || !batch || (n_rows && (!rows || !out_ops || !stats))) return RB_E_INVALID;
+    rb_hitstats_params p;
+    p.ops = batch->ops;
+    p.op_off = batch->op_off;
+    p.rows = rows;
+    p.n_rows = n_rows;
+    p.out_ops = out_ops;
+    p.stats = stats;
+    HIPCHK(ctx, rb_launch_hitstats(&p, ctx->stream));
+    return RB_OK;
+}
+
+extern "C" int rb_host_stats_rows(rb_ctx *ctx, uint64_t n_rec, const uint32_t *ops, const uint64_t *op_off, const rb_hit_row *rows, uint64_t n_rows,
+                                  const uint32_t *out_ops, uint64_t n_out, rb_reduce_row *stats) {
+    if (!ctx || (n_rows && (!rows || !stats)) || (n_rec && (!ops || !op_off)) || (n_out && !out_ops)) return RB_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBatch b(ctx);
+    b.v.n_rec = n_rec;
+    b.v.n_ops = n_rec ? op_off[n_rec] : 0;
+    const rb_hit_row *d_rows = nullptr;
+    const uint32_t *d_out = nullptr;
+    rb_reduce_row *d_stats = nullptr;
+    int rc = b.up(ops, (size_t)b.v.n_ops, &b.v.ops); // (up() leaves 256 readable bytes behind every array)
+    if (!rc) rc = b.up(op_off, (size_t)n_rec + 1, &b.v.op_off);
+    if (!rc) rc = b.up(rows, (size_t)n_rows, &d_rows);
+    if (!rc) rc = b.up(out_ops, (size_t)n_out, &d_out);
+    if (!rc) rc = b.alloc((size_t)n_rows + 1, &d_stats);
+    if (!rc) rc = rb_dev_stats_rows(ctx, &b.v, d_rows, n_rows, d_out, d_stats);
+    if (!rc && n_rows) rc = rb_dev_download(ctx, stats, d_stats, (size_t)n_rows * sizeof(rb_reduce_row));
+    return rc ? rc : rb_ctx_sync(ctx);
 }
 
 // ---- the box: what this GPU moves at the clip kernel's memory mix, and the clock it holds meanwhile (diagnostics for bench.py) ----

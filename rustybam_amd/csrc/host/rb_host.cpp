@@ -1143,8 +1143,59 @@ struct TextRows { // results of rb_host_liftover_text / rb_host_break_text (free
     rb_hit_row *rows = nullptr;
     uint64_t n_rows = 0, *toff = nullptr;
     uint8_t *text = nullptr;
-    ~TextRows() { rb_host_free(rows), rb_host_free(toff), rb_host_free(text); }
+    rb_reduce_row *stats = nullptr; // rb_host_liftover_stats_text / rb_host_break_stats_text: in place of toff / text
+    ~TextRows() { rb_host_free(rows), rb_host_free(toff), rb_host_free(text), rb_host_free(stats); }
 };
+// `rb liftover --stats` / `rb break-paf --stats`: the lines `rb stats --paf [--qbed]` prints for the records the plain command prints, from
+// the hit rows and the stats row of every row's clip (rb_dev_stats_rows) -- one cigar_stats_line per row with status OK, in row order.
+// names(h, s) fills the names, lengths and strand of row h's record; the coordinates are the hit row's.  The plain command's panic on a
+// hit row comes first, before any line.  A stats row whose status is not OK is what Paf::from_file of the second command panics on
+// (the clip kernels never write such a clip: a self-check): the lines in front of it are returned, the message goes to `trailing`.
+template <typename Names>
+std::vector<std::string> stats_lines(const rb_hit_row *rows, const rb_reduce_row *st, uint64_t n_rows, bool stats_qbed, std::string &trailing, Names names) {
+    for (uint64_t k = 0; k < n_rows; k++)
+        if (rows[k].status >= RB_ST_PANIC_NOTFOUND) throw Panic("Problem getting index in cigar: record " + std::to_string(rows[k].rec + 1));
+    uint64_t n_take = n_rows, printed = 0;
+    bool has_m = false;
+    for (uint64_t k = 0; k < n_rows && n_take == n_rows; k++) {
+        if (rows[k].status != RB_ST_OK) continue;
+        printed++;
+        if (st[k].status != RB_ST_OK) {
+            n_take = k;
+            trailing = "check_integrity: record " + std::to_string(printed) + " status " + std::to_string(st[k].status);
+        } else if (st[k].flags & RB_F_HAS_M) {
+            has_m = true;
+        }
+    }
+    if (has_m && trailing.empty()) fprintf(stderr, "\r⚠ warning: cigar string contains 'M', assuming mismatch since there is no MD tag."); // bamstats.rs:145-153
+    const unsigned TO = parallel_chunk_count((size_t)n_take);
+    std::vector<std::string> out_text(TO);
+    parallel_chunks((size_t)n_take, [&](unsigned t, size_t lo, size_t hi) {
+        for (size_t k = lo; k < hi; k++) {
+            const rb_hit_row &h = rows[k];
+            if (h.status != RB_ST_OK) continue;
+            const rb_reduce_row &r = st[k];
+            Stats s;
+            names(h, s);
+            s.r_st = (int64_t)h.t_st, s.r_en = (int64_t)h.t_en, s.q_st = (int64_t)h.q_st, s.q_en = (int64_t)h.q_en;
+            s.equal = r.equal, s.diff = r.diff, s.ins = r.ins, s.del = r.del, s.matches = r.matches;
+            s.ins_events = r.ins_events, s.del_events = r.del_events;
+            s.id_by_all = r.id_by_all, s.id_by_events = r.id_by_events, s.id_by_matches = r.id_by_matches;
+            out_text[t] += cigar_stats_line(s, stats_qbed);
+        }
+    });
+    return out_text;
+}
+// a record of a file read by the text route; qbed (liftover --qbed): the swapped record's columns, as assemble_lines prints them
+std::vector<std::string> stats_lines_of_file(const TextFile &f, const TextRows &R, bool qbed, bool stats_qbed, std::string &trailing) {
+    return stats_lines(R.rows, R.stats, R.n_rows, stats_qbed, trailing, [&](const rb_hit_row &h, Stats &s) {
+        const HeaderOnly &r = f.recs[h.rec];
+        std::string q(f.all.data() + r.q_name, r.q_name_n), t(f.all.data() + r.t_name, r.t_name_n);
+        s.strand = r.strand;
+        if (qbed) s.q_nm.swap(t), s.q_len = (int64_t)r.t_len, s.r_nm.swap(q), s.r_len = (int64_t)r.q_len;
+        else s.q_nm.swap(q), s.q_len = (int64_t)r.q_len, s.r_nm.swap(t), s.r_len = (int64_t)r.t_len;
+    });
+}
 // `println!("{}", rec)` for every Some(rec): header columns from the file text and the hit rows, CIGAR text from the device
 // qbed: the Display of the swapped record -- the line's target columns in front with the row's q_st / q_en (the hit rows are in the swapped
 // frame), then its query columns with the row's t_st / t_en
@@ -1195,8 +1246,13 @@ std::vector<std::string> assemble_lines(const TextFile &f, const std::vector<rb_
 // largest: main.rs:200-208 on the device (rb_host_liftover_largest_text) -- the rows that come back are the one record per id, in id order
 // qbed: main.rs:186-214 with --qbed (liftover.rs:139-148) -- RB_LIFT_QBED: the wrapper swaps the parsed CIGARs in place on the device and
 // lifts the swapped records; contigs are the records' query names, and the lines are the swapped records' (assemble_lines)
+// st (liftover --stats / --stats-qbed; not with largest): rb_host_liftover_stats_text instead, and the stats lines instead of the records
+struct StatsMode {
+    bool stats_qbed;
+    std::string *trailing;
+};
 static bool lift_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text, TextRuns *runs,
-                           bool largest, bool qbed) {
+                           bool largest, bool qbed, const StatsMode *st = nullptr) {
     // (one-shot command: the gigabytes behind these two are left to the end of the process instead of being unmapped piece by piece)
     TextFile &f = *new TextFile;
     if (!f.load(paf_path, nullptr, qbed)) return false; // the caller takes the general path
@@ -1235,6 +1291,13 @@ static bool lift_file_text(Engine &eng, const std::string &paf_path, const std::
                                                 norm.data(), &R.rows, &R.n_rows, &R.toff, &R.text, &cnt, win_key.data(), ids.size(), 0u, &declined),
                   "rb_host_liftover_largest_text");
         lap("rb_host_liftover_largest_text", tl);
+    } else if (st) {
+        eng.check(rb_host_liftover_stats_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
+                                              f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(), w_contig.data(),
+                                              w_st.data(), w_en.data(), policy, cig_status.data(), red.data(), norm.data(), &R.rows,
+                                              &R.n_rows, &R.stats, &cnt),
+                  "rb_host_liftover_stats_text");
+        lap("rb_host_liftover_stats_text", tl);
     } else {
         eng.check(rb_host_liftover_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
                                         f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(), w_contig.data(),
@@ -1246,6 +1309,11 @@ static bool lift_file_text(Engine &eng, const std::string &paf_path, const std::
     if (!f.check_loaded(cig_status, red)) return false; // (qbed: the reduce rows are the records' as read, the norm rows the swapped records')
     for (size_t i = 0; i < n; i++) panic_on(norm[i].status, "aligned_pairs", i); // liftover.rs:119-121
     if (declined) return false; // a stripped record inside a window, or a hit row that panics: the record route knows its id / replays the panic
+    if (st) {
+        out_text = stats_lines_of_file(f, R, qbed, st->stats_qbed, *st->trailing);
+        lap("stats lines", tl);
+        return true;
+    }
     RunMarks marks;
     out_text = assemble_lines(f, norm, R, &rgns, runs ? &marks : nullptr, qbed);
     if (runs) marks_to_runs(marks, out_text, *runs);
@@ -1260,9 +1328,14 @@ bool liftover_file_text(Engine &eng, const std::string &paf_path, const std::vec
 bool liftover_largest_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text, bool qbed) {
     return lift_file_text(eng, paf_path, rgns, out_text, nullptr, true, qbed);
 }
+bool liftover_stats_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, bool qbed, bool stats_qbed,
+                              std::vector<std::string> &out_text, std::string &trailing_panic) {
+    const StatsMode st{stats_qbed, &trailing_panic};
+    return lift_file_text(eng, paf_path, rgns, out_text, nullptr, false, qbed, &st);
+}
 
 // main.rs:271-281, text in -> text out
-bool break_file_text(Engine &eng, const std::string &paf_path, uint32_t break_length, std::vector<std::string> &out_text) {
+static bool break_file_text_impl(Engine &eng, const std::string &paf_path, uint32_t break_length, std::vector<std::string> &out_text, const StatsMode *st) {
     // (one-shot command: the gigabytes behind these two are left to the end of the process instead of being unmapped piece by piece)
     TextFile &f = *new TextFile;
     if (!f.load(paf_path)) return false;
@@ -1273,16 +1346,30 @@ bool break_file_text(Engine &eng, const std::string &paf_path, uint32_t break_le
     std::vector<rb_norm_row> norm(n);
     TextRows &R = *new TextRows;
     rb_counters cnt;
-    eng.check(rb_host_break_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
-                                 f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), break_length, eng.bsearch_policy, cig_status.data(),
-                                 red.data(), norm.data(), &R.rows, &R.n_rows, &R.toff, &R.text, &cnt),
-              "rb_host_break_text");
-    lap("rb_host_break_text", tl);
+    if (st)
+        eng.check(rb_host_break_stats_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
+                                           f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), break_length, eng.bsearch_policy,
+                                           cig_status.data(), red.data(), norm.data(), &R.rows, &R.n_rows, &R.stats, &cnt),
+                  "rb_host_break_stats_text");
+    else
+        eng.check(rb_host_break_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
+                                     f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), break_length, eng.bsearch_policy, cig_status.data(),
+                                     red.data(), norm.data(), &R.rows, &R.n_rows, &R.toff, &R.text, &cnt),
+                  "rb_host_break_text");
+    lap(st ? "rb_host_break_stats_text" : "rb_host_break_text", tl);
     if (!f.check_loaded(cig_status, red)) return false;
     for (size_t i = 0; i < n; i++) panic_on(norm[i].status, "aligned_pairs", i); // main.rs:275
-    out_text = assemble_lines(f, norm, R, nullptr);
-    lap("assemble lines", tl);
+    out_text = st ? stats_lines_of_file(f, R, false, st->stats_qbed, *st->trailing) : assemble_lines(f, norm, R, nullptr);
+    lap(st ? "stats lines" : "assemble lines", tl);
     return true;
+}
+bool break_file_text(Engine &eng, const std::string &paf_path, uint32_t break_length, std::vector<std::string> &out_text) {
+    return break_file_text_impl(eng, paf_path, break_length, out_text, nullptr);
+}
+bool break_stats_file_text(Engine &eng, const std::string &paf_path, uint32_t break_length, bool stats_qbed, std::vector<std::string> &out_text,
+                           std::string &trailing_panic) {
+    const StatsMode st{stats_qbed, &trailing_panic};
+    return break_file_text_impl(eng, paf_path, break_length, out_text, &st);
 }
 
 // ---- liftover / break-paf, text in -> text out, as a PIPELINE over chunks of the file (round 3) ---------------------------------------
@@ -1797,6 +1884,31 @@ std::vector<std::string> break_paf_on_indels_text(Engine &eng, const std::vector
     LiftResult L;
     run_break(eng, paf_recs, break_length, L);
     return rows_to_text(paf_recs, L.norm, L.rows, L.n_rows, L.out, nullptr);
+}
+
+// the record route of --stats: the rows and clips of run_liftover / run_break (host arrays, descriptor rows into the batch), their stats
+// through rb_host_stats_rows, then the same lines as the text route
+static std::vector<std::string> stats_text_of(Engine &eng, const LiftResult &L, bool stats_qbed, std::string &trailing) {
+    const std::vector<PafRecord> &recs = *L.recs;
+    HostBatch b(recs);
+    std::vector<rb_reduce_row> st((size_t)L.n_rows);
+    eng.check(rb_host_stats_rows(eng.ctx(), b.n(), b.ops.data(), b.op_off.data(), L.rows, L.n_rows, L.out, L.n_out, st.data()), "rb_host_stats_rows");
+    return stats_lines(L.rows, st.data(), L.n_rows, stats_qbed, trailing, [&](const rb_hit_row &h, Stats &s) {
+        const PafRecord &r = recs[h.rec]; // (liftover --qbed: the swapped record)
+        s.q_nm = r.q_name, s.q_len = (int64_t)r.q_len, s.r_nm = r.t_name, s.r_len = (int64_t)r.t_len, s.strand = r.strand;
+    });
+}
+std::vector<std::string> trim_paf_by_rgns_stats_text(Engine &eng, const std::vector<Region> &rgns, const std::vector<PafRecord> &paf_recs, bool invert_query,
+                                                     bool stats_qbed, std::string &trailing_panic) {
+    LiftResult L;
+    run_liftover(eng, rgns, paf_recs, invert_query, L);
+    return stats_text_of(eng, L, stats_qbed, trailing_panic);
+}
+std::vector<std::string> break_paf_on_indels_stats_text(Engine &eng, const std::vector<PafRecord> &paf_recs, uint32_t break_length, bool stats_qbed,
+                                                        std::string &trailing_panic) {
+    LiftResult L;
+    run_break(eng, paf_recs, break_length, L);
+    return stats_text_of(eng, L, stats_qbed, trailing_panic);
 }
 
 std::vector<Stats> stats_from_paf(Engine &eng, const std::vector<PafRecord> &recs) {

@@ -113,6 +113,20 @@ bool liftover_file_text(Engine &eng, const std::string &paf_path, const std::vec
 // the record route (two cg tags, a stripped record that lies inside a window, a hit row that panics), nothing was produced
 bool liftover_largest_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, std::vector<std::string> &out_text,
                                 bool qbed = false);
+// `rb liftover --stats` / `rb break-paf --stats` (this project's own flags): the lines `rb liftover .. | rb stats --paf [--qbed]` prints,
+// without the header -- one cigar_stats_line per record the plain command prints, from rb_dev_stats_rows of the clips where they lie; no
+// CIGAR text is printed or parsed in between.  The *_file_text forms: text in, rb_host_liftover_stats_text / rb_host_break_stats_text;
+// false = take the record route (the *_stats_text forms below), nothing was produced.  A panic of the plain command is thrown.
+// trailing_panic: the message of the second command's panic on a record the first printed (never, for clips the kernels wrote): the
+// lines in front of it are returned
+bool liftover_stats_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, bool qbed, bool stats_qbed,
+                              std::vector<std::string> &out_text, std::string &trailing_panic);
+bool break_stats_file_text(Engine &eng, const std::string &paf_path, uint32_t break_length, bool stats_qbed, std::vector<std::string> &out_text,
+                           std::string &trailing_panic);
+std::vector<std::string> trim_paf_by_rgns_stats_text(Engine &eng, const std::vector<Region> &rgns, const std::vector<PafRecord> &paf_recs, bool invert_query,
+                                                     bool stats_qbed, std::string &trailing_panic);
+std::vector<std::string> break_paf_on_indels_stats_text(Engine &eng, const std::vector<PafRecord> &paf_recs, uint32_t break_length, bool stats_qbed,
+                                                        std::string &trailing_panic);
 // the same two routes as a pipeline over chunks of a big plain file (a few host threads, each with its own context on `device`):
 // the sink receives the chunks' outputs in file order while later chunks are still being read / clipped / printed.  A chunk's text
 // is contig-major within the chunk (runs); false = not applicable or a line needs the general parser (pipeline_started(): the

@@ -38,8 +38,8 @@ static int usage() {
     fprintf(stderr,
             "usage: rb [--bsearch modern|legacy] [--device N] [--gpus N] <subcommand> ...\n"
             "  stats [-q|--qbed] [-p|--paf] <PAF or BAM>\n"
-            "  liftover -b|--bed <BED> [-q|--qbed] [-l|--largest] [PAF]\n"
-            "  break-paf [-m|--max-size 100] [PAF]\n"
+            "  liftover -b|--bed <BED> [-q|--qbed] [-l|--largest] [--stats|--stats-qbed] [PAF]\n"
+            "  break-paf [-m|--max-size 100] [--stats|--stats-qbed] [PAF]\n"
             "  trim-paf [-m|--match-score 1] [-d|--diff-score 1] [-i|--indel-score 1] [-r|--remove-contained] [PAF]\n"
             "  invert [PAF]\n"
             "  orient [-s|--scaffold] [-i|--insert 1000000] [PAF]\n"
@@ -47,6 +47,9 @@ static int usage() {
             "  nucfreq [-r|--region chr:st-en] [-b|--bed <BED>] [-s|--small] <BAM>\n"
             "--gpus N: the PAF records in N shards, one worker process per GPU (liftover, break-paf, stats --paf, invert: contiguous\n"
             "          runs of lines; trim-paf: ranges of the sorted query names); the output is the single-GPU output byte for byte.\n"
+            "--stats / --stats-qbed (liftover, break-paf; this engine's own flags, like --gpus and --bsearch): print what\n"
+            "          `rb <cmd> ... | rb stats --paf` (--stats-qbed: `... | rb stats --paf --qbed`) prints, from the clips on the device:\n"
+            "          no PAF text in between.  -q keeps its liftover meaning beside either.  Not with --gpus N > 1 or --largest.\n"
             "Every other rustybam subcommand is outside this engine's scope.\n");
     return 2;
 }
@@ -899,6 +902,7 @@ int main(int argc, char **argv) {
     }
     std::string paf_path = "-", bed_path;
     bool qbed = false, largest = false, remove_contained = false, is_paf = false;
+    int stats_mode = 0; // liftover / break-paf: 1 = --stats, 2 = --stats-qbed
     int ms = 1, ds = 1, is = 1;
     uint32_t max_size = 100;
     uint64_t paired_len = 0, min_aln = 0, min_query = 0, insert = 1000000;
@@ -917,6 +921,8 @@ int main(int argc, char **argv) {
         else if (s == "--aln" || (s == "-a" && filter)) min_aln = strtoull(next(), nullptr, 10);
         else if (s == "--insert" || (s == "-i" && orient)) insert = strtoull(next(), nullptr, 10);
         else if (s == "--scaffold" || (s == "-s" && orient)) do_scaffold = true;
+        else if (s == "--stats") stats_mode = 1;
+        else if (s == "--stats-qbed") stats_mode = 2;
         else if (s == "-p" || s == "--paf") is_paf = true;
         else if (s == "-q" || s == "--qbed") qbed = true;
         else if (s == "-l" || s == "--largest") largest = true;
@@ -927,6 +933,16 @@ int main(int argc, char **argv) {
         else if (s == "-d" || s == "--diff-score") ds = atoi(next());
         else if (s == "-i" || s == "--indel-score") is = atoi(next());
         else paf_path = s;
+    }
+    const bool is_lift = cmd == "liftover" || cmd == "lo", is_brk = cmd == "break-paf" || cmd == "breakpaf" || cmd == "bp";
+    if (stats_mode && !(is_lift || is_brk)) return usage();
+    if (stats_mode && gpus > 1) {
+        fprintf(stderr, "rb: --stats / --stats-qbed run on one GPU: not with --gpus %d\n", gpus);
+        return 2;
+    }
+    if (stats_mode && largest) {
+        fprintf(stderr, "rb: --stats / --stats-qbed do not combine with --largest\n");
+        return 2;
     }
     if (gpus > 1) {
         const bool lift = cmd == "liftover" || cmd == "lo", brk = cmd == "break-paf" || cmd == "breakpaf" || cmd == "bp";
@@ -998,6 +1014,19 @@ int main(int argc, char **argv) {
                 }
                 return o;
             };
+            if (stats_mode) { // what `rb liftover .. | rb stats --paf [--qbed]` prints: the second command's header whatever the first does
+                put(rb::cigar_stats_header(stats_mode == 2));
+                std::vector<std::string> text;
+                std::string panic;
+                if (!(text_path && rb::liftover_stats_file_text(eng, paf_path, rgns, qbed, stats_mode == 2, text, panic))) {
+                    rb::Paf paf = rb::Paf::from_file(eng, paf_path);
+                    text = rb::trim_paf_by_rgns_stats_text(eng, rgns, paf.records, qbed, stats_mode == 2, panic);
+                }
+                lap("liftover --stats", tl);
+                emit(text);
+                if (!panic.empty()) throw rb::Panic(panic);
+                done(0);
+            }
             if (!largest && !qbed && text_path && try_pipelined(device, policy, false, 0, paf_path, rgns)) {
                 lap("liftover (text to text, pipelined)", tl);
                 done(0);
@@ -1062,6 +1091,19 @@ int main(int argc, char **argv) {
                 lap("write", tl);
             }
         } else if (cmd == "break-paf" || cmd == "breakpaf" || cmd == "bp") {
+            if (stats_mode) {
+                put(rb::cigar_stats_header(stats_mode == 2));
+                std::vector<std::string> text;
+                std::string panic;
+                if (!(text_path && rb::break_stats_file_text(eng, paf_path, max_size, stats_mode == 2, text, panic))) {
+                    rb::Paf paf = rb::Paf::from_file(eng, paf_path);
+                    text = rb::break_paf_on_indels_stats_text(eng, paf.records, max_size, stats_mode == 2, panic);
+                }
+                lap("break-paf --stats", tl);
+                emit(text);
+                if (!panic.empty()) throw rb::Panic(panic);
+                done(0);
+            }
             if (text_path && try_pipelined(device, policy, true, max_size, paf_path, std::vector<rb::Region>())) done(0);
             std::vector<std::string> text;
             if (!(text_path && rb::break_file_text(eng, paf_path, max_size, text))) {

@@ -188,6 +188,17 @@ extern "C" hipError_t rb_launch_largest_rec_keys(const rb_norm_row *norm, uint64
 extern "C" hipError_t rb_launch_largest_gather(const rb_hit_row *rows, const uint32_t *out_ops, const uint64_t *sel, uint64_t n_sel, rb_hit_row *sel_rows,
                                                uint32_t *sel_desc, hipStream_t stream);
 
+// ---- k_hitstats.hip: stats of every hit row's clip ----
+struct rb_hitstats_params {
+    const uint32_t *ops;     // the batch's packed ops (descriptor rows point into them)
+    const uint64_t *op_off;  // used as a table of starts only
+    const rb_hit_row *rows;
+    uint64_t n_rows;
+    const uint32_t *out_ops;
+    rb_reduce_row *stats;    // [n_rows] OUT
+};
+extern "C" hipError_t rb_launch_hitstats(const rb_hitstats_params *p, hipStream_t stream);
+
 // ---- k_nucfreq.hip: nucfreq ----
 struct rb_nf_params {
     uint64_t n_reads;
