@@ -128,7 +128,7 @@ def test_declines_irregular_records_one_by_one(ctx, oracle):
             assert [(g[0],) + g[2:] for g in got] == ogot, (mode, max_size)
 
 
-def test_many_pieces_in_several_passes(ctx):
+def test_many_pieces_in_several_passes(ctx, oracle):
     torch, eng, dev = ctx
     # n long indels in one regular record, n + 1 pieces: exactly a pass, one more, several passes, pieces that span segments of the
     # stream (a record of 6000+ ops), long insertions next to long deletions (pieces without reference bases are no pieces)
@@ -151,6 +151,7 @@ def test_many_pieces_in_several_passes(ctx):
         assert cnt1["redo_two_walk"] == 0 and cnt2["redo_two_walk"] == 0
         assert rows1.shape[0] == rows2.shape[0] == n_cut + 1, (n_cut, rows1.shape, rows2.shape)
         assert D1.digest(rows1, out1) == D1.digest(rows2, out2), n_cut
+        assert D1.digest(rows2, out2) == digest_rows(*oracle.break_paf(oracle.Batch(*batch_args(one), one["contig"]), 100)), n_cut
     # long pieces (each keeps its place in an output slot) around a piece of one op at a pass boundary: pieces 30 and 32 then lie
     # in the same slot within one 16-byte group of each other, and belong to different passes
     for tiny_at in (31, 63, 33):
@@ -168,3 +169,4 @@ def test_many_pieces_in_several_passes(ctx):
         rows1, out1, cnt1 = D1.run(max_size=100, policy=BASE | rustybam_amd.BREAK_ONE_WALK, rows_cap=8192)
         assert cnt1["redo_two_walk"] == 0 and rows1.shape[0] == rows2.shape[0] == 71
         assert D1.digest(rows1, out1) == D1.digest(rows2, out2), tiny_at
+        assert D1.digest(rows2, out2) == digest_rows(*oracle.break_paf(oracle.Batch(*batch_args(one), one["contig"]), 100)), tiny_at
