@@ -385,6 +385,48 @@ int rb_dev_largest(rb_ctx *ctx, const rb_hit_row *rows, uint64_t n_rows, const u
 int rb_dev_stats_rows(rb_ctx *ctx, const rb_batch_view *batch, const rb_hit_row *rows, uint64_t n_rows, const uint32_t *out_ops,
                       rb_reduce_row *stats /* [n_rows] OUT */);
 
+/* ---- the hit rows of a clip call as a batch (`rb break-paf .. | rb liftover ..` without the text in between) ---- *
+ * The second command's Paf::from_file over what the first one printed: every row of rb_dev_liftover / rb_dev_break with status RB_ST_OK
+ * becomes one record ("piece") of a new dense batch, in row order (for rb_dev_break: record order then piece order, the order
+ * `rb break-paf` prints).  Rows of any other status produce nothing (the reference's None); a row with a status >= 16 (a panic) sets
+ * info->declined, the caller replays the file on the record route.
+ *   piece p of row k:  new_ops[new_op_off[p] .. new_op_off[p + 1]) = the clip's ops, found as rb_dev_stats_rows finds them (plain ops at
+ *       out_ops[out_off ..][out_n]; a descriptor d = out_ops + out_off means src->ops[src->op_off[rec] + d[0] ..][d[1]], for rows without
+ *       RB_HIT_INSIDE the first length replaced by d[2] and the last by d[3] (0 = keep), a one-op clip with both takes d[2] + d[3] - len);
+ *       both forms may occur in one call.  src->op_off[rec] is used as a START only: a batch in RB_LIFT_OP_STARTS form works.
+ *       t_st / t_en / q_st / q_en [p] = the row's; strand / contig [p] = src's at rows[k].rec; parent[p] = rows[k].rec.
+ *       new_op_off is the exclusive prefix of the pieces' op counts, new_op_off[n_pieces] = n_ops: an ordinary batch.
+ *   LENGTHS OF 2^28 AND MORE: a clip's words are copied as words, so a clip that holds RB_OP_CONT words (plain ops the generic kernel
+ *       wrote; the clip kernels write no descriptor over a record that has one) is HANDLED: owner and continuation arrive together.  A
+ *       descriptor's replaced first / last length (d[2], d[3], or d[2] + d[3] - len) of 2^28 and more would need a continuation word the
+ *       piece has no place for: that DECLINES (info->declined != 0; the word written holds the low 28 bits).
+ *   info (device memory, 64 B, written by every call): n_pieces and n_ops are EXACT whatever the capacities; overflow != 0: pieces_cap or
+ *       ops_cap was too small and the outputs are incomplete; declined as above.
+ *   new_ops == NULL: sizes only -- info is written (overflow 0) and nothing else; the other outputs may be NULL, the capacities are ignored.
+ *   CAPACITY (tests/test_gpu_rows_to_batch.py, as tests/test_gpu_capacity.py states it for the clip calls): nothing is written at or behind
+ *       new_ops[ops_cap], the per-piece arrays [pieces_cap], new_op_off[pieces_cap + 1] or the end of the scratch; a short call returns
+ *       RB_OK with overflow set, and a second call with exactly the reported counts fits.
+ *   MEMORY: reads the rows, whole aligned 16-byte groups that hold at least one word of a clip, the 16 bytes of a descriptor, and op_off /
+ *       strand / contig of the rows' records; rows, out_ops, src->ops and new_ops must be 16-byte aligned, out_ops and src->ops readable up
+ *       to the next multiple of four words behind the last clip.  Writes new_ops[0 .. n_ops), the per-piece arrays [0 .. n_pieces),
+ *       new_op_off[0 .. n_pieces], info and the scratch (rb_rows_to_batch_scratch_bytes(n_rows) bytes, 256-byte aligned), nothing else:
+ *       the caller leaves the batch's usual readable slack behind new_ops if it hands the pieces to a clip call.
+ *   Enqueues on the context's stream, does not synchronise.  n_rows == 0 is valid.  Two calls on the same input write the same bytes.
+ * rb_rows_to_batch_shape: the kernel's thresholds, for tests (no device needed): out[0] = ops per step of a row of 16 lanes, out[1] = the
+ *   longest clip a row takes (longer ones are walked by the whole wavefront), out[2] = ops per step of the wavefront. */
+typedef struct rb_pieces_info {
+    uint64_t n_pieces, n_ops;
+    uint32_t overflow;
+    uint32_t declined;
+    uint64_t _reserved[5];
+} rb_pieces_info; /* 64 B */
+size_t rb_rows_to_batch_scratch_bytes(uint64_t n_rows);
+void rb_rows_to_batch_shape(uint32_t out[3]);
+int rb_dev_rows_to_batch(rb_ctx *ctx, const rb_batch_view *src, const rb_hit_row *rows, uint64_t n_rows, const uint32_t *out_ops,
+                         uint64_t pieces_cap, uint64_t ops_cap, uint32_t *new_ops, uint64_t *new_op_off /* [pieces_cap + 1] */,
+                         uint64_t *t_st, uint64_t *t_en, uint64_t *q_st, uint64_t *q_en, uint8_t *strand, uint32_t *contig,
+                         uint32_t *parent /* each [pieces_cap] */, rb_pieces_info *info, void *scratch);
+
 /* ---- break-paf -------------------------------------------------------------------------------- *
  * Pieces between indels longer than max_size, record order then piece order; same row shape,
  * rb_hit_row.win = piece ordinal among the candidate windows of the record. */
@@ -577,6 +619,31 @@ int rb_host_break_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, u
                              const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
                              const uint8_t *strand, uint32_t max_size, int bsearch_policy, uint8_t *cig_status, rb_reduce_row *reduce_out,
                              rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, rb_reduce_row **stats, rb_counters *counters);
+/* `rb break-paf --max-size N in.paf | rb liftover --bed W -` (and the same with `| rb stats --paf` behind it) as ONE device pipeline: the
+ * pieces are never printed, read back, parsed or uploaded.  Arguments as rb_host_liftover_text / rb_host_liftover_stats_text plus max_size;
+ * RB_LIFT_QBED is refused (RB_E_INVALID).  Flow: parse, rb_dev_scan_records, rb_dev_break in descriptor mode, rb_dev_rows_to_batch (the
+ * second command's Paf::from_file), rb_dev_scan_records on the pieces (its aligned_pairs), a plan over the pieces -- contigs in order of
+ * first appearance among the PIECES --, rb_dev_liftover in descriptor mode on the piece batch, then rb_dev_format_cigars or
+ * rb_dev_stats_rows as in the plain wrappers.  The first clip call's rows, descriptors and workspace are freed before the second call
+ * allocates its own: the peak is one liftover call plus the piece batch.
+ * On return rows[k].rec is the PARENT record's index in the input (names, lengths and mapq come from there), (*row_piece)[k] the piece's
+ * ordinal among all pieces (malloc'ed, rb_host_free), rows[k].win the window; a piece's own id is empty (a record read from a file).
+ * reduce_out / norm_out are the INPUT records' rows (the first command's checks).
+ * *declined != 0 (the call returns RB_OK, nothing else is promised; free what came back): the caller replays the file on the record
+ * route -- a status that is not RB_ST_OK in the input's reduce or norm rows, a panic status in a row of either clip call or in a piece's
+ * norm row, a piece whose norm row has RB_F_STRIPPED (its own id would be _TO.<lead>.<trail>), or rb_pieces_info.declined. */
+int rb_host_break_liftover_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
+                                const uint8_t *strand, const uint32_t *contig, uint64_t n_win, const uint32_t *w_contig, const uint64_t *w_st,
+                                const uint64_t *w_en, uint32_t max_size, int bsearch_policy, uint8_t *cig_status, rb_reduce_row *reduce_out,
+                                rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off, uint8_t **row_text,
+                                rb_counters *counters, uint32_t **row_piece, int *declined);
+int rb_host_break_liftover_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                      const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
+                                      const uint8_t *strand, const uint32_t *contig, uint64_t n_win, const uint32_t *w_contig, const uint64_t *w_st,
+                                      const uint64_t *w_en, uint32_t max_size, int bsearch_policy, uint8_t *cig_status, rb_reduce_row *reduce_out,
+                                      rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, rb_reduce_row **stats, rb_counters *counters,
+                                      uint32_t **row_piece, int *declined);
 /* rb_dev_stats_rows on host arrays (the rows and clips of rb_host_liftover / rb_host_break, whose out_ops are dense and whose rows never
  * carry RB_HIT_DESCRIPTOR; descriptor rows work too, through ops / op_off): uploads, runs, downloads.  stats [n_rows] caller-allocated. */
 int rb_host_stats_rows(rb_ctx *ctx, uint64_t n_rec, const uint32_t *ops, const uint64_t *op_off, const rb_hit_row *rows, uint64_t n_rows,

@@ -40,6 +40,8 @@ COUNTERS_DT = np.dtype(
      ("overflow", "<u4"), ("phase", "<u4", 5), ("brk_scratch_short", "<u4"), ("redo_two_walk", "<u4")])
 assert REDUCE_DT.itemsize == 72 and NORM_DT.itemsize == 64 and HIT_DT.itemsize == 64 and COUNTERS_DT.itemsize == 64
 assert PAIR_DT.itemsize == 128
+PIECES_INFO_DT = np.dtype([("n_pieces", "<u8"), ("n_ops", "<u8"), ("overflow", "<u4"), ("declined", "<u4"), ("_reserved", "<u8", 5)])  # rb_pieces_info
+assert PIECES_INFO_DT.itemsize == 64
 
 
 def hit_rows_from(rows):
@@ -107,6 +109,16 @@ def exported_symbols():
         except AttributeError:
             pass
     return out
+
+
+def rows_to_batch_shape():
+    """(ops per step of a row of 16 lanes, longest clip a row takes, ops per step of the wavefront) of rb_dev_rows_to_batch's copy kernel
+    (rb_rows_to_batch_shape: no device needed)"""
+    out = (C.c_uint32 * 3)()
+    f = lib().rb_rows_to_batch_shape
+    f.restype = None
+    f(out)
+    return tuple(int(x) for x in out)
 
 
 def _p(a):
@@ -344,6 +356,69 @@ class Engine:
             self.sync()
             for b in bufs:
                 self.dev_free(b)
+
+    def rows_to_batch_scratch_bytes(self, n_rows):
+        f = self.L.rb_rows_to_batch_scratch_bytes
+        f.restype = C.c_size_t
+        return int(f(C.c_uint64(n_rows)))
+
+    def dev_rows_to_batch(self, view, rows_ptr, n_rows, out_ptr, pieces_cap, ops_cap, new_ops_ptr, new_off_ptr, coord_ptrs, strand_ptr, contig_ptr,
+                          parent_ptr, info_ptr, scratch_ptr):
+        """rb_dev_rows_to_batch on device addresses (coord_ptrs = t_st, t_en, q_st, q_en of the pieces; new_ops_ptr 0: sizes only, the other
+        outputs may then be 0 too); enqueues on the context's stream"""
+        t_st, t_en, q_st, q_en = coord_ptrs if coord_ptrs else (0, 0, 0, 0)
+        v = C.c_void_p
+        self._chk(self.L.rb_dev_rows_to_batch(self.ctx, C.byref(view), v(rows_ptr or 0), C.c_uint64(n_rows), v(out_ptr or 0), C.c_uint64(pieces_cap),
+                                              C.c_uint64(ops_cap), v(new_ops_ptr or 0), v(new_off_ptr or 0), v(t_st or 0), v(t_en or 0), v(q_st or 0),
+                                              v(q_en or 0), v(strand_ptr or 0), v(contig_ptr or 0), v(parent_ptr or 0), v(info_ptr), v(scratch_ptr or 0)),
+                  "rb_dev_rows_to_batch")
+
+    def rows_to_batch(self, ops, op_off, strand, contig, rows, out_ops):
+        """rb_dev_rows_to_batch on host arrays (ops / op_off / strand / contig: the batch the rows came from, op_off a table of starts; rows:
+        HIT_DT; out_ops: what the rows' out_off index): a sizes-only call, then the fill with exactly those sizes -> (dict of the piece
+        batch's arrays ops, op_off, t_st, t_en, q_st, q_en, strand, contig, parent; info PIECES_INFO_DT)"""
+        rows = _arr(rows, HIT_DT)
+
+        def padded(a):  # readable up to the next multiple of four words
+            a = _arr(a, np.uint32)
+            return np.concatenate([a, np.zeros(-len(a) % 4 + 4, np.uint32)])
+        ops, out_ops, op_off = padded(ops), padded(out_ops), _arr(op_off, np.uint64)
+        strand, contig = _arr(strand, np.uint8), _arr(contig, np.uint32)
+        bufs = []
+
+        def dev(n_bytes, src=None):
+            bufs.append(self.dev_alloc(max(n_bytes, 256)))
+            if src is not None and src.nbytes:
+                self._chk(self.L.rb_dev_upload(self.ctx, C.c_void_p(bufs[-1]), _p(src), C.c_size_t(src.nbytes)), "rb_dev_upload")
+            return bufs[-1]
+
+        def down(ptr, n, dt):
+            a = np.zeros(n, dt)
+            if a.nbytes:
+                self._chk(self.L.rb_dev_download(self.ctx, _p(a), C.c_void_p(ptr), C.c_size_t(a.nbytes)), "rb_dev_download")
+            return a
+        try:
+            view = self.batch_view(max(len(op_off) - 1, 0), len(ops), dev(ops.nbytes, ops), dev(op_off.nbytes, op_off), 0, 0, 0, 0,
+                                   dev(strand.nbytes, strand), dev(contig.nbytes, contig))
+            d_rows, d_out, d_info = dev(rows.nbytes, rows), dev(out_ops.nbytes, out_ops), dev(64)
+            d_scr = dev(self.rows_to_batch_scratch_bytes(len(rows)))
+            self.dev_rows_to_batch(view, d_rows, len(rows), d_out, 0, 0, 0, 0, None, 0, 0, 0, d_info, d_scr)
+            info = down(d_info, 1, PIECES_INFO_DT)[0]
+            n_p, n_o = int(info["n_pieces"]), int(info["n_ops"])
+            d_new, d_off = dev(4 * n_o + 128), dev(8 * (n_p + 1))
+            d_c = [dev(8 * n_p) for _ in range(4)]
+            d_s, d_ct, d_par = dev(n_p), dev(4 * n_p), dev(4 * n_p)
+            self.dev_rows_to_batch(view, d_rows, len(rows), d_out, n_p, n_o, d_new, d_off, d_c, d_s, d_ct, d_par, d_info, d_scr)
+            info = down(d_info, 1, PIECES_INFO_DT)[0]
+            b = dict(ops=down(d_new, n_o, np.uint32), op_off=down(d_off, n_p + 1, np.uint64), strand=down(d_s, n_p, np.uint8),
+                     contig=down(d_ct, n_p, np.uint32), parent=down(d_par, n_p, np.uint32))
+            for k, ptr in zip(("t_st", "t_en", "q_st", "q_en"), d_c):
+                b[k] = down(ptr, n_p, np.uint64)
+            return b, info
+        finally:
+            self.sync()
+            for x in bufs:
+                self.dev_free(x)
 
     def largest_scratch_bytes(self, n_keys):
         f = self.L.rb_largest_scratch_bytes

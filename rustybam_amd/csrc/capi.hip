@@ -1634,55 +1634,14 @@ extern "C" int rb_host_format_cigars(rb_ctx *ctx, const uint32_t *ops, uint64_t 
     return RB_OK;
 }
 
-// what rb_host_liftover_largest_text adds to rb_host_liftover_text
-struct largest_text {
-    const uint32_t *win_key;
-    uint64_t n_keys;
-    uint32_t inside_key;
-    int *declined;
-};
-// text in -> text out around the clip kernels; scan_only stops after the record scan (rb_host_scan_text).  lg: liftover --largest -- the hit
-// rows stay on the device, rb_dev_largest picks one per key, and only those rows come back, get format items and are printed
-// stats (rb_host_liftover_stats_text, rb_host_break_stats_text): no text out -- rb_dev_stats_rows runs on the rows and clips where the clip
-// kernels left them, and the rows come back with one reduce row each; row_text_off / row_text are not used
-static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool scan_only, uint64_t n_rec, const uint8_t *text,
-                          uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en,
-                          const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand, const uint32_t *contig, uint64_t n_win,
-                          const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en, int policy, uint8_t *cig_status,
-                          rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off,
-                          uint8_t **row_text, rb_counters *counters, const largest_text *lg = nullptr, rb_reduce_row **stats = nullptr) {
-    if (!ctx || (n_rec && (!cig_off || !cig_end || !cig_status)) || (stats && (lg || scan_only))) return RB_E_INVALID;
-    // liftover --qbed: the wrappers' own bit, taken out before anything reaches rb_dev_liftover
-    const bool qbed = (policy & RB_LIFT_QBED) != 0;
-    policy &= ~RB_LIFT_QBED;
-    if (qbed && (is_break || scan_only)) return fail(ctx, RB_E_INVALID, "RB_LIFT_QBED: only rb_host_liftover_text and rb_host_liftover_largest_text take it");
-    if (lg) *lg->declined = 0;
-    if (stats) *stats = nullptr;
-    if (n_rec == 0) { // an empty file: no rows, no text
-        if (rows) *rows = nullptr;
-        if (n_rows) *n_rows = 0;
-        if (row_text) *row_text = nullptr;
-        if (row_text_off) {
-            *row_text_off = (uint64_t *)calloc(2, 8);
-            if (!*row_text_off) return fail(ctx, RB_E_NOMEM, "malloc");
-        }
-        if (counters) memset(counters, 0, sizeof *counters);
-        return RB_OK;
-    }
-    rb_hit_row *rows_dummy = nullptr;
-    uint64_t n_dummy = 0, *off_dummy = nullptr;
-    uint8_t *text_dummy = nullptr;
-    if (scan_only) rows = &rows_dummy, n_rows = &n_dummy, row_text_off = &off_dummy, row_text = &text_dummy;
-    if (stats) row_text_off = &off_dummy, row_text = &text_dummy;
-    if (!rows || !n_rows || !row_text_off || !row_text) return RB_E_INVALID;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    *rows = nullptr;
-    *row_text_off = nullptr;
-    *row_text = nullptr;
-    *n_rows = 0;
-    DevBatch b(ctx);
+// The front of the text wrappers: the records' `cg:Z:` values parsed on the device, and the batch b.v made of them and of the uploaded
+// columns (op_off: its offsets on the host; *contig NULL: every record on contig 0, zc then holds the ids).  *parsed = false: a CIGAR did
+// not parse (cig_status says which), nothing else was done.
+static int text_to_batch(rb_ctx *ctx, DevBatch &b, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end,
+                         const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand,
+                         const uint32_t **contig, std::vector<uint32_t> &zc, uint8_t *cig_status, std::vector<uint64_t> &op_off, bool *parsed, double &tl) {
     int rc;
-    double tl = rb_now_s();
+    *parsed = false;
     // ---- text -> ops on the device ----
     uint8_t *d_text = nullptr, *d_status = nullptr;
     const uint64_t *d_coff = nullptr, *d_cend = nullptr;
@@ -1707,15 +1666,14 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
     if ((rc = rb_dev_parse_cigars(ctx, d_text, d_coff, d_cend, n_rec, d_opoff, d_ops, ops_cap, d_status, d_scr))) return rc;
     if (n_rec && (rc = rb_dev_download(ctx, cig_status, d_status, (size_t)n_rec))) return rc;
     for (uint64_t r = 0; r < n_rec; r++)
-        if (cig_status[r] != RB_TEXT_OK) return RB_OK; // the caller reports it (the reference panics at paf.rs:399)
-    std::vector<uint64_t> op_off((size_t)n_rec + 1, 0);
+        if (cig_status[r] != RB_TEXT_OK) return RB_OK; // (*parsed stays false) the caller reports it (the reference panics at paf.rs:399)
+    op_off.assign((size_t)n_rec + 1, 0);
     if ((rc = rb_dev_download(ctx, op_off.data(), d_opoff, ((size_t)n_rec + 1) * 8))) return rc;
     rb_lap("parse cigars + op_off D2H", tl);
     // ---- the batch, device-resident ----
-    std::vector<uint32_t> zc;
-    if (!contig) {
+    if (!*contig) {
         zc.assign(n_rec, 0);
-        contig = zc.data();
+        *contig = zc.data();
     }
     b.v.n_rec = n_rec;
     b.v.n_ops = op_off[n_rec];
@@ -1726,67 +1684,23 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
     if ((rc = b.up(q_st, (size_t)n_rec, &b.v.q_st))) return rc;
     if ((rc = b.up(q_en, (size_t)n_rec, &b.v.q_en))) return rc;
     if ((rc = b.up(strand, (size_t)n_rec, &b.v.strand))) return rc;
-    if ((rc = b.up(contig, (size_t)n_rec, &b.v.contig))) return rc;
-    rb_norm_row *d_norm = nullptr;
-    rb_reduce_row *d_red = nullptr;
-    if ((rc = b.alloc(n_rec, &d_norm))) return rc;
-    if (reduce_out && (rc = b.alloc(n_rec, &d_red))) return rc;
-    if (qbed) {
-        // Paf::from_file's check_integrity (paf.rs:70) is the record's as read: reduce rows first, from the unswapped batch.  Then the ops
-        // are swapped where they lie (the descriptors of the clip index this array), the t and q columns change places, and the scan for
-        // the norm rows -- aligned_pairs' remove_trailing_indels -- sees the swapped record.
-        if (reduce_out && (rc = rb_dev_scan_records(ctx, &b.v, d_red, nullptr))) return rc;
-        if ((rc = rb_dev_swap(ctx, &b.v, d_ops))) return rc;
-        std::swap(b.v.t_st, b.v.q_st), std::swap(b.v.t_en, b.v.q_en);
-        if ((rc = rb_dev_scan_records(ctx, &b.v, nullptr, d_norm))) return rc;
-    } else if ((rc = rb_dev_scan_records(ctx, &b.v, d_red, d_norm))) {
-        return rc;
-    }
-    if (norm_out && (rc = rb_dev_download(ctx, norm_out, d_norm, n_rec * sizeof(rb_norm_row)))) return rc;
-    if (reduce_out && (rc = rb_dev_download(ctx, reduce_out, d_red, n_rec * sizeof(rb_reduce_row)))) return rc;
-    rb_lap("scan_records + rows D2H", tl);
-    if (scan_only) return RB_OK;
-    rb_counters hc;
-    rb_hit_row *d_rows = nullptr;
-    uint32_t *d_out = nullptr;
-    rc = lift_sized(ctx, b, op_off.data(), contig, n_win, w_contig, w_st, w_en, d_norm, is_break, max_size, policy | RB_LIFT_DESCRIPTORS,
-                    &d_rows, &d_out, &hc, tl);
-    uint64_t nr = hc.n_hits;
-    const rb_hit_row *d_take = d_rows; // the rows that go to the host, and the descriptor of row k of them at d_take_desc[4k]
-    const uint32_t *d_take_desc = d_out;
-    if (!rc && lg) { // ---- one row per key ----
-        const uint32_t *d_wkey = nullptr;
-        uint32_t *d_rkey = nullptr, *d_sdesc = nullptr;
-        uint64_t *d_sel = nullptr, *d_lout = nullptr; // d_lout: out[0], out[1] of rb_dev_largest, then the worst panic status of all rows
-        rb_hit_row *d_srows = nullptr;
-        void *d_lscr = nullptr;
-        uint64_t lout[3] = {0, 0, 0};
-        rc = b.up(lg->win_key, (size_t)n_win, &d_wkey);
-        if (!rc) rc = b.alloc((size_t)n_rec, &d_rkey);
-        if (!rc) rc = b.alloc((size_t)lg->n_keys + 1, &d_sel);
-        if (!rc) rc = b.alloc(3, &d_lout);
-        if (!rc) rc = b.alloc(rb_largest_scratch_bytes(lg->n_keys), (uint8_t **)&d_lscr);
-        if (!rc && rb_launch_largest_rec_keys(d_norm, n_rec, lg->inside_key, d_rkey, ctx->stream) != hipSuccess) rc = fail(ctx, RB_E_HIP, "rb_launch_largest_rec_keys");
-        if (!rc) rc = largest_impl(ctx, d_rows, nr, d_wkey, d_rkey, lg->n_keys, d_sel, d_lout, d_lscr, (uint32_t *)(d_lout + 2));
-        if (!rc) rc = rb_dev_download(ctx, lout, d_lout, sizeof lout);
-        if (rc) return rc;
-        // every window key is inside the key space (checked by the caller of this function), so a row left out is an INSIDE row of a
-        // stripped record; a panic status anywhere is the reference's panic inside trim_paf_by_rgns, before it selects anything
-        if ((uint32_t)lout[2] != 0 || lout[1] != 0) {
-            *lg->declined = (uint32_t)lout[2] != 0 ? 2 : 1;
-            return RB_OK;
-        }
-        nr = lout[0];
-        rc = b.alloc((size_t)nr + 1, &d_srows);
-        if (!rc) rc = b.alloc((size_t)nr * 4 + 4, &d_sdesc);
-        if (!rc && rb_launch_largest_gather(d_rows, d_out, d_sel, nr, d_srows, d_sdesc, ctx->stream) != hipSuccess) rc = fail(ctx, RB_E_HIP, "rb_launch_largest_gather");
-        d_take = d_srows, d_take_desc = d_sdesc;
-        rb_lap("largest + gather", tl);
-    }
+    if ((rc = b.up(*contig, (size_t)n_rec, &b.v.contig))) return rc;
+    *parsed = true;
+    return RB_OK;
+}
+
+// The tail of the text wrappers: the hit rows of a clip call in descriptor mode on the device-resident batch `v` (op_off: its offsets on the
+// host) go to the host -- with the stats of every row's clip where it lies (stats != NULL: rb_dev_stats_rows, no text), or with the clipped
+// CIGAR of every row printed on the device (rb_dev_format_cigars).  d_rows / d_out: all rows and the clip call's out_ops; d_take /
+// d_take_desc: the rows that are printed and the descriptor of row k of them at d_take_desc[4k] (the same two unless --largest selected).
+// plain_ops: v.ops hold no continuation words.  rc: what the calls in front returned (nothing is done if it is not RB_OK).
+static int lift_text_tail(rb_ctx *ctx, DevBatch &b, const rb_batch_view &v, const uint64_t *op_off, int rc, const rb_hit_row *d_rows, const uint32_t *d_out,
+                          const rb_hit_row *d_take, const uint32_t *d_take_desc, uint64_t nr, const rb_counters &hc, bool plain_ops, rb_hit_row **rows,
+                          uint64_t *n_rows, uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters, rb_reduce_row **stats, double &tl) {
     if (stats) { // ---- the stats of every row's clip where it lies; rows and stats to the host, no text ----
         rb_reduce_row *d_stats = nullptr;
         if (!rc) rc = b.alloc((size_t)nr + 1, &d_stats);
-        if (!rc) rc = rb_dev_stats_rows(ctx, &b.v, d_rows, nr, d_out, d_stats);
+        if (!rc) rc = rb_dev_stats_rows(ctx, &v, d_rows, nr, d_out, d_stats);
         if (!rc) {
             *rows = (rb_hit_row *)malloc((size_t)(nr + 1) * sizeof(rb_hit_row));
             *stats = (rb_reduce_row *)malloc((size_t)(nr + 1) * sizeof(rb_reduce_row));
@@ -1846,11 +1760,11 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
         if (!rc && nr) rc = rb_dev_upload(ctx, d_first, first.data(), (size_t)nr * 8);
         if (!rc && nr) rc = rb_dev_upload(ctx, d_cnt3, c3.data(), (size_t)nr * 12);
         if (!rc) rc = rb_ctx_sync(ctx);
-        if (!rc) rc = format_cigars_impl(ctx, d_ops, d_out, nr, d_first, d_cnt3, d_cnt3 + nr, d_cnt3 + 2 * nr, d_toff, nullptr, 0, d_scr2, false, true);
+        if (!rc) rc = format_cigars_impl(ctx, v.ops, d_out, nr, d_first, d_cnt3, d_cnt3 + nr, d_cnt3 + 2 * nr, d_toff, nullptr, 0, d_scr2, false, plain_ops);
         if (!rc) rc = rb_dev_download(ctx, *row_text_off, d_toff, ((size_t)nr + 1) * 8);
         const uint64_t bytes = rc ? 0 : (*row_text_off)[nr];
         if (!rc) rc = b.alloc((size_t)bytes + 16, &d_rtext);
-        if (!rc) rc = format_cigars_impl(ctx, d_ops, d_out, nr, d_first, d_cnt3, d_cnt3 + nr, d_cnt3 + 2 * nr, d_toff, d_rtext, bytes, d_scr2, true, true);
+        if (!rc) rc = format_cigars_impl(ctx, v.ops, d_out, nr, d_first, d_cnt3, d_cnt3 + nr, d_cnt3 + 2 * nr, d_toff, d_rtext, bytes, d_scr2, true, plain_ops);
         if (!rc) {
             *row_text = (uint8_t *)malloc((size_t)bytes + 16);
             if (!*row_text) rc = fail(ctx, RB_E_NOMEM, "malloc(%llu text bytes)", (unsigned long long)bytes);
@@ -1869,6 +1783,121 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
         *rows = nullptr, *row_text_off = nullptr, *row_text = nullptr;
     }
     return rc;
+}
+
+// what rb_host_liftover_largest_text adds to rb_host_liftover_text
+struct largest_text {
+    const uint32_t *win_key;
+    uint64_t n_keys;
+    uint32_t inside_key;
+    int *declined;
+};
+// text in -> text out around the clip kernels; scan_only stops after the record scan (rb_host_scan_text).  lg: liftover --largest -- the hit
+// rows stay on the device, rb_dev_largest picks one per key, and only those rows come back, get format items and are printed
+// stats (rb_host_liftover_stats_text, rb_host_break_stats_text): no text out -- rb_dev_stats_rows runs on the rows and clips where the clip
+// kernels left them, and the rows come back with one reduce row each; row_text_off / row_text are not used
+static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool scan_only, uint64_t n_rec, const uint8_t *text,
+                          uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en,
+                          const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand, const uint32_t *contig, uint64_t n_win,
+                          const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en, int policy, uint8_t *cig_status,
+                          rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off,
+                          uint8_t **row_text, rb_counters *counters, const largest_text *lg = nullptr, rb_reduce_row **stats = nullptr) {
+    if (!ctx || (n_rec && (!cig_off || !cig_end || !cig_status)) || (stats && (lg || scan_only))) return RB_E_INVALID;
+    // liftover --qbed: the wrappers' own bit, taken out before anything reaches rb_dev_liftover
+    const bool qbed = (policy & RB_LIFT_QBED) != 0;
+    policy &= ~RB_LIFT_QBED;
+    if (qbed && (is_break || scan_only)) return fail(ctx, RB_E_INVALID, "RB_LIFT_QBED: only rb_host_liftover_text and rb_host_liftover_largest_text take it");
+    if (lg) *lg->declined = 0;
+    if (stats) *stats = nullptr;
+    if (n_rec == 0) { // an empty file: no rows, no text
+        if (rows) *rows = nullptr;
+        if (n_rows) *n_rows = 0;
+        if (row_text) *row_text = nullptr;
+        if (row_text_off) {
+            *row_text_off = (uint64_t *)calloc(2, 8);
+            if (!*row_text_off) return fail(ctx, RB_E_NOMEM, "malloc");
+        }
+        if (counters) memset(counters, 0, sizeof *counters);
+        return RB_OK;
+    }
+    rb_hit_row *rows_dummy = nullptr;
+    uint64_t n_dummy = 0, *off_dummy = nullptr;
+    uint8_t *text_dummy = nullptr;
+    if (scan_only) rows = &rows_dummy, n_rows = &n_dummy, row_text_off = &off_dummy, row_text = &text_dummy;
+    if (stats) row_text_off = &off_dummy, row_text = &text_dummy;
+    if (!rows || !n_rows || !row_text_off || !row_text) return RB_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    *rows = nullptr;
+    *row_text_off = nullptr;
+    *row_text = nullptr;
+    *n_rows = 0;
+    DevBatch b(ctx);
+    int rc;
+    double tl = rb_now_s();
+    std::vector<uint64_t> op_off;
+    std::vector<uint32_t> zc;
+    bool parsed = false;
+    if ((rc = text_to_batch(ctx, b, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, &contig, zc, cig_status, op_off, &parsed, tl))) return rc;
+    if (!parsed) return RB_OK;
+    uint32_t *d_ops = (uint32_t *)b.v.ops;
+    rb_norm_row *d_norm = nullptr;
+    rb_reduce_row *d_red = nullptr;
+    if ((rc = b.alloc(n_rec, &d_norm))) return rc;
+    if (reduce_out && (rc = b.alloc(n_rec, &d_red))) return rc;
+    if (qbed) {
+        // Paf::from_file's check_integrity (paf.rs:70) is the record's as read: reduce rows first, from the unswapped batch.  Then the ops
+        // are swapped where they lie (the descriptors of the clip index this array), the t and q columns change places, and the scan for
+        // the norm rows -- aligned_pairs' remove_trailing_indels -- sees the swapped record.
+        if (reduce_out && (rc = rb_dev_scan_records(ctx, &b.v, d_red, nullptr))) return rc;
+        if ((rc = rb_dev_swap(ctx, &b.v, d_ops))) return rc;
+        std::swap(b.v.t_st, b.v.q_st), std::swap(b.v.t_en, b.v.q_en);
+        if ((rc = rb_dev_scan_records(ctx, &b.v, nullptr, d_norm))) return rc;
+    } else if ((rc = rb_dev_scan_records(ctx, &b.v, d_red, d_norm))) {
+        return rc;
+    }
+    if (norm_out && (rc = rb_dev_download(ctx, norm_out, d_norm, n_rec * sizeof(rb_norm_row)))) return rc;
+    if (reduce_out && (rc = rb_dev_download(ctx, reduce_out, d_red, n_rec * sizeof(rb_reduce_row)))) return rc;
+    rb_lap("scan_records + rows D2H", tl);
+    if (scan_only) return RB_OK;
+    rb_counters hc;
+    rb_hit_row *d_rows = nullptr;
+    uint32_t *d_out = nullptr;
+    rc = lift_sized(ctx, b, op_off.data(), contig, n_win, w_contig, w_st, w_en, d_norm, is_break, max_size, policy | RB_LIFT_DESCRIPTORS,
+                    &d_rows, &d_out, &hc, tl);
+    uint64_t nr = hc.n_hits;
+    const rb_hit_row *d_take = d_rows; // the rows that go to the host, and the descriptor of row k of them at d_take_desc[4k]
+    const uint32_t *d_take_desc = d_out;
+    if (!rc && lg) { // ---- one row per key ----
+        const uint32_t *d_wkey = nullptr;
+        uint32_t *d_rkey = nullptr, *d_sdesc = nullptr;
+        uint64_t *d_sel = nullptr, *d_lout = nullptr; // d_lout: out[0], out[1] of rb_dev_largest, then the worst panic status of all rows
+        rb_hit_row *d_srows = nullptr;
+        void *d_lscr = nullptr;
+        uint64_t lout[3] = {0, 0, 0};
+        rc = b.up(lg->win_key, (size_t)n_win, &d_wkey);
+        if (!rc) rc = b.alloc((size_t)n_rec, &d_rkey);
+        if (!rc) rc = b.alloc((size_t)lg->n_keys + 1, &d_sel);
+        if (!rc) rc = b.alloc(3, &d_lout);
+        if (!rc) rc = b.alloc(rb_largest_scratch_bytes(lg->n_keys), (uint8_t **)&d_lscr);
+        if (!rc && rb_launch_largest_rec_keys(d_norm, n_rec, lg->inside_key, d_rkey, ctx->stream) != hipSuccess) rc = fail(ctx, RB_E_HIP, "rb_launch_largest_rec_keys");
+        if (!rc) rc = largest_impl(ctx, d_rows, nr, d_wkey, d_rkey, lg->n_keys, d_sel, d_lout, d_lscr, (uint32_t *)(d_lout + 2));
+        if (!rc) rc = rb_dev_download(ctx, lout, d_lout, sizeof lout);
+        if (rc) return rc;
+        // every window key is inside the key space (checked by the caller of this function), so a row left out is an INSIDE row of a
+        // stripped record; a panic status anywhere is the reference's panic inside trim_paf_by_rgns, before it selects anything
+        if ((uint32_t)lout[2] != 0 || lout[1] != 0) {
+            *lg->declined = (uint32_t)lout[2] != 0 ? 2 : 1;
+            return RB_OK;
+        }
+        nr = lout[0];
+        rc = b.alloc((size_t)nr + 1, &d_srows);
+        if (!rc) rc = b.alloc((size_t)nr * 4 + 4, &d_sdesc);
+        if (!rc && rb_launch_largest_gather(d_rows, d_out, d_sel, nr, d_srows, d_sdesc, ctx->stream) != hipSuccess) rc = fail(ctx, RB_E_HIP, "rb_launch_largest_gather");
+        d_take = d_srows, d_take_desc = d_sdesc;
+        rb_lap("largest + gather", tl);
+    }
+    return lift_text_tail(ctx, b, b.v, op_off.data(), rc, d_rows, d_out, d_take, d_take_desc, nr, hc, true, rows, n_rows, row_text_off, row_text, counters,
+                          stats, tl);
 }
 
 extern "C" int rb_host_liftover_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
@@ -1929,6 +1958,159 @@ extern "C" int rb_host_scan_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *tex
                                  rb_norm_row *norm_out) {
     return host_lift_text(ctx, false, 0, true, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, nullptr, 0, nullptr,
                           nullptr, nullptr, 0, cig_status, reduce_out, norm_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+// ---- `rb break-paf --max-size N in.paf | rb liftover --bed W -` as one device pipeline (rb_host_break_liftover_text / _stats_text) ------
+// parse, scan, break in descriptor mode, rb_dev_rows_to_batch (the pieces as a batch: the second command's Paf::from_file), scan of the
+// pieces (its check_integrity and aligned_pairs' remove_trailing_indels), a plan over the pieces, liftover in descriptor mode on the piece
+// batch, and the tail of host_lift_text.  The first clip call's rows, descriptors and workspace are freed before the second call sizes its
+// own.  Whatever only the record route prints right -- a panic in either stage, a piece whose own id would be _TO.<..> -- sets *declined.
+static int host_break_lift_text(rb_ctx *ctx, uint32_t max_size, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
+                                const uint8_t *strand, const uint32_t *contig, uint64_t n_win, const uint32_t *w_contig, const uint64_t *w_st,
+                                const uint64_t *w_en, int policy, uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows,
+                                uint64_t *n_rows, uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters, uint32_t **row_piece, int *declined,
+                                rb_reduce_row **stats) {
+    if (!ctx || !rows || !n_rows || !row_piece || !declined || (n_rec && (!cig_off || !cig_end || !cig_status))) return RB_E_INVALID;
+    if (!stats && (!row_text_off || !row_text)) return RB_E_INVALID;
+    if (policy & RB_LIFT_QBED) return fail(ctx, RB_E_INVALID, "RB_LIFT_QBED: the break-paf | liftover pipeline lifts over target windows only");
+    uint64_t *off_dummy = nullptr;
+    uint8_t *text_dummy = nullptr;
+    if (stats) *stats = nullptr, row_text_off = &off_dummy, row_text = &text_dummy;
+    *rows = nullptr, *n_rows = 0, *row_text_off = nullptr, *row_text = nullptr, *row_piece = nullptr, *declined = 0;
+    if (counters) memset(counters, 0, sizeof *counters);
+    auto empty = [&]() -> int { // no record reaches the second command: no rows, no text
+        if (!stats && !(*row_text_off = (uint64_t *)calloc(2, 8))) return fail(ctx, RB_E_NOMEM, "malloc");
+        return RB_OK;
+    };
+    if (n_rec == 0) return empty();
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBatch b(ctx), pb(ctx); // the input batch; the piece batch
+    int rc;
+    double tl = rb_now_s();
+    std::vector<uint64_t> op_off;
+    std::vector<uint32_t> zc;
+    bool parsed = false;
+    // (break-paf's rows come in record order: its plan sees every record on contig 0, as rb_host_break_text's does; the records' own contigs
+    //  go to the device beside the batch, for the pieces to inherit)
+    const uint32_t *no_contig = nullptr, *d_contig = nullptr;
+    if ((rc = text_to_batch(ctx, b, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, &no_contig, zc, cig_status, op_off, &parsed, tl))) return rc;
+    if (!parsed) return RB_OK;
+    if (contig && (rc = b.up(contig, (size_t)n_rec, &d_contig))) return rc;
+    rb_batch_view sv = b.v; // what rb_dev_rows_to_batch reads strand and contig from
+    if (d_contig) sv.contig = d_contig;
+    // ---- the first command: Paf::from_file's check_integrity, aligned_pairs, break_paf_on_indels ----
+    rb_norm_row *d_norm = nullptr;
+    rb_reduce_row *d_red = nullptr;
+    std::vector<rb_norm_row> norm((size_t)n_rec);
+    std::vector<rb_reduce_row> red((size_t)n_rec);
+    if ((rc = b.alloc(n_rec, &d_norm))) return rc;
+    if ((rc = b.alloc(n_rec, &d_red))) return rc;
+    if ((rc = rb_dev_scan_records(ctx, &b.v, d_red, d_norm))) return rc;
+    if ((rc = rb_dev_download(ctx, norm.data(), d_norm, n_rec * sizeof(rb_norm_row)))) return rc;
+    if ((rc = rb_dev_download(ctx, red.data(), d_red, n_rec * sizeof(rb_reduce_row)))) return rc;
+    if (norm_out) memcpy(norm_out, norm.data(), n_rec * sizeof(rb_norm_row));
+    if (reduce_out) memcpy(reduce_out, red.data(), n_rec * sizeof(rb_reduce_row));
+    rb_lap("scan_records + rows D2H", tl);
+    for (uint64_t r = 0; r < n_rec; r++)
+        if (red[r].status != RB_ST_OK || norm[r].status != RB_ST_OK) { // the first command panics: before it prints (from_file), or part-way
+            *declined = 1;
+            return RB_OK;
+        }
+    auto drop = [&](DevBatch &o, void *q) { // a buffer the batch owns, given back now
+        auto it = std::find(o.owned.begin(), o.owned.end(), q);
+        if (it != o.owned.end()) o.owned.erase(it);
+        if (q) (void)rb_dev_free(ctx, q);
+    };
+    rb_counters hc;
+    rb_hit_row *d_rows = nullptr;
+    uint32_t *d_out = nullptr;
+    if ((rc = lift_sized(ctx, b, op_off.data(), no_contig, 0, nullptr, nullptr, nullptr, d_norm, true, max_size, policy | RB_LIFT_DESCRIPTORS, &d_rows, &d_out, &hc, tl)))
+        return rc;
+    // ---- the pieces as a batch ----
+    rb_pieces_info info, *d_info = nullptr;
+    void *d_scr = nullptr;
+    if ((rc = b.alloc(1, &d_info))) return rc;
+    if ((rc = b.alloc(rb_rows_to_batch_scratch_bytes(hc.n_hits), (uint8_t **)&d_scr))) return rc;
+    if ((rc = rb_dev_rows_to_batch(ctx, &sv, d_rows, hc.n_hits, d_out, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_info, d_scr)))
+        return rc;
+    if ((rc = rb_dev_download(ctx, &info, d_info, sizeof info))) return rc;
+    if (info.declined) {
+        *declined = 1;
+        return RB_OK;
+    }
+    const uint64_t n_p = info.n_pieces;
+    if (n_p == 0) return empty();
+    uint32_t *p_ops = nullptr, *p_contig = nullptr, *p_parent = nullptr;
+    uint64_t *p_off = nullptr, *p_c[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint8_t *p_strand = nullptr;
+    rc = pb.alloc((size_t)info.n_ops + 64, &p_ops); // (the clip kernels read whole 128-byte lines of the ops)
+    if (!rc) rc = pb.alloc((size_t)n_p + 2, &p_off);
+    for (int i = 0; i < 4 && !rc; i++) rc = pb.alloc((size_t)n_p, &p_c[i]);
+    if (!rc) rc = pb.alloc((size_t)n_p, &p_strand);
+    if (!rc) rc = pb.alloc((size_t)n_p, &p_contig);
+    if (!rc) rc = pb.alloc((size_t)n_p, &p_parent);
+    if (!rc)
+        rc = rb_dev_rows_to_batch(ctx, &sv, d_rows, hc.n_hits, d_out, n_p, info.n_ops, p_ops, p_off, p_c[0], p_c[1], p_c[2], p_c[3], p_strand, p_contig, p_parent,
+                                  d_info, d_scr);
+    std::vector<uint64_t> pop_off((size_t)n_p + 1);
+    std::vector<uint32_t> pcontig((size_t)n_p), parent((size_t)n_p);
+    if (!rc) rc = rb_dev_download(ctx, &info, d_info, sizeof info);
+    if (!rc && (info.overflow || info.n_pieces != n_p)) rc = fail(ctx, RB_E_CAPACITY, "rb_dev_rows_to_batch: the sized call did not fit");
+    if (!rc) rc = rb_dev_download(ctx, pop_off.data(), p_off, ((size_t)n_p + 1) * 8);
+    if (!rc) rc = rb_dev_download(ctx, pcontig.data(), p_contig, (size_t)n_p * 4);
+    if (!rc) rc = rb_dev_download(ctx, parent.data(), p_parent, (size_t)n_p * 4);
+    if (rc) return rc;
+    drop(b, d_rows), drop(b, d_out), drop(b, d_scr); // the first clip call's arena goes before the second one sizes its own
+    rb_lap("rows -> piece batch", tl);
+    pb.v.n_rec = n_p, pb.v.n_ops = info.n_ops, pb.v.ops = p_ops, pb.v.op_off = p_off;
+    pb.v.t_st = p_c[0], pb.v.t_en = p_c[1], pb.v.q_st = p_c[2], pb.v.q_en = p_c[3], pb.v.strand = p_strand, pb.v.contig = p_contig;
+    // ---- the second command: aligned_pairs of every piece (liftover.rs:119-121), trim_paf_by_rgns ----
+    rb_norm_row *d_pnorm = nullptr;
+    std::vector<rb_norm_row> pnorm((size_t)n_p);
+    if ((rc = pb.alloc(n_p, &d_pnorm))) return rc;
+    if ((rc = rb_dev_scan_records(ctx, &pb.v, nullptr, d_pnorm))) return rc;
+    if ((rc = rb_dev_download(ctx, pnorm.data(), d_pnorm, n_p * sizeof(rb_norm_row)))) return rc;
+    for (uint64_t p = 0; p < n_p; p++)
+        if (pnorm[p].status != RB_ST_OK || (pnorm[p].flags & RB_F_STRIPPED)) { // a panic, or an id of the piece's own (_TO.<..>) that no row carries
+            *declined = 1;
+            return RB_OK;
+        }
+    rb_hit_row *d_rows2 = nullptr;
+    uint32_t *d_out2 = nullptr;
+    rc = lift_sized(ctx, pb, pop_off.data(), pcontig.data(), n_win, w_contig, w_st, w_en, d_pnorm, false, 0, policy | RB_LIFT_DESCRIPTORS, &d_rows2, &d_out2, &hc, tl);
+    rc = lift_text_tail(ctx, pb, pb.v, pop_off.data(), rc, d_rows2, d_out2, d_rows2, d_out2, hc.n_hits, hc, false, rows, n_rows, row_text_off, row_text, counters,
+                        stats, tl);
+    if (rc) return rc;
+    // ---- rows back in the input's terms: rec = the parent record, row_piece = the piece ----
+    *row_piece = (uint32_t *)malloc(((size_t)*n_rows + 1) * 4);
+    if (!*row_piece) return fail(ctx, RB_E_NOMEM, "malloc(row_piece)");
+    for (uint64_t k = 0; k < *n_rows; k++) {
+        rb_hit_row &h = (*rows)[k];
+        if (h.status >= RB_ST_PANIC_NOTFOUND) *declined = 1; // the second command panics inside trim_paf_by_rgns
+        (*row_piece)[k] = h.rec;
+        h.rec = parent[h.rec];
+    }
+    return RB_OK;
+}
+extern "C" int rb_host_break_liftover_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                           const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
+                                           const uint64_t *q_en, const uint8_t *strand, const uint32_t *contig, uint64_t n_win,
+                                           const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en, uint32_t max_size, int policy,
+                                           uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows,
+                                           uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters, uint32_t **row_piece, int *declined) {
+    return host_break_lift_text(ctx, max_size, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig, n_win, w_contig, w_st, w_en,
+                                policy, cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, counters, row_piece, declined, nullptr);
+}
+extern "C" int rb_host_break_liftover_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                                 const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
+                                                 const uint64_t *q_en, const uint8_t *strand, const uint32_t *contig, uint64_t n_win,
+                                                 const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en, uint32_t max_size, int policy,
+                                                 uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows,
+                                                 uint64_t *n_rows, rb_reduce_row **stats, rb_counters *counters, uint32_t **row_piece, int *declined) {
+    if (!stats) return RB_E_INVALID;
+    return host_break_lift_text(ctx, max_size, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig, n_win, w_contig, w_st, w_en,
+                                policy, cig_status, reduce_out, norm_out, rows, n_rows, nullptr, nullptr, counters, row_piece, declined, stats);
 }
 
 extern "C" int rb_host_swap(rb_ctx *ctx, uint64_t n_rec, const uint32_t *ops, const uint64_t *op_off, const uint8_t *strand,
@@ -2082,6 +2264,42 @@ extern "C" int rb_host_stats_rows(rb_ctx *ctx, uint64_t n_rec, const uint32_t *o
     if (!rc) rc = rb_dev_stats_rows(ctx, &b.v, d_rows, n_rows, d_out, d_stats);
     if (!rc && n_rows) rc = rb_dev_download(ctx, stats, d_stats, (size_t)n_rows * sizeof(rb_reduce_row));
     return rc ? rc : rb_ctx_sync(ctx);
+}
+
+// ---- the hit rows of a clip call as a dense batch (k_rows_batch.hip) ----------------------------------
+// scratch of rb_dev_rows_to_batch: [ops per row (n_rows + 1) u64][1 per OK row (n_rows + 1) u64][block sums of the scans]
+static size_t rtb_cnt_bytes(uint64_t n_rows) { return ((size_t)(n_rows + 1) * 8 + 255) & ~(size_t)255; }
+extern "C" size_t rb_rows_to_batch_scratch_bytes(uint64_t n_rows) { return 2 * rtb_cnt_bytes(n_rows) + (rb_scan_block_sums_count(n_rows) + 4) * 8; }
+extern "C" void rb_rows_to_batch_shape(uint32_t out[3]) { out[0] = rb_rtb_row_step(), out[1] = rb_rtb_row_max(), out[2] = rb_rtb_wave_step(); }
+extern "C" int rb_dev_rows_to_batch(rb_ctx *ctx, const rb_batch_view *src, const rb_hit_row *rows, uint64_t n_rows, const uint32_t *out_ops,
+                                    uint64_t pieces_cap, uint64_t ops_cap, uint32_t *new_ops, uint64_t *new_op_off, uint64_t *t_st, uint64_t *t_en,
+                                    uint64_t *q_st, uint64_t *q_en, uint8_t *strand, uint32_t *contig, uint32_t *parent, rb_pieces_info *info,
+                                    void *scratch) {
+    if (!ctx || !src || !info || (n_rows && (!rows || !out_ops || !scratch))) return RB_E_INVALID;
+    if (new_ops && (!new_op_off || !t_st || !t_en || !q_st || !q_en || !strand || !contig || !parent)) return RB_E_INVALID;
+    if ((((uintptr_t)rows | (uintptr_t)out_ops | (uintptr_t)src->ops | (uintptr_t)new_ops) & 15u) != 0)
+        return fail(ctx, RB_E_INVALID, "rb_dev_rows_to_batch: rows, out_ops, the batch's ops and new_ops must be 16-byte aligned");
+    rb_rows_batch_params p;
+    memset(&p, 0, sizeof p);
+    p.ops = src->ops, p.op_off = src->op_off, p.src_strand = src->strand, p.src_contig = src->contig;
+    p.rows = rows, p.n_rows = n_rows, p.out_ops = out_ops;
+    p.pieces_cap = pieces_cap, p.ops_cap = ops_cap;
+    p.cnt_ops = (uint64_t *)scratch;
+    p.cnt_pieces = (uint64_t *)((char *)scratch + rtb_cnt_bytes(n_rows));
+    uint64_t *blk = (uint64_t *)((char *)scratch + 2 * rtb_cnt_bytes(n_rows));
+    p.new_ops = new_ops, p.new_op_off = new_op_off;
+    p.t_st = t_st, p.t_en = t_en, p.q_st = q_st, p.q_en = q_en, p.strand = strand, p.contig = contig, p.parent = parent;
+    p.info = info;
+    HIPCHK(ctx, rb_fill_async(info, 0, sizeof *info, ctx->stream));
+    if (n_rows == 0) {
+        if (new_ops) HIPCHK(ctx, rb_fill_async(new_op_off, 0, 8, ctx->stream));
+        return RB_OK;
+    }
+    HIPCHK(ctx, rb_launch_rows_batch_count(&p, ctx->stream));
+    HIPCHK(ctx, rb_launch_exclusive_scan(p.cnt_ops, n_rows, blk, &info->n_ops, ctx->stream));
+    HIPCHK(ctx, rb_launch_exclusive_scan(p.cnt_pieces, n_rows, blk, &info->n_pieces, ctx->stream));
+    if (new_ops) HIPCHK(ctx, rb_launch_rows_batch_fill(&p, ctx->stream)); // (NULL: sizes only -- info says what the dense batch holds)
+    return RB_OK;
 }
 
 // ---- the box: what this GPU moves at the clip kernel's memory mix, and the clock it holds meanwhile (diagnostics for bench.py) ----

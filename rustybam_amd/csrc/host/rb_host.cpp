@@ -908,7 +908,8 @@ void run_liftover(Engine &eng, const std::vector<Region> &rgns, const std::vecto
     L.contig.swap(b.contig), L.contig_names.swap(b.contig_names);
     for (size_t i = 0; i < L.norm.size(); i++) panic_on(L.norm[i].status, "aligned_pairs", i); // liftover.rs:119-121
 }
-void run_break(Engine &eng, const std::vector<PafRecord> &paf_recs, uint32_t break_length, LiftResult &L) {
+// check = false: a record whose aligned_pairs panics is left to the caller (L.norm says which)
+void run_break(Engine &eng, const std::vector<PafRecord> &paf_recs, uint32_t break_length, LiftResult &L, bool check = true) {
     L.recs = &paf_recs;
     HostBatch b(paf_recs);
     L.norm.resize(b.n());
@@ -918,7 +919,7 @@ void run_break(Engine &eng, const std::vector<PafRecord> &paf_recs, uint32_t bre
                             &L.n_rows, &L.out,
                             &L.n_out, &cnt),
               "rb_host_break");
-    for (size_t i = 0; i < L.norm.size(); i++) panic_on(L.norm[i].status, "aligned_pairs", i); // main.rs:275
+    for (size_t i = 0; check && i < L.norm.size(); i++) panic_on(L.norm[i].status, "aligned_pairs", i); // main.rs:275
 }
 } // namespace
 
@@ -1370,6 +1371,56 @@ bool break_stats_file_text(Engine &eng, const std::string &paf_path, uint32_t br
                            std::string &trailing_panic) {
     const StatsMode st{stats_qbed, &trailing_panic};
     return break_file_text_impl(eng, paf_path, break_length, out_text, &st);
+}
+
+// `rb liftover --break N`, text in -> text out: break-paf, the pieces read back as records and lifted over the windows in one device
+// visit (rb_host_break_liftover_text / _stats_text); a row's names, lengths and mapq are its PARENT record's, a piece's own id is empty.
+// false = take the record route (break_liftover_text / break_liftover_stats_text): two cg tags, a panic in either command, a piece whose
+// id would carry _TO.<..>; nothing was produced.  A panic of the first command's Paf::from_file is thrown.
+bool break_liftover_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, uint32_t break_length, int stats_mode,
+                              std::vector<std::string> &out_text, std::string &trailing_panic) {
+    TextFile &f = *new TextFile; // (one-shot command, as lift_file_text)
+    if (!f.load(paf_path)) return false;
+    double tl = now_s();
+    const size_t n = f.recs.size();
+    std::vector<uint32_t> w_contig(rgns.size());
+    std::vector<uint64_t> w_st(rgns.size()), w_en(rgns.size());
+    for (size_t i = 0; i < rgns.size(); i++) {
+        auto it = f.contig_id.find(std::string_view(rgns[i].name));
+        if (it == f.contig_id.end()) it = f.contig_id.emplace(std::string_view(rgns[i].name), (uint32_t)f.contig_id.size()).first; // no record there
+        w_contig[i] = it->second, w_st[i] = rgns[i].st, w_en[i] = rgns[i].en;
+    }
+    std::vector<uint8_t> cig_status(n ? n : 1);
+    std::vector<rb_reduce_row> red(n);
+    std::vector<rb_norm_row> norm(n);
+    TextRows &R = *new TextRows;
+    uint32_t *row_piece = nullptr;
+    rb_counters cnt;
+    int declined = 0;
+    if (stats_mode)
+        eng.check(rb_host_break_liftover_stats_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
+                                                    f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(), w_contig.data(),
+                                                    w_st.data(), w_en.data(), break_length, eng.bsearch_policy, cig_status.data(), red.data(), norm.data(), &R.rows,
+                                                    &R.n_rows, &R.stats, &cnt, &row_piece, &declined),
+                  "rb_host_break_liftover_stats_text");
+    else
+        eng.check(rb_host_break_liftover_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
+                                              f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(), w_contig.data(),
+                                              w_st.data(), w_en.data(), break_length, eng.bsearch_policy, cig_status.data(), red.data(), norm.data(), &R.rows,
+                                              &R.n_rows, &R.toff, &R.text, &cnt, &row_piece, &declined),
+                  "rb_host_break_liftover_text");
+    rb_host_free(row_piece); // (which piece a row came from is not printed)
+    lap(stats_mode ? "rb_host_break_liftover_stats_text" : "rb_host_break_liftover_text", tl);
+    if (!f.check_loaded(cig_status, red)) return false; // (throws the panics of the first command's Paf::from_file, in its order of checks)
+    if (declined) return false;
+    if (stats_mode) {
+        out_text = stats_lines_of_file(f, R, false, stats_mode == 2, trailing_panic);
+        return true;
+    }
+    const std::vector<rb_norm_row> own_id(n); // (all zero: a piece has no id of its own, and none that was stripped got here)
+    out_text = assemble_lines(f, own_id, R, &rgns);
+    lap("assemble lines", tl);
+    return true;
 }
 
 // ---- liftover / break-paf, text in -> text out, as a PIPELINE over chunks of the file (round 3) ---------------------------------------
@@ -1909,6 +1960,55 @@ std::vector<std::string> break_paf_on_indels_stats_text(Engine &eng, const std::
     LiftResult L;
     run_break(eng, paf_recs, break_length, L);
     return stats_text_of(eng, L, stats_qbed, trailing_panic);
+}
+
+// `rb liftover --break N`, record route: what `rb break-paf --max-size N | rb liftover --bed W -` does, command by command.
+// The first command prints record by record (main.rs:274-280): a record whose aligned_pairs or break_paf_on_indels panics ends its output,
+// and the pieces of the records in front of it still reach the second command (first_panic: the message, for after the second's output).
+// The second command's Paf::from_file reads a piece back with an empty id: the id:Z: tag of the first one's output is an ignored tag
+// (paf.rs:386-404, :425).
+static std::vector<PafRecord> break_pieces_reread(Engine &eng, const std::vector<PafRecord> &paf_recs, uint32_t break_length, std::string &first_panic) {
+    LiftResult L;
+    run_break(eng, paf_recs, break_length, L, false);
+    size_t bad = paf_recs.size();
+    for (size_t i = 0; i < L.norm.size() && bad == paf_recs.size(); i++)
+        if (L.norm[i].status >= RB_ST_PANIC_NOTFOUND) {
+            bad = i;
+            try {
+                panic_on(L.norm[i].status, "aligned_pairs", i);
+            } catch (const Panic &e) {
+                first_panic = e.what();
+            }
+        }
+    uint64_t n_rows = L.n_rows;
+    for (uint64_t k = 0; k < L.n_rows; k++) {
+        if (L.rows[k].rec >= bad) {
+            n_rows = k;
+            break;
+        }
+        if (L.rows[k].status >= RB_ST_PANIC_NOTFOUND) { // break_paf_on_indels of this record panics before any of its pieces is printed
+            bad = L.rows[k].rec;
+            first_panic = "Problem getting index in cigar: record " + std::to_string(L.rows[k].rec + 1);
+            n_rows = k;
+            while (n_rows > 0 && L.rows[n_rows - 1].rec == bad) n_rows--;
+            break;
+        }
+    }
+    std::vector<PafRecord> pieces = rows_to_records(paf_recs, L.norm, L.rows, n_rows, L.out, nullptr);
+    for (PafRecord &p : pieces) p.id.clear();
+    return pieces;
+}
+std::vector<std::string> break_liftover_text(Engine &eng, const std::vector<Region> &rgns, const std::vector<PafRecord> &paf_recs, uint32_t break_length,
+                                             std::string &first_panic) {
+    const std::vector<PafRecord> pieces = break_pieces_reread(eng, paf_recs, break_length, first_panic);
+    if (pieces.empty()) return {};
+    return trim_paf_by_rgns_text(eng, rgns, pieces, false);
+}
+std::vector<std::string> break_liftover_stats_text(Engine &eng, const std::vector<Region> &rgns, const std::vector<PafRecord> &paf_recs, uint32_t break_length,
+                                                   bool stats_qbed, std::string &first_panic, std::string &trailing_panic) {
+    const std::vector<PafRecord> pieces = break_pieces_reread(eng, paf_recs, break_length, first_panic);
+    if (pieces.empty()) return {};
+    return trim_paf_by_rgns_stats_text(eng, rgns, pieces, false, stats_qbed, trailing_panic);
 }
 
 std::vector<Stats> stats_from_paf(Engine &eng, const std::vector<PafRecord> &recs) {

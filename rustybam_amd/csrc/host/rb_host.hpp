@@ -127,6 +127,20 @@ std::vector<std::string> trim_paf_by_rgns_stats_text(Engine &eng, const std::vec
                                                      bool stats_qbed, std::string &trailing_panic);
 std::vector<std::string> break_paf_on_indels_stats_text(Engine &eng, const std::vector<PafRecord> &paf_recs, uint32_t break_length, bool stats_qbed,
                                                         std::string &trailing_panic);
+// `rb liftover --bed W --break N [--stats | --stats-qbed]` (this project's own flag): what `rb break-paf --max-size N in.paf | rb liftover
+// --bed W -` prints (with stats_mode 1 / 2: what `| rb stats --paf [--qbed] -` behind it prints, without the header), the pieces never
+// printed or read back.  The second command sees the printed pieces: their own id is empty again, contigs are ordered by first appearance
+// among the pieces, names, lengths and mapq are the parent record's.
+//   break_liftover_file_text   text in, rb_host_break_liftover_text / _stats_text; false = take the record route, nothing was produced
+//   break_liftover_[stats_]text the record route: break_paf_on_indels, the pieces re-read, trim_paf_by_rgns.  first_panic: the first command
+//                              panicked part-way (main.rs:274-280 prints record by record): what the second command makes of the pieces
+//                              printed by then is returned, the message goes here.  A panic of the second command is thrown.
+bool break_liftover_file_text(Engine &eng, const std::string &paf_path, const std::vector<Region> &rgns, uint32_t break_length, int stats_mode,
+                              std::vector<std::string> &out_text, std::string &trailing_panic);
+std::vector<std::string> break_liftover_text(Engine &eng, const std::vector<Region> &rgns, const std::vector<PafRecord> &paf_recs, uint32_t break_length,
+                                             std::string &first_panic);
+std::vector<std::string> break_liftover_stats_text(Engine &eng, const std::vector<Region> &rgns, const std::vector<PafRecord> &paf_recs, uint32_t break_length,
+                                                   bool stats_qbed, std::string &first_panic, std::string &trailing_panic);
 // the same two routes as a pipeline over chunks of a big plain file (a few host threads, each with its own context on `device`):
 // the sink receives the chunks' outputs in file order while later chunks are still being read / clipped / printed.  A chunk's text
 // is contig-major within the chunk (runs); false = not applicable or a line needs the general parser (pipeline_started(): the

@@ -38,7 +38,7 @@ static int usage() {
     fprintf(stderr,
             "usage: rb [--bsearch modern|legacy] [--device N] [--gpus N] <subcommand> ...\n"
             "  stats [-q|--qbed] [-p|--paf] <PAF or BAM>\n"
-            "  liftover -b|--bed <BED> [-q|--qbed] [-l|--largest] [--stats|--stats-qbed] [PAF]\n"
+            "  liftover -b|--bed <BED> [-q|--qbed] [-l|--largest] [--break N] [--stats|--stats-qbed] [PAF]\n"
             "  break-paf [-m|--max-size 100] [--stats|--stats-qbed] [PAF]\n"
             "  trim-paf [-m|--match-score 1] [-d|--diff-score 1] [-i|--indel-score 1] [-r|--remove-contained] [PAF]\n"
             "  invert [PAF]\n"
@@ -47,6 +47,8 @@ static int usage() {
             "  nucfreq [-r|--region chr:st-en] [-b|--bed <BED>] [-s|--small] <BAM>\n"
             "--gpus N: the PAF records in N shards, one worker process per GPU (liftover, break-paf, stats --paf, invert: contiguous\n"
             "          runs of lines; trim-paf: ranges of the sorted query names); the output is the single-GPU output byte for byte.\n"
+            "--break N (liftover; this engine's own flag): print what `rb break-paf --max-size N PAF | rb liftover -b BED -` prints, the\n"
+            "          pieces never printed or read back.  With --stats / --stats-qbed.  Not with -q, -l or --gpus N > 1.\n"
             "--stats / --stats-qbed (liftover, break-paf; this engine's own flags, like --gpus and --bsearch): print what\n"
             "          `rb <cmd> ... | rb stats --paf` (--stats-qbed: `... | rb stats --paf --qbed`) prints, from the clips on the device:\n"
             "          no PAF text in between.  -q keeps its liftover meaning beside either.  Not with --gpus N > 1 or --largest.\n"
@@ -903,6 +905,8 @@ int main(int argc, char **argv) {
     std::string paf_path = "-", bed_path;
     bool qbed = false, largest = false, remove_contained = false, is_paf = false;
     int stats_mode = 0; // liftover / break-paf: 1 = --stats, 2 = --stats-qbed
+    bool chain = false;     // liftover --break N: break-paf --max-size N in front of the liftover, in one process
+    uint32_t chain_size = 0;
     int ms = 1, ds = 1, is = 1;
     uint32_t max_size = 100;
     uint64_t paired_len = 0, min_aln = 0, min_query = 0, insert = 1000000;
@@ -923,6 +927,7 @@ int main(int argc, char **argv) {
         else if (s == "--scaffold" || (s == "-s" && orient)) do_scaffold = true;
         else if (s == "--stats") stats_mode = 1;
         else if (s == "--stats-qbed") stats_mode = 2;
+        else if (s == "--break") chain = true, chain_size = (uint32_t)strtoul(next(), nullptr, 10);
         else if (s == "-p" || s == "--paf") is_paf = true;
         else if (s == "-q" || s == "--qbed") qbed = true;
         else if (s == "-l" || s == "--largest") largest = true;
@@ -943,6 +948,14 @@ int main(int argc, char **argv) {
     if (stats_mode && largest) {
         fprintf(stderr, "rb: --stats / --stats-qbed do not combine with --largest\n");
         return 2;
+    }
+    if (chain) {
+        const char *why = !is_lift ? "belongs to liftover" : qbed ? "lifts over target windows: not with --qbed" : largest ? "does not combine with --largest"
+                          : gpus > 1 ? "runs on one GPU: not with --gpus N > 1" : nullptr;
+        if (why) {
+            fprintf(stderr, "rb: --break %s\n", why);
+            return 2;
+        }
     }
     if (gpus > 1) {
         const bool lift = cmd == "liftover" || cmd == "lo", brk = cmd == "break-paf" || cmd == "breakpaf" || cmd == "bp";
@@ -1014,6 +1027,21 @@ int main(int argc, char **argv) {
                 }
                 return o;
             };
+            if (chain) { // what `rb break-paf --max-size N in.paf | rb liftover --bed W - [| rb stats --paf [--qbed] -]` prints
+                if (stats_mode) put(rb::cigar_stats_header(stats_mode == 2));
+                std::vector<std::string> text;
+                std::string first_panic, panic;
+                if (!(text_path && rb::break_liftover_file_text(eng, paf_path, rgns, chain_size, stats_mode, text, panic))) {
+                    rb::Paf paf = rb::Paf::from_file(eng, paf_path);
+                    text = stats_mode ? rb::break_liftover_stats_text(eng, rgns, paf.records, chain_size, stats_mode == 2, first_panic, panic)
+                                      : rb::break_liftover_text(eng, rgns, paf.records, chain_size, first_panic);
+                }
+                lap("liftover --break", tl);
+                emit(text);
+                if (!panic.empty()) throw rb::Panic(panic);
+                if (!first_panic.empty()) throw rb::Panic(first_panic); // (the first command's: the second one has printed what reached it)
+                done(0);
+            }
             if (stats_mode) { // what `rb liftover .. | rb stats --paf [--qbed]` prints: the second command's header whatever the first does
                 put(rb::cigar_stats_header(stats_mode == 2));
                 std::vector<std::string> text;

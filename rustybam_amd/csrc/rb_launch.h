@@ -199,6 +199,31 @@ struct rb_hitstats_params {
 };
 extern "C" hipError_t rb_launch_hitstats(const rb_hitstats_params *p, hipStream_t stream);
 
+// ---- k_rows_batch.hip: the hit rows of a clip call as a dense batch ----
+struct rb_rows_batch_params {
+    const uint32_t *ops;      // the source batch's packed ops (descriptor rows point into them)
+    const uint64_t *op_off;   // used as a table of starts only
+    const uint8_t *src_strand;
+    const uint32_t *src_contig;
+    const rb_hit_row *rows;
+    uint64_t n_rows;
+    const uint32_t *out_ops;
+    uint64_t pieces_cap, ops_cap;
+    uint64_t *cnt_ops;        // [n_rows + 1] scratch: ops per row, then their exclusive prefix
+    uint64_t *cnt_pieces;     // [n_rows + 1] scratch: 1 per OK row, then the exclusive prefix (the row's piece)
+    uint32_t *new_ops;
+    uint64_t *new_op_off;
+    uint64_t *t_st, *t_en, *q_st, *q_en;
+    uint8_t *strand;
+    uint32_t *contig, *parent;
+    rb_pieces_info *info;
+};
+extern "C" hipError_t rb_launch_rows_batch_count(const rb_rows_batch_params *p, hipStream_t stream);
+extern "C" hipError_t rb_launch_rows_batch_fill(const rb_rows_batch_params *p, hipStream_t stream);
+extern "C" uint32_t rb_rtb_row_step(void);
+extern "C" uint32_t rb_rtb_wave_step(void);
+extern "C" uint32_t rb_rtb_row_max(void);
+
 // ---- k_nucfreq.hip: nucfreq ----
 struct rb_nf_params {
     uint64_t n_reads;
