@@ -81,8 +81,10 @@ def test_pairs_random(engine, oracle, mode, policy, scores):
 
 @pytest.mark.parametrize("ops_range", [(60, 200), (600, 900), (760, 776)])
 def test_pairs_long_regular_cigars(engine, oracle, ops_range):
-    """the wave-per-pair kernel stages a record 64 ops at a time and takes records of at most 768 ops; longer ones (and their
-    partners) go to the serial kernel: both sides of that limit, several staging steps, both strands"""
+    """regular records of 60 .. 900 ops with random overlaps: the pairs whose overlap leaves the row form's 64- and 128-op regions go to the
+    wave-per-pair kernel, which walks a record 64 ops at a time and stages the ops around the overlap -- at most 192, 1024, 6144 ops in LDS,
+    32768 in a device slab, whatever the record's length; only wider overlaps reach the serial kernel.  Several staging steps, both strands.
+    (The thresholds themselves are pinned by tests/test_gpu_trim_seams.py.)"""
     rng = np.random.default_rng(ops_range[0])
     b, left, right = _pairs_batch(rng, 40, "regular", ops_range=ops_range)
     for scores in ((1, 1, 1), (3, 1, 7)):
