@@ -280,9 +280,17 @@ def test_a_tile_is_cut_around_a_record_it_cannot_take(engine, oracle):
     w = sliding(span=300_000, step=49_999, width=12_000)  # (sparse enough that no tile is cut by its hits)
     # (with the record scan done beforehand the set-up knows which records are irregular; with the FUSED scan it only knows what the peek at a
     #  record's ends shows -- an irregularity in the middle is found behind the stream, and that tile still goes back as a whole)
+    # (under policy 0 the count is exact: tests/tile_seam_util.py restates the set-up's cuts, tests/test_tile_seam_inputs.py holds its count on
+    #  this input -- made there on the host alone -- inside the range asserted here)
+    import tile_seam_util as tsu
+    host_made = tsu.cut_test_input(bad, n_rec)
+    assert all(np.array_equal(b2[k], host_made[k]) for k in b2)
+    orows, _ = oracle.liftover(oracle.Batch(*batch_args(b2), b2["contig"]), *w)
     c = lift_both(engine, oracle, b2, w, 0, "tiles cut around irregular records")
     tiles, back = int(c["phase"][3]), int(c["phase"][4])
     assert tiles > 0 and len(bad) <= back < n_rec // 2, (tiles, back)
+    assert tiles == len(tsu.plan_tiles(b2["op_off"])) and back == tsu.expected_back(oracle, b2, orows), (tiles, back)
     lift_both(engine, oracle, b2, w, FUSED, "irregular records in the middle of tiles, fused scan", expect_back=len(bad))
     c = break_both(engine, oracle, b2, 50, 0, "break-paf, tiles cut around irregular records")
     assert int(c["phase"][3]) > 0 and len(bad) <= int(c["phase"][4]) < n_rec // 2, (int(c["phase"][3]), int(c["phase"][4]))
+    assert int(c["phase"][3]) == tiles and int(c["phase"][4]) == tsu.expected_back(oracle, b2, max_size=50), c["phase"]
