@@ -427,6 +427,62 @@ int rb_dev_rows_to_batch(rb_ctx *ctx, const rb_batch_view *src, const rb_hit_row
                          uint64_t *t_st, uint64_t *t_en, uint64_t *q_st, uint64_t *q_en, uint8_t *strand, uint32_t *contig,
                          uint32_t *parent /* each [pieces_cap] */, rb_pieces_info *info, void *scratch);
 
+/* ---- orient / filter over hit rows (`rb break-paf .. | rb orient - | rb filter .. -` without the text in between) ---- *
+ * <- Paf::orient (paf.rs:114-157, without the order column that only --scaffold reads) and main.rs:242-244: filter_query_len, filter_aln_len,
+ *    filter_aln_pairs (paf.rs:91-111), over the records the second command's Paf::from_file reads: every row of a clip call with status
+ *    RB_ST_OK, in row order.  Neither command touches a CIGAR; both are sums keyed by the record's (target name, query name) pair.  The host
+ *    interns the pairs into dense u32 keys per RECORD (orient appends + or - to every query name of a pair alike, so the pairs in front of the
+ *    filter are the same); the device never sees a string.
+ *   takes part   a row with status RB_ST_OK, rec < n_rec and rec_key[rec] < n_keys.  Rows of another status count nowhere and produce
+ *                nothing; an OK row without a valid key counts nowhere either and DECLINES.
+ *   orient       (RB_PAIRS_ORIENT) per key, over the rows that take part: orient = sum of +(q_en - q_st) where strand[rec] is not '-' and
+ *                -(q_en - q_st) where it is, as i64.  key_flip[key] = orient < 0 (strict: a sum of exactly 0 is not flipped); a flipped row
+ *                gets q_st' = q_len - q_en, q_en' = q_len - q_st (mod 2^64) with q_len = rec_q_len[rec].  The host derives the name suffix
+ *                and the printed strand from key_flip.  Without the bit key_flip is all zero.
+ *   filter       (RB_PAIRS_FILTER) a row passes if rec_q_len[rec] > min_query and t_en - t_st > min_aln; fspan[key] = sum of t_en - t_st
+ *                (u64) over the rows that PASS, and a row is kept if it passes and paired_len < fspan[key].  All three are strict.  Without
+ *                the bit every row that takes part is kept.
+ *   rows_out     [rows_cap] the kept rows, dense, in row order: 64-byte copies, q_st / q_en rewritten where the key is flipped, everything
+ *                else -- out_off and flags too -- as it was, so rb_dev_stats_rows, rb_dev_format_cigars and rb_dev_rows_to_batch work on
+ *                rows_out with the same batch and out_ops.
+ *   info         (device memory, 64 B, written by every call) n_kept is EXACT whatever rows_cap; n_flipped_rows = kept rows of flipped keys;
+ *                overflow != 0: rows_cap was too small, rows_out is incomplete; declined = the OR of RB_PAIRS_DECL_* -- the caller replays
+ *                the file on the record route, the other outputs are still what the rules above say:
+ *                  _PANIC      a row has a status >= 16 (the first command panicked part-way)
+ *                  _KEY        a row with status RB_ST_OK has rec >= n_rec or rec_key[rec] >= n_keys
+ *                  _WRAP       a row of a flipped key has q_len < q_en: the reference's subtraction wraps (or panics, by the build)
+ *                  _ZERO_SPAN  (RB_PAIRS_ORIENT only) a key that has rows has a total t_en - t_st of 0: orient divides by it (paf.rs:143).
+ *                              A piece of break-paf never has span 0: a self-check.
+ *   CAPACITY (tests/test_gpu_pairs_rows.py): nothing is written at or behind rows_out[rows_cap], key_flip[n_keys] or the end of the scratch;
+ *       a short rows_cap (0 too: rows_out may then be NULL) returns RB_OK with overflow set, and a second call with exactly n_kept fits.
+ *   MEMORY: reads rows[0 .. n_rows) as whole 16-byte pieces (rows and rows_out must be 16-byte aligned), rec_key / rec_q_len / strand at the
+ *       rows' records, nothing else.  Writes rows_out[0 .. min(n_kept, rows_cap)), key_flip[0 .. n_keys), info and the scratch
+ *       (rb_pairs_scratch_bytes(n_keys, n_rows) bytes, 256-byte aligned; the sums in it are zeroed by the call itself on the stream, every time).
+ *   Enqueues on the context's stream, does not synchronise.  n_rows == 0 and n_keys == 0 are valid; n_rows must be below 2^32 (RB_E_INVALID
+ *   otherwise: 256 GB of rows).  Two calls on the same input write the same
+ *   bytes: the sums are integers, the same in whatever order they are added, and the rows are placed by an exclusive scan, not by an atomic.
+ * rb_pairs_shape: the sum kernel's shape, for tests (no device needed): out[0] = consecutive rows one wavefront sums (it carries an open run of
+ *   one key from one group of 64 rows to the next), out[1] = rows per workgroup.
+ * rb_host_pairs_rows: the same rules in plain C++ on HOST arrays, no device and no context (the record route's self-check and the tests' second
+ *   opinion); same outputs, byte for byte.  Returns RB_OK or RB_E_INVALID. */
+enum { RB_PAIRS_ORIENT = 1, RB_PAIRS_FILTER = 2 };
+enum { RB_PAIRS_DECL_PANIC = 1, RB_PAIRS_DECL_KEY = 2, RB_PAIRS_DECL_WRAP = 4, RB_PAIRS_DECL_ZERO_SPAN = 8 };
+typedef struct rb_pairs_info {
+    uint64_t n_kept, n_flipped_rows;
+    uint32_t overflow;
+    uint32_t declined;
+    uint64_t _reserved[5];
+} rb_pairs_info; /* 64 B */
+size_t rb_pairs_scratch_bytes(uint64_t n_keys, uint64_t n_rows);
+void rb_pairs_shape(uint32_t out[2]);
+int rb_dev_pairs_rows(rb_ctx *ctx, const rb_hit_row *rows, uint64_t n_rows, const uint32_t *rec_key, const uint64_t *rec_q_len,
+                      const uint8_t *strand /* each [n_rec] */, uint64_t n_rec, uint64_t n_keys, uint32_t mode, uint64_t paired_len,
+                      uint64_t min_aln, uint64_t min_query, rb_hit_row *rows_out, uint64_t rows_cap, uint8_t *key_flip /* [n_keys] OUT */,
+                      rb_pairs_info *info, void *scratch);
+int rb_host_pairs_rows(const rb_hit_row *rows, uint64_t n_rows, const uint32_t *rec_key, const uint64_t *rec_q_len, const uint8_t *strand,
+                       uint64_t n_rec, uint64_t n_keys, uint32_t mode, uint64_t paired_len, uint64_t min_aln, uint64_t min_query,
+                       rb_hit_row *rows_out, uint64_t rows_cap, uint8_t *key_flip, rb_pairs_info *info);
+
 /* ---- break-paf -------------------------------------------------------------------------------- *
  * Pieces between indels longer than max_size, record order then piece order; same row shape,
  * rb_hit_row.win = piece ordinal among the candidate windows of the record. */
@@ -619,6 +675,27 @@ int rb_host_break_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, u
                              const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
                              const uint8_t *strand, uint32_t max_size, int bsearch_policy, uint8_t *cig_status, rb_reduce_row *reduce_out,
                              rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, rb_reduce_row **stats, rb_counters *counters);
+/* `rb break-paf --max-size N in.paf [| rb orient -] [| rb filter --paired-len L --aln A --query Q -]` (rb_host_break_pairs_text) and the same
+ * with `| rb stats --paf [--qbed] -` behind it (rb_host_break_pairs_stats_text) as ONE device pipeline: the pieces are never printed or read
+ * back.  Arguments as rb_host_break_text / rb_host_break_stats_text, then those of rb_dev_pairs_rows: rec_key / rec_q_len [n_rec] (the caller's
+ * interning of the records' (target name, query name) pairs, and column 2), n_keys, mode, the three thresholds; key_flip [n_keys] OUT (host).
+ * Flow: parse, rb_dev_scan_records, rb_dev_break in descriptor mode, rb_dev_pairs_rows on the rows where they lie, then rb_dev_format_cigars or
+ * rb_dev_stats_rows on the kept rows as in the plain wrappers.  The rows that come back are the KEPT rows, dense, in row order, flipped keys'
+ * q_st / q_en rewritten; the caller appends + / - to the query name and turns the strand by key_flip[rec_key[rows[k].rec]].
+ * *declined != 0 (the call returns RB_OK, no rows come back): rb_pairs_info.declined of the call -- the caller replays the file on the record
+ * route. */
+int rb_host_break_pairs_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                             const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
+                             const uint8_t *strand, uint32_t max_size, int bsearch_policy, uint8_t *cig_status, rb_reduce_row *reduce_out,
+                             rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off, uint8_t **row_text,
+                             rb_counters *counters, const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_keys, uint32_t mode,
+                             uint64_t paired_len, uint64_t min_aln, uint64_t min_query, uint8_t *key_flip, int *declined);
+int rb_host_break_pairs_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                   const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
+                                   const uint8_t *strand, uint32_t max_size, int bsearch_policy, uint8_t *cig_status, rb_reduce_row *reduce_out,
+                                   rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, rb_reduce_row **stats, rb_counters *counters,
+                                   const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_keys, uint32_t mode, uint64_t paired_len,
+                                   uint64_t min_aln, uint64_t min_query, uint8_t *key_flip, int *declined);
 /* `rb break-paf --max-size N in.paf | rb liftover --bed W -` (and the same with `| rb stats --paf` behind it) as ONE device pipeline: the
  * pieces are never printed, read back, parsed or uploaded.  Arguments as rb_host_liftover_text / rb_host_liftover_stats_text plus max_size;
  * RB_LIFT_QBED is refused (RB_E_INVALID).  Flow: parse, rb_dev_scan_records, rb_dev_break in descriptor mode, rb_dev_rows_to_batch (the

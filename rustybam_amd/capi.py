@@ -42,6 +42,10 @@ assert REDUCE_DT.itemsize == 72 and NORM_DT.itemsize == 64 and HIT_DT.itemsize =
 assert PAIR_DT.itemsize == 128
 PIECES_INFO_DT = np.dtype([("n_pieces", "<u8"), ("n_ops", "<u8"), ("overflow", "<u4"), ("declined", "<u4"), ("_reserved", "<u8", 5)])  # rb_pieces_info
 assert PIECES_INFO_DT.itemsize == 64
+PAIRS_INFO_DT = np.dtype([("n_kept", "<u8"), ("n_flipped_rows", "<u8"), ("overflow", "<u4"), ("declined", "<u4"), ("_reserved", "<u8", 5)])  # rb_pairs_info
+assert PAIRS_INFO_DT.itemsize == 64
+PAIRS_ORIENT, PAIRS_FILTER = 1, 2  # rb_dev_pairs_rows: mode
+PAIRS_DECL_PANIC, PAIRS_DECL_KEY, PAIRS_DECL_WRAP, PAIRS_DECL_ZERO_SPAN = 1, 2, 4, 8  # rb_pairs_info.declined
 
 
 def hit_rows_from(rows):
@@ -119,6 +123,30 @@ def rows_to_batch_shape():
     f.restype = None
     f(out)
     return tuple(int(x) for x in out)
+
+
+def pairs_shape():
+    """(consecutive rows one wavefront of rb_dev_pairs_rows' sum kernel walks, rows per workgroup) (rb_pairs_shape: no device needed)"""
+    out = (C.c_uint32 * 2)()
+    f = lib().rb_pairs_shape
+    f.restype = None
+    f(out)
+    return tuple(int(x) for x in out)
+
+
+def host_pairs_rows(rows, rec_key, rec_q_len, strand, n_keys, mode, paired_len=0, min_aln=0, min_query=0, rows_cap=None):
+    """rb_host_pairs_rows: orient / filter over hit rows in plain C++ on host arrays (no device, no context)
+    -> (rows_out HIT_DT [min(n_kept, rows_cap)], key_flip u8 [n_keys], info PAIRS_INFO_DT)"""
+    rows, rec_key = _arr(rows, HIT_DT), _arr(rec_key, np.uint32)
+    rec_q_len, strand = _arr(rec_q_len, np.uint64), _arr(strand, np.uint8)
+    cap = len(rows) if rows_cap is None else int(rows_cap)
+    out, flip, info = np.zeros(cap, HIT_DT), np.zeros(int(n_keys), np.uint8), np.zeros(1, PAIRS_INFO_DT)
+    rc = lib().rb_host_pairs_rows(_p(rows), C.c_uint64(len(rows)), _p(rec_key), _p(rec_q_len), _p(strand), C.c_uint64(len(rec_key)), C.c_uint64(int(n_keys)),
+                                  C.c_uint32(mode), C.c_uint64(paired_len), C.c_uint64(min_aln), C.c_uint64(min_query), _p(out), C.c_uint64(cap), _p(flip),
+                                  _p(info))
+    if rc != 0:
+        raise RbError(f"rb_host_pairs_rows failed with {rc}")
+    return out[:min(int(info[0]["n_kept"]), cap)], flip, info[0]
 
 
 def _p(a):
@@ -419,6 +447,53 @@ class Engine:
             self.sync()
             for x in bufs:
                 self.dev_free(x)
+
+    def pairs_scratch_bytes(self, n_keys, n_rows):
+        f = self.L.rb_pairs_scratch_bytes
+        f.restype = C.c_size_t
+        return int(f(C.c_uint64(n_keys), C.c_uint64(n_rows)))
+
+    def dev_pairs_rows(self, rows_ptr, n_rows, rec_key_ptr, rec_q_len_ptr, strand_ptr, n_rec, n_keys, mode, paired_len, min_aln, min_query, rows_out_ptr,
+                       rows_cap, key_flip_ptr, info_ptr, scratch_ptr):
+        """orient / filter over hit rows where they lie (every pointer a device address): the kept rows, dense, to rows_out_ptr[rows_cap], a
+        byte per key to key_flip_ptr, PAIRS_INFO_DT to info_ptr; enqueues on the context's stream"""
+        v = C.c_void_p
+        self._chk(self.L.rb_dev_pairs_rows(self.ctx, v(rows_ptr or 0), C.c_uint64(n_rows), v(rec_key_ptr or 0), v(rec_q_len_ptr or 0), v(strand_ptr or 0),
+                                           C.c_uint64(n_rec), C.c_uint64(n_keys), C.c_uint32(mode), C.c_uint64(paired_len), C.c_uint64(min_aln),
+                                           C.c_uint64(min_query), v(rows_out_ptr or 0), C.c_uint64(rows_cap), v(key_flip_ptr or 0), v(info_ptr),
+                                           v(scratch_ptr or 0)), "rb_dev_pairs_rows")
+
+    def pairs_rows(self, rows, rec_key, rec_q_len, strand, n_keys, mode, paired_len=0, min_aln=0, min_query=0):
+        """rb_dev_pairs_rows on host arrays (rows: HIT_DT): uploads, runs with room for every row, downloads
+        -> (rows_out HIT_DT [n_kept], key_flip u8 [n_keys], info PAIRS_INFO_DT)"""
+        rows, rec_key = _arr(rows, HIT_DT), _arr(rec_key, np.uint32)
+        rec_q_len, strand = _arr(rec_q_len, np.uint64), _arr(strand, np.uint8)
+        n_keys = int(n_keys)
+        bufs = []
+
+        def dev(n_bytes, src=None):
+            bufs.append(self.dev_alloc(max(n_bytes, 256)))
+            if src is not None and src.nbytes:
+                self._chk(self.L.rb_dev_upload(self.ctx, C.c_void_p(bufs[-1]), _p(src), C.c_size_t(src.nbytes)), "rb_dev_upload")
+            return bufs[-1]
+
+        def down(ptr, n, dt):
+            a = np.zeros(n, dt)
+            if a.nbytes:
+                self._chk(self.L.rb_dev_download(self.ctx, _p(a), C.c_void_p(ptr), C.c_size_t(a.nbytes)), "rb_dev_download")
+            return a
+        try:
+            d_rows, d_key, d_ql, d_s = dev(rows.nbytes, rows), dev(rec_key.nbytes, rec_key), dev(rec_q_len.nbytes, rec_q_len), dev(strand.nbytes, strand)
+            d_out, d_flip, d_info = dev(rows.nbytes), dev(n_keys), dev(64)
+            d_scr = dev(self.pairs_scratch_bytes(n_keys, len(rows)))
+            self.dev_pairs_rows(d_rows, len(rows), d_key, d_ql, d_s, len(rec_key), n_keys, mode, paired_len, min_aln, min_query, d_out, len(rows), d_flip,
+                                d_info, d_scr)
+            info = down(d_info, 1, PAIRS_INFO_DT)[0]
+            return down(d_out, int(info["n_kept"]), HIT_DT), down(d_flip, n_keys, np.uint8), info
+        finally:
+            self.sync()
+            for b in bufs:
+                self.dev_free(b)
 
     def largest_scratch_bytes(self, n_keys):
         f = self.L.rb_largest_scratch_bytes

@@ -1792,6 +1792,16 @@ struct largest_text {
     uint32_t inside_key;
     int *declined;
 };
+// what rb_host_break_pairs_text adds to rb_host_break_text: orient / filter over the pieces' rows before they are printed or counted
+struct pairs_text {
+    const uint32_t *rec_key;
+    const uint64_t *rec_q_len;
+    uint64_t n_keys;
+    uint32_t mode;
+    uint64_t paired_len, min_aln, min_query;
+    uint8_t *key_flip; // [n_keys] OUT (host)
+    int *declined;
+};
 // text in -> text out around the clip kernels; scan_only stops after the record scan (rb_host_scan_text).  lg: liftover --largest -- the hit
 // rows stay on the device, rb_dev_largest picks one per key, and only those rows come back, get format items and are printed
 // stats (rb_host_liftover_stats_text, rb_host_break_stats_text): no text out -- rb_dev_stats_rows runs on the rows and clips where the clip
@@ -1801,13 +1811,15 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
                           const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand, const uint32_t *contig, uint64_t n_win,
                           const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en, int policy, uint8_t *cig_status,
                           rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off,
-                          uint8_t **row_text, rb_counters *counters, const largest_text *lg = nullptr, rb_reduce_row **stats = nullptr) {
-    if (!ctx || (n_rec && (!cig_off || !cig_end || !cig_status)) || (stats && (lg || scan_only))) return RB_E_INVALID;
+                          uint8_t **row_text, rb_counters *counters, const largest_text *lg = nullptr, rb_reduce_row **stats = nullptr,
+                          const pairs_text *pr = nullptr) {
+    if (!ctx || (n_rec && (!cig_off || !cig_end || !cig_status)) || (stats && (lg || scan_only)) || (pr && (lg || scan_only || !is_break))) return RB_E_INVALID;
     // liftover --qbed: the wrappers' own bit, taken out before anything reaches rb_dev_liftover
     const bool qbed = (policy & RB_LIFT_QBED) != 0;
     policy &= ~RB_LIFT_QBED;
     if (qbed && (is_break || scan_only)) return fail(ctx, RB_E_INVALID, "RB_LIFT_QBED: only rb_host_liftover_text and rb_host_liftover_largest_text take it");
     if (lg) *lg->declined = 0;
+    if (pr) *pr->declined = 0;
     if (stats) *stats = nullptr;
     if (n_rec == 0) { // an empty file: no rows, no text
         if (rows) *rows = nullptr;
@@ -1896,6 +1908,36 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
         d_take = d_srows, d_take_desc = d_sdesc;
         rb_lap("largest + gather", tl);
     }
+    if (!rc && pr) { // ---- orient / filter: the kept rows, dense, flipped where their pair is; the tail works on those ----
+        const uint32_t *d_key = nullptr;
+        const uint64_t *d_qlen = nullptr;
+        rb_hit_row *d_prows = nullptr;
+        uint32_t *d_pdesc = nullptr;
+        uint8_t *d_flip = nullptr, *d_pscr = nullptr;
+        rb_pairs_info *d_info = nullptr, info;
+        rc = b.up(pr->rec_key, (size_t)n_rec, &d_key);
+        if (!rc) rc = b.up(pr->rec_q_len, (size_t)n_rec, &d_qlen);
+        if (!rc) rc = b.alloc((size_t)nr + 1, &d_prows);
+        if (!rc) rc = b.alloc((size_t)pr->n_keys + 1, &d_flip);
+        if (!rc) rc = b.alloc(1, &d_info);
+        if (!rc) rc = b.alloc(rb_pairs_scratch_bytes(pr->n_keys, nr), &d_pscr);
+        if (!rc) rc = rb_dev_pairs_rows(ctx, d_rows, nr, d_key, d_qlen, b.v.strand, n_rec, pr->n_keys, pr->mode, pr->paired_len, pr->min_aln, pr->min_query,
+                                        d_prows, nr, d_flip, d_info, d_pscr);
+        if (!rc) rc = rb_dev_download(ctx, &info, d_info, sizeof info);
+        if (!rc && pr->n_keys) rc = rb_dev_download(ctx, pr->key_flip, d_flip, (size_t)pr->n_keys);
+        if (rc) return rc;
+        if (info.declined || info.overflow) { // (rows_cap = every row: no overflow) the record route replays the file
+            *pr->declined = info.declined ? (int)info.declined : -1;
+            return RB_OK;
+        }
+        nr = info.n_kept;
+        if (!stats) { // (the text tail wants row k's descriptor at [4k])
+            rc = b.alloc((size_t)nr * 4 + 4, &d_pdesc);
+            if (!rc && rb_launch_pairs_desc(d_prows, nr, d_out, d_pdesc, ctx->stream) != hipSuccess) rc = fail(ctx, RB_E_HIP, "rb_launch_pairs_desc");
+        }
+        d_rows = d_prows, d_take = d_prows, d_take_desc = d_pdesc;
+        rb_lap("pairs rows", tl);
+    }
     return lift_text_tail(ctx, b, b.v, op_off.data(), rc, d_rows, d_out, d_take, d_take_desc, nr, hc, true, rows, n_rows, row_text_off, row_text, counters,
                           stats, tl);
 }
@@ -1951,6 +1993,40 @@ extern "C" int rb_host_break_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8
     if (!stats) return RB_E_INVALID;
     return host_lift_text(ctx, true, max_size, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, nullptr, 0,
                           nullptr, nullptr, nullptr, policy, cig_status, reduce_out, norm_out, rows, n_rows, nullptr, nullptr, counters, nullptr, stats);
+}
+static int break_pairs_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end,
+                            const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand, uint32_t max_size,
+                            int policy, uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows,
+                            uint64_t **row_text_off, uint8_t **row_text, rb_reduce_row **stats, rb_counters *counters, const uint32_t *rec_key,
+                            const uint64_t *rec_q_len, uint64_t n_keys, uint32_t mode, uint64_t paired_len, uint64_t min_aln, uint64_t min_query,
+                            uint8_t *key_flip, int *declined) {
+    if (!ctx || !declined || (n_rec && (!rec_key || !rec_q_len || !strand)) || (n_keys && !key_flip)) return RB_E_INVALID;
+    if (mode & ~(uint32_t)(RB_PAIRS_ORIENT | RB_PAIRS_FILTER)) return fail(ctx, RB_E_INVALID, "mode %u: RB_PAIRS_ORIENT | RB_PAIRS_FILTER", mode);
+    if (n_keys) memset(key_flip, 0, (size_t)n_keys);
+    const pairs_text pr{rec_key, rec_q_len, n_keys, mode, paired_len, min_aln, min_query, key_flip, declined};
+    return host_lift_text(ctx, true, max_size, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, nullptr, 0, nullptr,
+                          nullptr, nullptr, policy, cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, counters, nullptr, stats, &pr);
+}
+extern "C" int rb_host_break_pairs_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                        const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
+                                        const uint8_t *strand, uint32_t max_size, int policy, uint8_t *cig_status, rb_reduce_row *reduce_out,
+                                        rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off, uint8_t **row_text,
+                                        rb_counters *counters, const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_keys, uint32_t mode,
+                                        uint64_t paired_len, uint64_t min_aln, uint64_t min_query, uint8_t *key_flip, int *declined) {
+    return break_pairs_text(ctx, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, max_size, policy, cig_status, reduce_out, norm_out,
+                            rows, n_rows, row_text_off, row_text, nullptr, counters, rec_key, rec_q_len, n_keys, mode, paired_len, min_aln, min_query, key_flip,
+                            declined);
+}
+extern "C" int rb_host_break_pairs_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
+                                              const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
+                                              const uint64_t *q_en, const uint8_t *strand, uint32_t max_size, int policy, uint8_t *cig_status,
+                                              rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, rb_reduce_row **stats,
+                                              rb_counters *counters, const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_keys, uint32_t mode,
+                                              uint64_t paired_len, uint64_t min_aln, uint64_t min_query, uint8_t *key_flip, int *declined) {
+    if (!stats) return RB_E_INVALID;
+    return break_pairs_text(ctx, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, max_size, policy, cig_status, reduce_out, norm_out,
+                            rows, n_rows, nullptr, nullptr, stats, counters, rec_key, rec_q_len, n_keys, mode, paired_len, min_aln, min_query, key_flip,
+                            declined);
 }
 extern "C" int rb_host_scan_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
                                  const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
@@ -2299,6 +2375,90 @@ extern "C" int rb_dev_rows_to_batch(rb_ctx *ctx, const rb_batch_view *src, const
     HIPCHK(ctx, rb_launch_exclusive_scan(p.cnt_ops, n_rows, blk, &info->n_ops, ctx->stream));
     HIPCHK(ctx, rb_launch_exclusive_scan(p.cnt_pieces, n_rows, blk, &info->n_pieces, ctx->stream));
     if (new_ops) HIPCHK(ctx, rb_launch_rows_batch_fill(&p, ctx->stream)); // (NULL: sizes only -- info says what the dense batch holds)
+    return RB_OK;
+}
+
+// ---- orient / filter over hit rows (k_pairs.hip) -------------------------------------------------------
+// scratch of rb_dev_pairs_rows: [orient n_keys i64][tspan n_keys u64][fspan n_keys u64][1 per kept row (n_rows + 1) u64][block sums of the scan]
+static size_t pairs_sum_bytes(uint64_t n_keys) { return ((size_t)n_keys * 8 + 255) & ~(size_t)255; }
+static size_t pairs_cnt_bytes(uint64_t n_rows) { return ((size_t)(n_rows + 1) * 8 + 255) & ~(size_t)255; }
+extern "C" size_t rb_pairs_scratch_bytes(uint64_t n_keys, uint64_t n_rows) {
+    return 3 * pairs_sum_bytes(n_keys) + pairs_cnt_bytes(n_rows) + (rb_scan_block_sums_count(n_rows) + 4) * 8;
+}
+extern "C" void rb_pairs_shape(uint32_t out[2]) { out[0] = rb_pairs_wave_rows(), out[1] = rb_pairs_block_rows(); }
+extern "C" int rb_dev_pairs_rows(rb_ctx *ctx, const rb_hit_row *rows, uint64_t n_rows, const uint32_t *rec_key, const uint64_t *rec_q_len,
+                                 const uint8_t *strand, uint64_t n_rec, uint64_t n_keys, uint32_t mode, uint64_t paired_len, uint64_t min_aln,
+                                 uint64_t min_query, rb_hit_row *rows_out, uint64_t rows_cap, uint8_t *key_flip, rb_pairs_info *info, void *scratch) {
+    if (!ctx || !info || (n_rows && (!rows || !scratch)) || (n_rec && (!rec_key || !rec_q_len || !strand)) || (n_keys && (!key_flip || !scratch)) ||
+        (rows_cap && !rows_out) || (mode & ~(uint32_t)(RB_PAIRS_ORIENT | RB_PAIRS_FILTER)))
+        return RB_E_INVALID;
+    if ((((uintptr_t)rows | (uintptr_t)rows_out) & 15u) != 0) return fail(ctx, RB_E_INVALID, "rb_dev_pairs_rows: rows and rows_out must be 16-byte aligned");
+    if (n_rows >> 32) return fail(ctx, RB_E_INVALID, "rb_dev_pairs_rows: %llu rows (the call counts kept and flipped rows in the halves of one u64: below 2^32)", (unsigned long long)n_rows);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    rb_pairs_params p;
+    memset(&p, 0, sizeof p);
+    char *sc = (char *)scratch;
+    p.rows = rows, p.n_rows = n_rows, p.rec_key = rec_key, p.rec_q_len = rec_q_len, p.strand = strand, p.n_rec = n_rec, p.n_keys = n_keys;
+    p.mode = mode, p.paired_len = paired_len, p.min_aln = min_aln, p.min_query = min_query;
+    p.orient = (unsigned long long *)sc;
+    p.tspan = (unsigned long long *)(sc + pairs_sum_bytes(n_keys));
+    p.fspan = (unsigned long long *)(sc + 2 * pairs_sum_bytes(n_keys));
+    p.cnt = (uint64_t *)(sc + 3 * pairs_sum_bytes(n_keys));
+    p.rows_out = rows_out, p.rows_cap = rows_cap, p.key_flip = key_flip, p.info = info;
+    HIPCHK(ctx, rb_fill_async(info, 0, sizeof *info, ctx->stream));
+    if (n_keys) HIPCHK(ctx, rb_fill_async(sc, 0, 3 * pairs_sum_bytes(n_keys), ctx->stream)); // (every call: nothing of the last one counts)
+    HIPCHK(ctx, rb_launch_pairs(&p, (uint64_t *)(sc + 3 * pairs_sum_bytes(n_keys) + pairs_cnt_bytes(n_rows)), ctx->stream));
+    return RB_OK;
+}
+// the same rules on host arrays, in the reference's order of steps (no device: the record route's self-check, the tests' second opinion)
+extern "C" int rb_host_pairs_rows(const rb_hit_row *rows, uint64_t n_rows, const uint32_t *rec_key, const uint64_t *rec_q_len, const uint8_t *strand,
+                                  uint64_t n_rec, uint64_t n_keys, uint32_t mode, uint64_t paired_len, uint64_t min_aln, uint64_t min_query,
+                                  rb_hit_row *rows_out, uint64_t rows_cap, uint8_t *key_flip, rb_pairs_info *info) {
+    if (!info || (n_rows && !rows) || (n_rec && (!rec_key || !rec_q_len || !strand)) || (n_keys && !key_flip) || (rows_cap && !rows_out) ||
+        (mode & ~(uint32_t)(RB_PAIRS_ORIENT | RB_PAIRS_FILTER)))
+        return RB_E_INVALID;
+    memset(info, 0, sizeof *info);
+    std::vector<int64_t> orient((size_t)n_keys, 0);
+    std::vector<uint64_t> tspan((size_t)n_keys, 0), fspan((size_t)n_keys, 0);
+    std::vector<uint8_t> has((size_t)n_keys, 0), part((size_t)n_rows, 0);
+    const bool do_orient = (mode & RB_PAIRS_ORIENT) != 0, do_filter = (mode & RB_PAIRS_FILTER) != 0;
+    auto passes = [&](const rb_hit_row &h) { return !do_filter || (rec_q_len[h.rec] > min_query && h.t_en - h.t_st > min_aln); };
+    for (uint64_t k = 0; k < n_rows; k++) {
+        const rb_hit_row &h = rows[k];
+        if (h.status >= RB_ST_PANIC_NOTFOUND) info->declined |= RB_PAIRS_DECL_PANIC;
+        if (h.status != RB_ST_OK) continue;
+        if (h.rec >= n_rec || rec_key[h.rec] >= n_keys) {
+            info->declined |= RB_PAIRS_DECL_KEY;
+            continue;
+        }
+        part[k] = 1;
+        const uint32_t key = rec_key[h.rec];
+        has[key] = 1;
+        const uint64_t q = h.q_en - h.q_st;
+        if (do_orient) orient[key] = (int64_t)((uint64_t)orient[key] + (strand[h.rec] == (uint8_t)'-' ? 0 - q : q)); // paf.rs:124-128
+        tspan[key] += h.t_en - h.t_st;
+        if (do_filter && passes(h)) fspan[key] += h.t_en - h.t_st; // paf.rs:97, behind main.rs:242-243
+    }
+    for (uint64_t i = 0; i < n_keys; i++) {
+        key_flip[i] = orient[i] < 0 ? 1 : 0; // paf.rs:146
+        if (do_orient && has[i] && tspan[i] == 0) info->declined |= RB_PAIRS_DECL_ZERO_SPAN; // paf.rs:143
+    }
+    for (uint64_t k = 0; k < n_rows; k++) {
+        if (!part[k]) continue;
+        rb_hit_row h = rows[k];
+        const uint32_t key = rec_key[h.rec];
+        const uint64_t q_len = rec_q_len[h.rec];
+        if (key_flip[key]) {
+            if (q_len < h.q_en) info->declined |= RB_PAIRS_DECL_WRAP;
+            const uint64_t st = q_len - h.q_en, en = q_len - h.q_st; // paf.rs:148-151
+            h.q_st = st, h.q_en = en;
+        }
+        if (!(passes(rows[k]) && (!do_filter || paired_len < fspan[key]))) continue; // paf.rs:100
+        if (info->n_kept < rows_cap) rows_out[info->n_kept] = h;
+        else info->overflow = 1;
+        info->n_kept++;
+        if (key_flip[key]) info->n_flipped_rows++;
+    }
     return RB_OK;
 }
 

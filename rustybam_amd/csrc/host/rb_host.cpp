@@ -1187,12 +1187,22 @@ std::vector<std::string> stats_lines(const rb_hit_row *rows, const rb_reduce_row
     });
     return out_text;
 }
+// `rb break-paf --orient`: what Paf::orient does to the query name and the strand of a record whose (target, query) pair has key_flip set
+// (paf.rs:146-155); the rows carry the flipped coordinates already (rb_dev_pairs_rows).  orient false (a filter alone): nothing changes.
+struct PairNames {
+    const std::vector<uint32_t> *rec_key;
+    const std::vector<uint8_t> *key_flip;
+    bool orient;
+    bool flipped(uint32_t rec) const { return orient && (*key_flip)[(*rec_key)[rec]] != 0; }
+    char strand(uint32_t rec, char s) const { return flipped(rec) ? (s == '+' ? '-' : '+') : s; }
+};
 // a record of a file read by the text route; qbed (liftover --qbed): the swapped record's columns, as assemble_lines prints them
-std::vector<std::string> stats_lines_of_file(const TextFile &f, const TextRows &R, bool qbed, bool stats_qbed, std::string &trailing) {
+std::vector<std::string> stats_lines_of_file(const TextFile &f, const TextRows &R, bool qbed, bool stats_qbed, std::string &trailing, const PairNames *pn = nullptr) {
     return stats_lines(R.rows, R.stats, R.n_rows, stats_qbed, trailing, [&](const rb_hit_row &h, Stats &s) {
         const HeaderOnly &r = f.recs[h.rec];
         std::string q(f.all.data() + r.q_name, r.q_name_n), t(f.all.data() + r.t_name, r.t_name_n);
         s.strand = r.strand;
+        if (pn && pn->orient) q += pn->flipped(h.rec) ? '-' : '+', s.strand = pn->strand(h.rec, r.strand);
         if (qbed) s.q_nm.swap(t), s.q_len = (int64_t)r.t_len, s.r_nm.swap(q), s.r_len = (int64_t)r.q_len;
         else s.q_nm.swap(q), s.q_len = (int64_t)r.q_len, s.r_nm.swap(t), s.r_len = (int64_t)r.t_len;
     });
@@ -1201,7 +1211,7 @@ std::vector<std::string> stats_lines_of_file(const TextFile &f, const TextRows &
 // qbed: the Display of the swapped record -- the line's target columns in front with the row's q_st / q_en (the hit rows are in the swapped
 // frame), then its query columns with the row's t_st / t_en
 std::vector<std::string> assemble_lines(const TextFile &f, const std::vector<rb_norm_row> &norm, const TextRows &R, const std::vector<Region> *rgns,
-                                        RunMarks *marks = nullptr, bool qbed = false) {
+                                        RunMarks *marks = nullptr, bool qbed = false, const PairNames *pn = nullptr) {
     for (uint64_t k = 0; k < R.n_rows; k++)
         if (R.rows[k].status >= RB_ST_PANIC_NOTFOUND) throw Panic("Problem getting index in cigar: record " + std::to_string(R.rows[k].rec + 1));
     const unsigned TO = parallel_chunk_count((size_t)R.n_rows);
@@ -1228,12 +1238,15 @@ std::vector<std::string> assemble_lines(const TextFile &f, const std::vector<rb_
                 o += s.strand; o += '\t'; o.append(f.all.data() + s.q_name, s.q_name_n); o += '\t'; num(s.q_len); o += '\t'; num(h.t_st); o += '\t';
                 num(h.t_en);
             } else {
-                o.append(f.all.data() + s.q_name, s.q_name_n); o += '\t'; num(s.q_len); o += '\t'; num(h.q_st); o += '\t'; num(h.q_en); o += '\t';
-                o += s.strand; o += '\t'; o.append(f.all.data() + s.t_name, s.t_name_n); o += '\t'; num(s.t_len); o += '\t'; num(h.t_st); o += '\t';
+                o.append(f.all.data() + s.q_name, s.q_name_n);
+                if (pn && pn->orient) o += pn->flipped(h.rec) ? '-' : '+';
+                o += '\t'; num(s.q_len); o += '\t'; num(h.q_st); o += '\t'; num(h.q_en); o += '\t';
+                o += pn ? pn->strand(h.rec, s.strand) : s.strand; o += '\t'; o.append(f.all.data() + s.t_name, s.t_name_n); o += '\t'; num(s.t_len); o += '\t'; num(h.t_st); o += '\t';
                 num(h.t_en);
             }
             o += '\t'; num(h.nmatch); o += '\t'; num(h.aln_len); o += '\t'; num(s.mapq); o += "\tid:Z:";
-            if (rgns && !(h.flags & RB_HIT_INSIDE)) o += (*rgns)[h.win].id;
+            if (pn) {} // (a piece read back by the next command: its id is empty whatever the first command printed, paf.rs:386-404)
+            else if (rgns && !(h.flags & RB_HIT_INSIDE)) o += (*rgns)[h.win].id;
             else o += f.stripped_suffix(h.rec, norm[h.rec]); // (a record read from a file has an empty id of its own)
             o += "\tcg:Z:";
             o.append((const char *)R.text + R.toff[k], (size_t)(R.toff[k + 1] - R.toff[k]));
@@ -1371,6 +1384,91 @@ bool break_stats_file_text(Engine &eng, const std::string &paf_path, uint32_t br
                            std::string &trailing_panic) {
     const StatsMode st{stats_qbed, &trailing_panic};
     return break_file_text_impl(eng, paf_path, break_length, out_text, &st);
+}
+
+// `rb break-paf --max-size N [--orient] [--paired-len L --aln A --query Q] [--stats | --stats-qbed]`, text in -> text out: break-paf, then
+// orient and / or filter over the pieces' rows on the device (rb_host_break_pairs_text / _stats_text): the pieces are never printed or read
+// back.  false = take the record route (break_pairs_text): two cg tags, a record or a piece the first command panics on, a flipped record that
+// ends behind its query's length; nothing was produced.  A panic of the first command's Paf::from_file is thrown.
+bool break_pairs_file_text(Engine &eng, const std::string &paf_path, uint32_t break_length, bool orient, bool filter, uint64_t paired_len, uint64_t min_aln,
+                           uint64_t min_query, int stats_mode, std::vector<std::string> &out_text, std::string &trailing_panic) {
+    TextFile &f = *new TextFile; // (one-shot command, as in break_file_text_impl)
+    if (!f.load(paf_path)) return false;
+    double tl = now_s();
+    const size_t n = f.recs.size();
+    // the (target name, query name) pairs as dense keys, in order of first appearance
+    struct PairHash {
+        size_t operator()(const std::pair<std::string_view, std::string_view> &k) const {
+            return std::hash<std::string_view>()(k.first) * 1000003u ^ std::hash<std::string_view>()(k.second);
+        }
+    };
+    std::unordered_map<std::pair<std::string_view, std::string_view>, uint32_t, PairHash> ids;
+    std::vector<uint32_t> rec_key(n);
+    std::vector<uint64_t> rec_q_len(n);
+    for (size_t i = 0; i < n; i++) {
+        const HeaderOnly &h = f.recs[i];
+        rec_key[i] = ids.emplace(std::make_pair(f.name(h.t_name, h.t_name_n), f.name(h.q_name, h.q_name_n)), (uint32_t)ids.size()).first->second;
+        rec_q_len[i] = h.q_len;
+    }
+    std::vector<uint8_t> key_flip(ids.size() + 1, 0);
+    lap("pair keys", tl);
+    std::vector<uint8_t> cig_status(n ? n : 1);
+    std::vector<rb_reduce_row> red(n);
+    std::vector<rb_norm_row> norm(n);
+    TextRows &R = *new TextRows;
+    rb_counters cnt;
+    int declined = 0;
+    const uint32_t mode = (orient ? RB_PAIRS_ORIENT : 0) | (filter ? RB_PAIRS_FILTER : 0);
+    if (stats_mode)
+        eng.check(rb_host_break_pairs_stats_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
+                                                 f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), break_length, eng.bsearch_policy, cig_status.data(),
+                                                 red.data(), norm.data(), &R.rows, &R.n_rows, &R.stats, &cnt, rec_key.data(), rec_q_len.data(), ids.size(), mode,
+                                                 paired_len, min_aln, min_query, key_flip.data(), &declined),
+                  "rb_host_break_pairs_stats_text");
+    else
+        eng.check(rb_host_break_pairs_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
+                                           f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), break_length, eng.bsearch_policy, cig_status.data(),
+                                           red.data(), norm.data(), &R.rows, &R.n_rows, &R.toff, &R.text, &cnt, rec_key.data(), rec_q_len.data(), ids.size(), mode,
+                                           paired_len, min_aln, min_query, key_flip.data(), &declined),
+                  "rb_host_break_pairs_text");
+    lap(stats_mode ? "rb_host_break_pairs_stats_text" : "rb_host_break_pairs_text", tl);
+    if (!f.check_loaded(cig_status, red)) return false;
+    for (size_t i = 0; i < n; i++)
+        if (norm[i].status != RB_ST_OK) return false; // (the first command panics part-way: the record route knows what reached the second)
+    if (declined) return false;
+    const PairNames pn{&rec_key, &key_flip, orient};
+    out_text = stats_mode ? stats_lines_of_file(f, R, false, stats_mode == 2, trailing_panic, &pn) : assemble_lines(f, norm, R, nullptr, nullptr, false, &pn);
+    lap(stats_mode ? "stats lines" : "assemble lines", tl);
+    return true;
+}
+// the record route: the existing commands one behind the other -- break_paf_on_indels, the pieces re-read with an empty id, Paf::orient,
+// the three filters (main.rs:242-244), then records_to_text or stats_from_paf.  first_panic: the first command panicked part-way; what the
+// later commands make of the pieces printed by then is returned.  A panic of a later command (orient's divide by zero) is thrown.
+static std::vector<PafRecord> break_pieces_reread(Engine &eng, const std::vector<PafRecord> &paf_recs, uint32_t break_length, std::string &first_panic);
+std::vector<std::string> break_pairs_text(Engine &eng, const std::vector<PafRecord> &paf_recs, uint32_t break_length, bool orient, bool filter,
+                                          uint64_t paired_len, uint64_t min_aln, uint64_t min_query, int stats_mode, std::string &first_panic) {
+    double tl = now_s();
+    Paf p;
+    p.records = break_pieces_reread(eng, paf_recs, break_length, first_panic);
+    if (orient) {
+        p.orient();
+        // a flipped record that ends behind its query's length came out with q_st' = q_len - q_en wrapped around (paf.rs:148); orient itself
+        // prints it, the next command's Paf::from_file panics on it (check_integrity, paf.rs:839) before it prints a record
+        if (filter || stats_mode)
+            for (size_t i = 0; i < p.records.size(); i++)
+                if (p.records[i].q_en < p.records[i].q_st) throw Panic("check_integrity: record " + std::to_string(i + 1) + " status " + std::to_string((int)RB_ST_PANIC_INTEGRITY_Q));
+    }
+    lap("record route: pieces re-read, orient", tl);
+    if (filter) {
+        p.filter_query_len(min_query);
+        p.filter_aln_len(min_aln);
+        p.filter_aln_pairs(paired_len);
+    }
+    if (p.records.empty()) return {};
+    if (!stats_mode) return records_to_text(p.records);
+    std::vector<std::string> text(1);
+    for (const Stats &s : stats_from_paf(eng, p.records)) text[0] += cigar_stats_line(s, stats_mode == 2);
+    return text;
 }
 
 // `rb liftover --break N`, text in -> text out: break-paf, the pieces read back as records and lifted over the windows in one device

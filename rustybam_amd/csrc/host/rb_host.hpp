@@ -141,6 +141,17 @@ std::vector<std::string> break_liftover_text(Engine &eng, const std::vector<Regi
                                              std::string &first_panic);
 std::vector<std::string> break_liftover_stats_text(Engine &eng, const std::vector<Region> &rgns, const std::vector<PafRecord> &paf_recs, uint32_t break_length,
                                                    bool stats_qbed, std::string &first_panic, std::string &trailing_panic);
+// `rb break-paf --max-size N [--orient] [--paired-len L] [--aln A] [--query Q] [--stats | --stats-qbed]` (this project's own flags): what
+// `rb break-paf --max-size N in.paf [| rb orient -] [| rb filter --paired-len L --aln A --query Q -] [| rb stats --paf [--qbed] -]` prints
+// (stats_mode 1 / 2: without the header), the pieces never printed or read back.  Orient and filter are sums over the pieces' headers keyed by
+// the (target name, query name) pair: rb_dev_pairs_rows on the hit rows of rb_dev_break.
+//   break_pairs_file_text  text in, rb_host_break_pairs_text / _stats_text; false = take the record route, nothing was produced
+//   break_pairs_text       the record route: break_paf_on_indels, the pieces re-read with an empty id, Paf::orient, Paf::filter_*, then
+//                          records_to_text or stats_from_paf.  first_panic as in break_liftover_text; a later command's panic is thrown.
+bool break_pairs_file_text(Engine &eng, const std::string &paf_path, uint32_t break_length, bool orient, bool filter, uint64_t paired_len, uint64_t min_aln,
+                           uint64_t min_query, int stats_mode, std::vector<std::string> &out_text, std::string &trailing_panic);
+std::vector<std::string> break_pairs_text(Engine &eng, const std::vector<PafRecord> &paf_recs, uint32_t break_length, bool orient, bool filter,
+                                          uint64_t paired_len, uint64_t min_aln, uint64_t min_query, int stats_mode, std::string &first_panic);
 // the same two routes as a pipeline over chunks of a big plain file (a few host threads, each with its own context on `device`):
 // the sink receives the chunks' outputs in file order while later chunks are still being read / clipped / printed.  A chunk's text
 // is contig-major within the chunk (runs); false = not applicable or a line needs the general parser (pipeline_started(): the

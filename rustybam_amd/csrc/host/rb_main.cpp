@@ -39,7 +39,7 @@ static int usage() {
             "usage: rb [--bsearch modern|legacy] [--device N] [--gpus N] <subcommand> ...\n"
             "  stats [-q|--qbed] [-p|--paf] <PAF or BAM>\n"
             "  liftover -b|--bed <BED> [-q|--qbed] [-l|--largest] [--break N] [--stats|--stats-qbed] [PAF]\n"
-            "  break-paf [-m|--max-size 100] [--stats|--stats-qbed] [PAF]\n"
+            "  break-paf [-m|--max-size 100] [--orient] [--paired-len L] [--aln A] [--query Q] [--stats|--stats-qbed] [PAF]\n"
             "  trim-paf [-m|--match-score 1] [-d|--diff-score 1] [-i|--indel-score 1] [-r|--remove-contained] [PAF]\n"
             "  invert [PAF]\n"
             "  orient [-s|--scaffold] [-i|--insert 1000000] [PAF]\n"
@@ -49,6 +49,9 @@ static int usage() {
             "          runs of lines; trim-paf: ranges of the sorted query names); the output is the single-GPU output byte for byte.\n"
             "--break N (liftover; this engine's own flag): print what `rb break-paf --max-size N PAF | rb liftover -b BED -` prints, the\n"
             "          pieces never printed or read back.  With --stats / --stats-qbed.  Not with -q, -l or --gpus N > 1.\n"
+            "--orient, --paired-len L / --aln A / --query Q (break-paf; this engine's own flags): print what `rb break-paf .. PAF | rb orient -`\n"
+            "          and / or `.. | rb filter --paired-len L --aln A --query Q -` prints (orient first), the pieces never printed or read\n"
+            "          back.  With --stats / --stats-qbed.  Not with --scaffold, --insert or --gpus N > 1.\n"
             "--stats / --stats-qbed (liftover, break-paf; this engine's own flags, like --gpus and --bsearch): print what\n"
             "          `rb <cmd> ... | rb stats --paf` (--stats-qbed: `... | rb stats --paf --qbed`) prints, from the clips on the device:\n"
             "          no PAF text in between.  -q keeps its liftover meaning beside either.  Not with --gpus N > 1 or --largest.\n"
@@ -911,6 +914,8 @@ int main(int argc, char **argv) {
     uint32_t max_size = 100;
     uint64_t paired_len = 0, min_aln = 0, min_query = 0, insert = 1000000;
     bool do_scaffold = false;
+    // break-paf --orient / --paired-len / --aln / --query: `| rb orient -` / `| rb filter .. -` behind break-paf, in one process
+    bool brk_orient = false, filter_flags = false, scaffold_flags = false;
     const bool trim = cmd == "trim-paf" || cmd == "trim" || cmd == "tp";
     const bool filter = cmd == "filter", orient = cmd == "orient", nucfreq = cmd == "nucfreq";
     std::string region;
@@ -920,11 +925,12 @@ int main(int argc, char **argv) {
         auto next = [&]() -> const char * { return a + 1 < argc ? argv[++a] : ""; };
         if (nucfreq && (s == "-r" || s == "--region")) region = next();
         else if (nucfreq && (s == "-s" || s == "--small")) small = true;
-        else if (s == "--paired-len" || (s == "-p" && filter)) paired_len = strtoull(next(), nullptr, 10);
-        else if (s == "--query" || (s == "-q" && filter)) min_query = strtoull(next(), nullptr, 10);
-        else if (s == "--aln" || (s == "-a" && filter)) min_aln = strtoull(next(), nullptr, 10);
-        else if (s == "--insert" || (s == "-i" && orient)) insert = strtoull(next(), nullptr, 10);
-        else if (s == "--scaffold" || (s == "-s" && orient)) do_scaffold = true;
+        else if (s == "--paired-len" || (s == "-p" && filter)) paired_len = strtoull(next(), nullptr, 10), filter_flags = true;
+        else if (s == "--query" || (s == "-q" && filter)) min_query = strtoull(next(), nullptr, 10), filter_flags = true;
+        else if (s == "--aln" || (s == "-a" && filter)) min_aln = strtoull(next(), nullptr, 10), filter_flags = true;
+        else if (s == "--insert" || (s == "-i" && orient)) insert = strtoull(next(), nullptr, 10), scaffold_flags = true;
+        else if (s == "--scaffold" || (s == "-s" && orient)) do_scaffold = true, scaffold_flags = true;
+        else if (s == "--orient") brk_orient = true;
         else if (s == "--stats") stats_mode = 1;
         else if (s == "--stats-qbed") stats_mode = 2;
         else if (s == "--break") chain = true, chain_size = (uint32_t)strtoul(next(), nullptr, 10);
@@ -940,6 +946,16 @@ int main(int argc, char **argv) {
         else paf_path = s;
     }
     const bool is_lift = cmd == "liftover" || cmd == "lo", is_brk = cmd == "break-paf" || cmd == "breakpaf" || cmd == "bp";
+    {
+        const char *why = brk_orient && !is_brk ? "--orient belongs to break-paf (the orient command takes no flag for it)"
+                          : filter_flags && !(filter || is_brk) ? "--paired-len / --aln / --query belong to filter and break-paf"
+                          : scaffold_flags && is_brk ? "--scaffold / --insert belong to the orient command: not with break-paf"
+                          : (brk_orient || (filter_flags && is_brk)) && gpus > 1 ? "--orient / --paired-len / --aln / --query run on one GPU: not with --gpus N > 1" : nullptr;
+        if (why) {
+            fprintf(stderr, "rb: %s\n", why);
+            return 2;
+        }
+    }
     if (stats_mode && !(is_lift || is_brk)) return usage();
     if (stats_mode && gpus > 1) {
         fprintf(stderr, "rb: --stats / --stats-qbed run on one GPU: not with --gpus %d\n", gpus);
@@ -1119,6 +1135,20 @@ int main(int argc, char **argv) {
                 lap("write", tl);
             }
         } else if (cmd == "break-paf" || cmd == "breakpaf" || cmd == "bp") {
+            if (brk_orient || filter_flags) { // what `rb break-paf .. [| rb orient -] [| rb filter .. -] [| rb stats --paf [--qbed] -]` prints
+                if (stats_mode) put(rb::cigar_stats_header(stats_mode == 2));
+                std::vector<std::string> text;
+                std::string first_panic, panic;
+                if (!(text_path && rb::break_pairs_file_text(eng, paf_path, max_size, brk_orient, filter_flags, paired_len, min_aln, min_query, stats_mode, text, panic))) {
+                    rb::Paf paf = rb::Paf::from_file(eng, paf_path);
+                    text = rb::break_pairs_text(eng, paf.records, max_size, brk_orient, filter_flags, paired_len, min_aln, min_query, stats_mode, first_panic);
+                }
+                lap("break-paf --orient / --paired-len", tl);
+                emit(text);
+                if (!panic.empty()) throw rb::Panic(panic);
+                if (!first_panic.empty()) throw rb::Panic(first_panic); // (the first command's: the later ones have printed what reached them)
+                done(0);
+            }
             if (stats_mode) {
                 put(rb::cigar_stats_header(stats_mode == 2));
                 std::vector<std::string> text;

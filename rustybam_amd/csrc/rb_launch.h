@@ -188,6 +188,28 @@ extern "C" hipError_t rb_launch_largest_rec_keys(const rb_norm_row *norm, uint64
 extern "C" hipError_t rb_launch_largest_gather(const rb_hit_row *rows, const uint32_t *out_ops, const uint64_t *sel, uint64_t n_sel, rb_hit_row *sel_rows,
                                                uint32_t *sel_desc, hipStream_t stream);
 
+// ---- k_pairs.hip: orient / filter over hit rows, keyed by the records' (target, query) pair ----
+struct rb_pairs_params {
+    const rb_hit_row *rows;
+    uint64_t n_rows;
+    const uint32_t *rec_key;   // [n_rec]
+    const uint64_t *rec_q_len; // [n_rec]
+    const uint8_t *strand;     // [n_rec]
+    uint64_t n_rec, n_keys;
+    uint32_t mode;             // RB_PAIRS_ORIENT | RB_PAIRS_FILTER
+    uint64_t paired_len, min_aln, min_query;
+    unsigned long long *orient, *tspan, *fspan; // [n_keys] each, zeroed: the three sums (orient is an i64 in two's complement)
+    uint64_t *cnt;             // [n_rows + 1]: 1 per kept row, then the exclusive prefix
+    rb_hit_row *rows_out;
+    uint64_t rows_cap;
+    uint8_t *key_flip;         // [n_keys] OUT
+    rb_pairs_info *info;       // zeroed
+};
+extern "C" hipError_t rb_launch_pairs(const rb_pairs_params *p, uint64_t *block_sums, hipStream_t stream);
+extern "C" hipError_t rb_launch_pairs_desc(const rb_hit_row *rows, uint64_t n_rows, const uint32_t *out_ops, uint32_t *desc /* [4 * n_rows] */, hipStream_t stream);
+extern "C" uint32_t rb_pairs_wave_rows(void);
+extern "C" uint32_t rb_pairs_block_rows(void);
+
 // ---- k_hitstats.hip: stats of every hit row's clip ----
 struct rb_hitstats_params {
     const uint32_t *ops;     // the batch's packed ops (descriptor rows point into them)
