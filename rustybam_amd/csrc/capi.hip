@@ -1395,6 +1395,46 @@ struct DevBatch {
         return rc;
     }
 };
+// ---- the arguments of the text entry points (rb_host_*_text), stated once.  An extern wrapper fills the packs by brace-initialisation in
+// the order of its own parameter list; the internal functions take them by reference.
+struct text_cols { // the input columns
+    uint64_t n_rec;
+    const uint8_t *text;
+    uint64_t text_bytes;
+    const uint64_t *cig_off, *cig_end, *t_st, *t_en, *q_st, *q_en;
+    const uint8_t *strand;
+    const uint32_t *contig;
+};
+struct text_wins { // the windows (value-initialised: a break route has none)
+    uint64_t n_win;
+    const uint32_t *w_contig;
+    const uint64_t *w_st, *w_en;
+};
+struct text_outs { // the outputs; a stats form passes stats and no row_text_off / row_text, rb_host_scan_text passes the first three alone
+    uint8_t *cig_status;
+    rb_reduce_row *reduce_out;
+    rb_norm_row *norm_out;
+    rb_hit_row **rows;
+    uint64_t *n_rows, **row_text_off;
+    uint8_t **row_text;
+    rb_reduce_row **stats;
+    rb_counters *counters;
+    // storage of the pack's own for what such a caller does not pass (text_front_of points there; nothing is ever allocated into it)
+    rb_hit_row *own_rows = nullptr;
+    uint64_t own_n = 0, *own_off = nullptr;
+    uint8_t *own_text = nullptr;
+    void drop() { // an error behind the point where the results were allocated: the caller gets none of them
+        free(*rows), free(*row_text_off), free(*row_text);
+        *rows = nullptr, *row_text_off = nullptr, *row_text = nullptr, *n_rows = 0;
+        if (stats) free(*stats), *stats = nullptr;
+    }
+    int finish(int rc, uint64_t n, const rb_counters &hc) { // the end of a route: the counts with the results, or no results
+        if (rc) drop();
+        else *n_rows = n;
+        if (!rc && counters) *counters = hc;
+        return rc;
+    }
+};
 } // namespace
 
 extern "C" void rb_host_free(void *p) { free(p); }
@@ -1634,12 +1674,22 @@ extern "C" int rb_host_format_cigars(rb_ctx *ctx, const uint32_t *ops, uint64_t 
     return RB_OK;
 }
 
-// The front of the text wrappers: the records' `cg:Z:` values parsed on the device, and the batch b.v made of them and of the uploaded
-// columns (op_off: its offsets on the host; *contig NULL: every record on contig 0, zc then holds the ids).  *parsed = false: a CIGAR did
-// not parse (cig_status says which), nothing else was done.
-static int text_to_batch(rb_ctx *ctx, DevBatch &b, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end,
-                         const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand,
-                         const uint32_t **contig, std::vector<uint32_t> &zc, uint8_t *cig_status, std::vector<uint64_t> &op_off, bool *parsed, double &tl) {
+// What the front of a text route leaves for the rest of it: the batch's op offsets on the host, the contig ids its plan is made with (the
+// caller's, or zc: every record on contig 0), the record scan's buffers (they go with the batch), the lap clock.  done: the call is over.
+struct text_front {
+    std::vector<uint64_t> op_off;
+    std::vector<uint32_t> zc;
+    const uint32_t *contig = nullptr, *d_contig = nullptr;
+    rb_norm_row *d_norm = nullptr;
+    rb_reduce_row *d_red = nullptr;
+    double tl = 0;
+    bool done = true;
+};
+// The records' `cg:Z:` values parsed on the device, and the batch b.v made of them and of the uploaded columns (f.op_off: its offsets on
+// the host; f.contig NULL: every record on contig 0, f.zc then holds the ids).  *parsed = false: a CIGAR did not parse (cig_status says
+// which), nothing else was done.
+static int text_to_batch(rb_ctx *ctx, DevBatch &b, const text_cols &c, uint8_t *cig_status, text_front &f, bool *parsed) {
+    const uint64_t n_rec = c.n_rec, text_bytes = c.text_bytes, *cig_off = c.cig_off, *cig_end = c.cig_end;
     int rc;
     *parsed = false;
     // ---- text -> ops on the device ----
@@ -1649,7 +1699,7 @@ static int text_to_batch(rb_ctx *ctx, DevBatch &b, uint64_t n_rec, const uint8_t
     uint32_t *d_ops = nullptr;
     void *d_scr = nullptr;
     if ((rc = b.alloc((size_t)text_bytes + 32, &d_text))) return rc;
-    if (text_bytes && (rc = rb_dev_upload(ctx, d_text, text, (size_t)text_bytes))) return rc;
+    if (text_bytes && (rc = rb_dev_upload(ctx, d_text, c.text, (size_t)text_bytes))) return rc;
     if ((rc = b.up(cig_off, (size_t)n_rec, &d_coff))) return rc;
     if ((rc = b.up(cig_end, (size_t)n_rec, &d_cend))) return rc;
     uint64_t cig_bytes = 0;
@@ -1662,62 +1712,103 @@ static int text_to_batch(rb_ctx *ctx, DevBatch &b, uint64_t n_rec, const uint8_t
     if ((rc = b.alloc((size_t)ops_cap + 4, &d_ops))) return rc;
     if ((rc = b.alloc((size_t)n_rec + 1, &d_status))) return rc;
     if ((rc = b.alloc(rb_text_scratch_bytes(n_rec), (uint8_t **)&d_scr))) return rc;
-    rb_lap("H2D text", tl);
+    rb_lap("H2D text", f.tl);
     if ((rc = rb_dev_parse_cigars(ctx, d_text, d_coff, d_cend, n_rec, d_opoff, d_ops, ops_cap, d_status, d_scr))) return rc;
     if (n_rec && (rc = rb_dev_download(ctx, cig_status, d_status, (size_t)n_rec))) return rc;
     for (uint64_t r = 0; r < n_rec; r++)
         if (cig_status[r] != RB_TEXT_OK) return RB_OK; // (*parsed stays false) the caller reports it (the reference panics at paf.rs:399)
-    op_off.assign((size_t)n_rec + 1, 0);
-    if ((rc = rb_dev_download(ctx, op_off.data(), d_opoff, ((size_t)n_rec + 1) * 8))) return rc;
-    rb_lap("parse cigars + op_off D2H", tl);
+    f.op_off.assign((size_t)n_rec + 1, 0);
+    if ((rc = rb_dev_download(ctx, f.op_off.data(), d_opoff, ((size_t)n_rec + 1) * 8))) return rc;
+    rb_lap("parse cigars + op_off D2H", f.tl);
     // ---- the batch, device-resident ----
-    if (!*contig) {
-        zc.assign(n_rec, 0);
-        *contig = zc.data();
+    if (!f.contig) {
+        f.zc.assign(n_rec, 0);
+        f.contig = f.zc.data();
     }
     b.v.n_rec = n_rec;
-    b.v.n_ops = op_off[n_rec];
+    b.v.n_ops = f.op_off[n_rec];
     b.v.ops = d_ops;
     b.v.op_off = d_opoff;
-    if ((rc = b.up(t_st, (size_t)n_rec, &b.v.t_st))) return rc;
-    if ((rc = b.up(t_en, (size_t)n_rec, &b.v.t_en))) return rc;
-    if ((rc = b.up(q_st, (size_t)n_rec, &b.v.q_st))) return rc;
-    if ((rc = b.up(q_en, (size_t)n_rec, &b.v.q_en))) return rc;
-    if ((rc = b.up(strand, (size_t)n_rec, &b.v.strand))) return rc;
-    if ((rc = b.up(*contig, (size_t)n_rec, &b.v.contig))) return rc;
+    if ((rc = b.up(c.t_st, (size_t)n_rec, &b.v.t_st))) return rc;
+    if ((rc = b.up(c.t_en, (size_t)n_rec, &b.v.t_en))) return rc;
+    if ((rc = b.up(c.q_st, (size_t)n_rec, &b.v.q_st))) return rc;
+    if ((rc = b.up(c.q_en, (size_t)n_rec, &b.v.q_en))) return rc;
+    if ((rc = b.up(c.strand, (size_t)n_rec, &b.v.strand))) return rc;
+    if ((rc = b.up(f.contig, (size_t)n_rec, &b.v.contig))) return rc;
     *parsed = true;
     return RB_OK;
 }
 
-// The tail of the text wrappers: the hit rows of a clip call in descriptor mode on the device-resident batch `v` (op_off: its offsets on the
-// host) go to the host -- with the stats of every row's clip where it lies (stats != NULL: rb_dev_stats_rows, no text), or with the clipped
-// CIGAR of every row printed on the device (rb_dev_format_cigars).  d_rows / d_out: all rows and the clip call's out_ops; d_take /
-// d_take_desc: the rows that are printed and the descriptor of row k of them at d_take_desc[4k] (the same two unless --largest selected).
-// plain_ops: v.ops hold no continuation words.  rc: what the calls in front returned (nothing is done if it is not RB_OK).
-static int lift_text_tail(rb_ctx *ctx, DevBatch &b, const rb_batch_view &v, const uint64_t *op_off, int rc, const rb_hit_row *d_rows, const uint32_t *d_out,
-                          const rb_hit_row *d_take, const uint32_t *d_take_desc, uint64_t nr, const rb_counters &hc, bool plain_ops, rb_hit_row **rows,
-                          uint64_t *n_rows, uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters, rb_reduce_row **stats, double &tl) {
-    if (stats) { // ---- the stats of every row's clip where it lies; rows and stats to the host, no text ----
+// The front of host_lift_text and host_break_lift_text, up to and including the record scan's buffers.  text_args_ok: the null checks on
+// the packs, which both make before they refuse anything else or write anything.  text_front_of: the outputs cleared, the result of an empty
+// file, hipSetDevice (the one of the call), text_to_batch, d_norm / d_red.  f.done: the call is over with what is returned -- an empty
+// file, or a CIGAR that did not parse (o.cig_status says which).  pipeline: the break -> liftover routes, whose plan sees every record
+// on contig 0 and which always want the reduce rows.
+static bool text_args_ok(const rb_ctx *ctx, const text_cols &c, const text_outs &o) {
+    return ctx && (!c.n_rec || (c.cig_off && c.cig_end && o.cig_status));
+}
+static int text_front_of(rb_ctx *ctx, const text_cols &c, text_outs &o, bool scan_only, bool pipeline, DevBatch &b, text_front &f) {
+    if (o.stats) *o.stats = nullptr;
+    // (deliberate ABI behaviour: the pipeline's pair clears *counters before it parses, the others only with the empty file's result below)
+    if (pipeline && o.counters) memset(o.counters, 0, sizeof *o.counters);
+    if (c.n_rec == 0) { // an empty file: no rows, no text
+        if (o.rows) *o.rows = nullptr;
+        if (o.n_rows) *o.n_rows = 0;
+        if (o.row_text) *o.row_text = nullptr;
+        if (o.row_text_off) {
+            *o.row_text_off = (uint64_t *)calloc(2, 8);
+            if (!*o.row_text_off) return fail(ctx, RB_E_NOMEM, "malloc");
+        }
+        if (o.counters) memset(o.counters, 0, sizeof *o.counters);
+        return RB_OK;
+    }
+    if (scan_only) o.rows = &o.own_rows, o.n_rows = &o.own_n;
+    if (scan_only || o.stats) o.row_text_off = &o.own_off, o.row_text = &o.own_text;
+    if (!o.rows || !o.n_rows || !o.row_text_off || !o.row_text) return RB_E_INVALID;
+    // (deliberate ABI behaviour: *row_text_off stays NULL when a CIGAR does not parse, unlike the empty file's two zero words)
+    *o.rows = nullptr, *o.row_text_off = nullptr, *o.row_text = nullptr, *o.n_rows = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    bool parsed = false;
+    f.tl = rb_now_s();
+    f.contig = pipeline ? nullptr : c.contig;
+    if ((rc = text_to_batch(ctx, b, c, o.cig_status, f, &parsed)) || !parsed) return rc;
+    if (pipeline && c.contig && (rc = b.up(c.contig, (size_t)c.n_rec, &f.d_contig))) return rc; // (the records' own, for the pieces to inherit)
+    if ((rc = b.alloc(c.n_rec, &f.d_norm))) return rc;
+    if ((pipeline || o.reduce_out) && (rc = b.alloc(c.n_rec, &f.d_red))) return rc;
+    f.done = false;
+    return RB_OK;
+}
+
+// the rows a clip call left on the device: all of them and the call's out_ops; the rows that are printed and the descriptor of row k of
+// them at take_desc[4k] (the same two unless --largest or the pairs pass selected); how many go to the host
+struct tail_rows {
+    const rb_hit_row *rows;
+    const uint32_t *out;
+    const rb_hit_row *take;
+    const uint32_t *take_desc;
+    uint64_t n;
+};
+// The tail of the text wrappers: the hit rows of a clip call in descriptor mode on the device-resident batch b.v (op_off: its offsets on the
+// host) go to the host -- with the stats of every row's clip where it lies (o.stats != NULL: rb_dev_stats_rows, no text), or with the clipped
+// CIGAR of every row printed on the device (rb_dev_format_cigars).  plain_ops: b.v.ops hold no continuation words.  rc: what the calls in
+// front returned (nothing is done if it is not RB_OK).
+static int lift_text_tail(rb_ctx *ctx, DevBatch &b, const uint64_t *op_off, int rc, const tail_rows &t, const rb_counters &hc, bool plain_ops, text_outs &o,
+                          double &tl) {
+    const uint64_t nr = t.n;
+    if (o.stats) { // ---- the stats of every row's clip where it lies; rows and stats to the host, no text ----
         rb_reduce_row *d_stats = nullptr;
         if (!rc) rc = b.alloc((size_t)nr + 1, &d_stats);
-        if (!rc) rc = rb_dev_stats_rows(ctx, &v, d_rows, nr, d_out, d_stats);
+        if (!rc) rc = rb_dev_stats_rows(ctx, &b.v, t.rows, nr, t.out, d_stats);
         if (!rc) {
-            *rows = (rb_hit_row *)malloc((size_t)(nr + 1) * sizeof(rb_hit_row));
-            *stats = (rb_reduce_row *)malloc((size_t)(nr + 1) * sizeof(rb_reduce_row));
-            if (!*rows || !*stats) rc = fail(ctx, RB_E_NOMEM, "malloc(rows)");
+            *o.rows = (rb_hit_row *)malloc((size_t)(nr + 1) * sizeof(rb_hit_row));
+            *o.stats = (rb_reduce_row *)malloc((size_t)(nr + 1) * sizeof(rb_reduce_row));
+            if (!*o.rows || !*o.stats) rc = fail(ctx, RB_E_NOMEM, "malloc(rows)");
         }
-        if (!rc && nr) rc = rb_dev_download(ctx, *rows, d_rows, (size_t)nr * sizeof(rb_hit_row));
-        if (!rc && nr) rc = rb_dev_download(ctx, *stats, d_stats, (size_t)nr * sizeof(rb_reduce_row));
+        if (!rc && nr) rc = rb_dev_download(ctx, *o.rows, t.rows, (size_t)nr * sizeof(rb_hit_row));
+        if (!rc && nr) rc = rb_dev_download(ctx, *o.stats, d_stats, (size_t)nr * sizeof(rb_reduce_row));
         rb_lap("stats rows + rows D2H", tl);
-        if (!rc) {
-            *n_rows = nr;
-            if (counters) *counters = hc;
-        } else {
-            free(*rows);
-            free(*stats);
-            *rows = nullptr, *stats = nullptr;
-        }
-        return rc;
+        return o.finish(rc, nr, hc);
     }
     // ---- rows to the host, clip items back to the device, text out ----
     std::vector<uint32_t> desc;
@@ -1725,21 +1816,21 @@ static int lift_text_tail(rb_ctx *ctx, DevBatch &b, const rb_batch_view &v, cons
     uint32_t *d_cnt3 = nullptr; // count | first_len | last_len, three arrays of nr
     uint8_t *d_rtext = nullptr;
     if (!rc) {
-        *rows = (rb_hit_row *)malloc((size_t)(nr + 1) * sizeof(rb_hit_row));
-        *row_text_off = (uint64_t *)malloc((size_t)(nr + 2) * 8);
-        if (!*rows || !*row_text_off) rc = fail(ctx, RB_E_NOMEM, "malloc(rows)");
+        *o.rows = (rb_hit_row *)malloc((size_t)(nr + 1) * sizeof(rb_hit_row));
+        *o.row_text_off = (uint64_t *)malloc((size_t)(nr + 2) * 8);
+        if (!*o.rows || !*o.row_text_off) rc = fail(ctx, RB_E_NOMEM, "malloc(rows)");
     }
-    if (!rc && nr) rc = rb_dev_download(ctx, *rows, d_take, (size_t)nr * sizeof(rb_hit_row));
+    if (!rc && nr) rc = rb_dev_download(ctx, *o.rows, t.take, (size_t)nr * sizeof(rb_hit_row));
     if (!rc && nr) {
         desc.resize((size_t)nr * 4);
-        rc = rb_dev_download(ctx, desc.data(), d_take_desc, (size_t)nr * 16); // descriptor of row k at out_ops[4k]
+        rc = rb_dev_download(ctx, desc.data(), t.take_desc, (size_t)nr * 16); // descriptor of row k at out_ops[4k]
     }
     rb_lap("rows D2H", tl);
     if (!rc) {
         std::vector<uint64_t> first((size_t)nr + 1, 0);
         std::vector<uint32_t> c3((size_t)nr * 3 + 1, 0);
         for (uint64_t k = 0; k < nr; k++) {
-            const rb_hit_row &h = (*rows)[k];
+            const rb_hit_row &h = (*o.rows)[k];
             if (h.status != RB_ST_OK) continue;
             if (h.flags & RB_HIT_DESCRIPTOR) {
                 const uint32_t *d = &desc[(size_t)k * 4];
@@ -1760,29 +1851,20 @@ static int lift_text_tail(rb_ctx *ctx, DevBatch &b, const rb_batch_view &v, cons
         if (!rc && nr) rc = rb_dev_upload(ctx, d_first, first.data(), (size_t)nr * 8);
         if (!rc && nr) rc = rb_dev_upload(ctx, d_cnt3, c3.data(), (size_t)nr * 12);
         if (!rc) rc = rb_ctx_sync(ctx);
-        if (!rc) rc = format_cigars_impl(ctx, v.ops, d_out, nr, d_first, d_cnt3, d_cnt3 + nr, d_cnt3 + 2 * nr, d_toff, nullptr, 0, d_scr2, false, plain_ops);
-        if (!rc) rc = rb_dev_download(ctx, *row_text_off, d_toff, ((size_t)nr + 1) * 8);
-        const uint64_t bytes = rc ? 0 : (*row_text_off)[nr];
+        if (!rc) rc = format_cigars_impl(ctx, b.v.ops, t.out, nr, d_first, d_cnt3, d_cnt3 + nr, d_cnt3 + 2 * nr, d_toff, nullptr, 0, d_scr2, false, plain_ops);
+        if (!rc) rc = rb_dev_download(ctx, *o.row_text_off, d_toff, ((size_t)nr + 1) * 8);
+        const uint64_t bytes = rc ? 0 : (*o.row_text_off)[nr];
         if (!rc) rc = b.alloc((size_t)bytes + 16, &d_rtext);
-        if (!rc) rc = format_cigars_impl(ctx, v.ops, d_out, nr, d_first, d_cnt3, d_cnt3 + nr, d_cnt3 + 2 * nr, d_toff, d_rtext, bytes, d_scr2, true, plain_ops);
+        if (!rc) rc = format_cigars_impl(ctx, b.v.ops, t.out, nr, d_first, d_cnt3, d_cnt3 + nr, d_cnt3 + 2 * nr, d_toff, d_rtext, bytes, d_scr2, true, plain_ops);
         if (!rc) {
-            *row_text = (uint8_t *)malloc((size_t)bytes + 16);
-            if (!*row_text) rc = fail(ctx, RB_E_NOMEM, "malloc(%llu text bytes)", (unsigned long long)bytes);
-            else rb_advise_huge(*row_text, (size_t)bytes);
+            *o.row_text = (uint8_t *)malloc((size_t)bytes + 16);
+            if (!*o.row_text) rc = fail(ctx, RB_E_NOMEM, "malloc(%llu text bytes)", (unsigned long long)bytes);
+            else rb_advise_huge(*o.row_text, (size_t)bytes);
         }
-        if (!rc && bytes) rc = rb_dev_download(ctx, *row_text, d_rtext, (size_t)bytes);
+        if (!rc && bytes) rc = rb_dev_download(ctx, *o.row_text, d_rtext, (size_t)bytes);
         rb_lap("format cigars + text D2H", tl);
     }
-    if (!rc) {
-        *n_rows = nr;
-        if (counters) *counters = hc;
-    } else {
-        free(*rows);
-        free(*row_text_off);
-        free(*row_text);
-        *rows = nullptr, *row_text_off = nullptr, *row_text = nullptr;
-    }
-    return rc;
+    return o.finish(rc, nr, hc);
 }
 
 // what rb_host_liftover_largest_text adds to rb_host_liftover_text
@@ -1802,79 +1884,59 @@ struct pairs_text {
     uint8_t *key_flip; // [n_keys] OUT (host)
     int *declined;
 };
-// text in -> text out around the clip kernels; scan_only stops after the record scan (rb_host_scan_text).  lg: liftover --largest -- the hit
-// rows stay on the device, rb_dev_largest picks one per key, and only those rows come back, get format items and are printed
-// stats (rb_host_liftover_stats_text, rb_host_break_stats_text): no text out -- rb_dev_stats_rows runs on the rows and clips where the clip
-// kernels left them, and the rows come back with one reduce row each; row_text_off / row_text are not used
-static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool scan_only, uint64_t n_rec, const uint8_t *text,
-                          uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en,
-                          const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand, const uint32_t *contig, uint64_t n_win,
-                          const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en, int policy, uint8_t *cig_status,
-                          rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off,
-                          uint8_t **row_text, rb_counters *counters, const largest_text *lg = nullptr, rb_reduce_row **stats = nullptr,
-                          const pairs_text *pr = nullptr) {
-    if (!ctx || (n_rec && (!cig_off || !cig_end || !cig_status)) || (stats && (lg || scan_only)) || (pr && (lg || scan_only || !is_break))) return RB_E_INVALID;
+// what selects the route of host_lift_text: liftover over the windows (lg: --largest), break-paf at max_size (pr: --orient / --paired-len),
+// or the record scan alone (rb_host_scan_text)
+struct text_route {
+    bool is_break, scan_only;
+    uint32_t max_size;
+    int policy;
+    const largest_text *lg;
+    const pairs_text *pr;
+    static text_route liftover(int policy, const largest_text *lg) { return {false, false, 0, policy, lg, nullptr}; }
+    static text_route brk(uint32_t max_size, int policy, const pairs_text *pr) { return {true, false, max_size, policy, nullptr, pr}; }
+    static text_route scan() { return {false, true, 0, 0, nullptr, nullptr}; }
+};
+// text in -> text out around the clip kernels; scan_only stops after the record scan.  lg: the hit rows stay on the device, rb_dev_largest
+// picks one per key, and only those rows come back, get format items and are printed.  o.stats (the *_stats_text forms; not with lg): no
+// text out -- rb_dev_stats_rows runs on the rows and clips where the clip kernels left them, and the rows come back with one reduce row each
+static int host_lift_text(rb_ctx *ctx, const text_route &rt, const text_cols &c, const text_wins &w, text_outs &o) {
+    if (!text_args_ok(ctx, c, o) || (o.stats && (rt.lg || rt.scan_only))) return RB_E_INVALID;
     // liftover --qbed: the wrappers' own bit, taken out before anything reaches rb_dev_liftover
-    const bool qbed = (policy & RB_LIFT_QBED) != 0;
-    policy &= ~RB_LIFT_QBED;
-    if (qbed && (is_break || scan_only)) return fail(ctx, RB_E_INVALID, "RB_LIFT_QBED: only rb_host_liftover_text and rb_host_liftover_largest_text take it");
+    const bool qbed = (rt.policy & RB_LIFT_QBED) != 0;
+    const int policy = rt.policy & ~RB_LIFT_QBED;
+    if (qbed && (rt.is_break || rt.scan_only)) return fail(ctx, RB_E_INVALID, "RB_LIFT_QBED: only rb_host_liftover_text and rb_host_liftover_largest_text take it");
+    const largest_text *lg = rt.lg;
+    const pairs_text *pr = rt.pr;
     if (lg) *lg->declined = 0;
     if (pr) *pr->declined = 0;
-    if (stats) *stats = nullptr;
-    if (n_rec == 0) { // an empty file: no rows, no text
-        if (rows) *rows = nullptr;
-        if (n_rows) *n_rows = 0;
-        if (row_text) *row_text = nullptr;
-        if (row_text_off) {
-            *row_text_off = (uint64_t *)calloc(2, 8);
-            if (!*row_text_off) return fail(ctx, RB_E_NOMEM, "malloc");
-        }
-        if (counters) memset(counters, 0, sizeof *counters);
-        return RB_OK;
-    }
-    rb_hit_row *rows_dummy = nullptr;
-    uint64_t n_dummy = 0, *off_dummy = nullptr;
-    uint8_t *text_dummy = nullptr;
-    if (scan_only) rows = &rows_dummy, n_rows = &n_dummy, row_text_off = &off_dummy, row_text = &text_dummy;
-    if (stats) row_text_off = &off_dummy, row_text = &text_dummy;
-    if (!rows || !n_rows || !row_text_off || !row_text) return RB_E_INVALID;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    *rows = nullptr;
-    *row_text_off = nullptr;
-    *row_text = nullptr;
-    *n_rows = 0;
     DevBatch b(ctx);
-    int rc;
-    double tl = rb_now_s();
-    std::vector<uint64_t> op_off;
-    std::vector<uint32_t> zc;
-    bool parsed = false;
-    if ((rc = text_to_batch(ctx, b, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, &contig, zc, cig_status, op_off, &parsed, tl))) return rc;
-    if (!parsed) return RB_OK;
+    text_front f;
+    int rc = text_front_of(ctx, c, o, rt.scan_only, false, b, f);
+    if (rc || f.done) return rc;
+    const uint64_t n_rec = c.n_rec, n_win = w.n_win;
+    double &tl = f.tl;
     uint32_t *d_ops = (uint32_t *)b.v.ops;
-    rb_norm_row *d_norm = nullptr;
-    rb_reduce_row *d_red = nullptr;
-    if ((rc = b.alloc(n_rec, &d_norm))) return rc;
-    if (reduce_out && (rc = b.alloc(n_rec, &d_red))) return rc;
+    rb_norm_row *d_norm = f.d_norm;
+    rb_reduce_row *d_red = f.d_red;
     if (qbed) {
         // Paf::from_file's check_integrity (paf.rs:70) is the record's as read: reduce rows first, from the unswapped batch.  Then the ops
         // are swapped where they lie (the descriptors of the clip index this array), the t and q columns change places, and the scan for
         // the norm rows -- aligned_pairs' remove_trailing_indels -- sees the swapped record.
-        if (reduce_out && (rc = rb_dev_scan_records(ctx, &b.v, d_red, nullptr))) return rc;
+        if (o.reduce_out && (rc = rb_dev_scan_records(ctx, &b.v, d_red, nullptr))) return rc;
         if ((rc = rb_dev_swap(ctx, &b.v, d_ops))) return rc;
         std::swap(b.v.t_st, b.v.q_st), std::swap(b.v.t_en, b.v.q_en);
         if ((rc = rb_dev_scan_records(ctx, &b.v, nullptr, d_norm))) return rc;
     } else if ((rc = rb_dev_scan_records(ctx, &b.v, d_red, d_norm))) {
         return rc;
     }
-    if (norm_out && (rc = rb_dev_download(ctx, norm_out, d_norm, n_rec * sizeof(rb_norm_row)))) return rc;
-    if (reduce_out && (rc = rb_dev_download(ctx, reduce_out, d_red, n_rec * sizeof(rb_reduce_row)))) return rc;
+    if (o.norm_out && (rc = rb_dev_download(ctx, o.norm_out, d_norm, n_rec * sizeof(rb_norm_row)))) return rc;
+    if (o.reduce_out && (rc = rb_dev_download(ctx, o.reduce_out, d_red, n_rec * sizeof(rb_reduce_row)))) return rc;
     rb_lap("scan_records + rows D2H", tl);
-    if (scan_only) return RB_OK;
+    if (rt.scan_only) return RB_OK;
     rb_counters hc;
     rb_hit_row *d_rows = nullptr;
     uint32_t *d_out = nullptr;
-    rc = lift_sized(ctx, b, op_off.data(), contig, n_win, w_contig, w_st, w_en, d_norm, is_break, max_size, policy | RB_LIFT_DESCRIPTORS,
+    rc = lift_sized(ctx, b, f.op_off.data(), f.contig, n_win, w.w_contig, w.w_st, w.w_en, d_norm, rt.is_break, rt.max_size, policy | RB_LIFT_DESCRIPTORS,
                     &d_rows, &d_out, &hc, tl);
     uint64_t nr = hc.n_hits;
     const rb_hit_row *d_take = d_rows; // the rows that go to the host, and the descriptor of row k of them at d_take_desc[4k]
@@ -1931,15 +1993,14 @@ static int host_lift_text(rb_ctx *ctx, bool is_break, uint32_t max_size, bool sc
             return RB_OK;
         }
         nr = info.n_kept;
-        if (!stats) { // (the text tail wants row k's descriptor at [4k])
+        if (!o.stats) { // (the text tail wants row k's descriptor at [4k])
             rc = b.alloc((size_t)nr * 4 + 4, &d_pdesc);
             if (!rc && rb_launch_pairs_desc(d_prows, nr, d_out, d_pdesc, ctx->stream) != hipSuccess) rc = fail(ctx, RB_E_HIP, "rb_launch_pairs_desc");
         }
         d_rows = d_prows, d_take = d_prows, d_take_desc = d_pdesc;
         rb_lap("pairs rows", tl);
     }
-    return lift_text_tail(ctx, b, b.v, op_off.data(), rc, d_rows, d_out, d_take, d_take_desc, nr, hc, true, rows, n_rows, row_text_off, row_text, counters,
-                          stats, tl);
+    return lift_text_tail(ctx, b, f.op_off.data(), rc, {d_rows, d_out, d_take, d_take_desc, nr}, hc, true, o, tl);
 }
 
 extern "C" int rb_host_liftover_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
@@ -1948,8 +2009,9 @@ extern "C" int rb_host_liftover_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t 
                                      const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en, int policy, uint8_t *cig_status,
                                      rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows,
                                      uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters) {
-    return host_lift_text(ctx, false, 0, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig, n_win,
-                          w_contig, w_st, w_en, policy, cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, counters);
+    const text_cols c{n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig};
+    text_outs o{cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, nullptr, counters};
+    return host_lift_text(ctx, text_route::liftover(policy, nullptr), c, {n_win, w_contig, w_st, w_en}, o);
 }
 extern "C" int rb_host_liftover_largest_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
                                              const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
@@ -1964,16 +2026,18 @@ extern "C" int rb_host_liftover_largest_text(rb_ctx *ctx, uint64_t n_rec, const 
     for (uint64_t i = 0; i < n_win; i++)
         if (win_key[i] >= n_keys) return fail(ctx, RB_E_INVALID, "window %llu: key %u outside the %llu keys", (unsigned long long)i, win_key[i], (unsigned long long)n_keys);
     const largest_text lg{win_key, n_keys, inside_key, declined};
-    return host_lift_text(ctx, false, 0, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig, n_win,
-                          w_contig, w_st, w_en, policy, cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, counters, &lg);
+    const text_cols c{n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig};
+    text_outs o{cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, nullptr, counters};
+    return host_lift_text(ctx, text_route::liftover(policy, &lg), c, {n_win, w_contig, w_st, w_en}, o);
 }
 extern "C" int rb_host_break_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
                                   const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
                                   const uint64_t *q_en, const uint8_t *strand, uint32_t max_size, int policy, uint8_t *cig_status,
                                   rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows,
                                   uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters) {
-    return host_lift_text(ctx, true, max_size, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, nullptr, 0,
-                          nullptr, nullptr, nullptr, policy, cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, counters);
+    const text_cols c{n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand}; // (no contig: every record on contig 0)
+    text_outs o{cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, nullptr, counters};
+    return host_lift_text(ctx, text_route::brk(max_size, policy, nullptr), c, {}, o);
 }
 extern "C" int rb_host_liftover_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
                                            const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
@@ -1982,8 +2046,9 @@ extern "C" int rb_host_liftover_stats_text(rb_ctx *ctx, uint64_t n_rec, const ui
                                            rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows,
                                            rb_reduce_row **stats, rb_counters *counters) {
     if (!stats) return RB_E_INVALID;
-    return host_lift_text(ctx, false, 0, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig, n_win,
-                          w_contig, w_st, w_en, policy, cig_status, reduce_out, norm_out, rows, n_rows, nullptr, nullptr, counters, nullptr, stats);
+    const text_cols c{n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig};
+    text_outs o{cig_status, reduce_out, norm_out, rows, n_rows, nullptr, nullptr, stats, counters};
+    return host_lift_text(ctx, text_route::liftover(policy, nullptr), c, {n_win, w_contig, w_st, w_en}, o);
 }
 extern "C" int rb_host_break_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
                                         const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
@@ -1991,21 +2056,15 @@ extern "C" int rb_host_break_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8
                                         rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows,
                                         rb_reduce_row **stats, rb_counters *counters) {
     if (!stats) return RB_E_INVALID;
-    return host_lift_text(ctx, true, max_size, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, nullptr, 0,
-                          nullptr, nullptr, nullptr, policy, cig_status, reduce_out, norm_out, rows, n_rows, nullptr, nullptr, counters, nullptr, stats);
+    const text_cols c{n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand}; // (no contig: every record on contig 0)
+    text_outs o{cig_status, reduce_out, norm_out, rows, n_rows, nullptr, nullptr, stats, counters};
+    return host_lift_text(ctx, text_route::brk(max_size, policy, nullptr), c, {}, o);
 }
-static int break_pairs_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end,
-                            const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand, uint32_t max_size,
-                            int policy, uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows,
-                            uint64_t **row_text_off, uint8_t **row_text, rb_reduce_row **stats, rb_counters *counters, const uint32_t *rec_key,
-                            const uint64_t *rec_q_len, uint64_t n_keys, uint32_t mode, uint64_t paired_len, uint64_t min_aln, uint64_t min_query,
-                            uint8_t *key_flip, int *declined) {
-    if (!ctx || !declined || (n_rec && (!rec_key || !rec_q_len || !strand)) || (n_keys && !key_flip)) return RB_E_INVALID;
-    if (mode & ~(uint32_t)(RB_PAIRS_ORIENT | RB_PAIRS_FILTER)) return fail(ctx, RB_E_INVALID, "mode %u: RB_PAIRS_ORIENT | RB_PAIRS_FILTER", mode);
-    if (n_keys) memset(key_flip, 0, (size_t)n_keys);
-    const pairs_text pr{rec_key, rec_q_len, n_keys, mode, paired_len, min_aln, min_query, key_flip, declined};
-    return host_lift_text(ctx, true, max_size, false, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, nullptr, 0, nullptr,
-                          nullptr, nullptr, policy, cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, counters, nullptr, stats, &pr);
+static int break_pairs_text(rb_ctx *ctx, const text_cols &c, uint32_t max_size, int policy, text_outs &o, const pairs_text &pr) {
+    if (!ctx || !pr.declined || (c.n_rec && (!pr.rec_key || !pr.rec_q_len || !c.strand)) || (pr.n_keys && !pr.key_flip)) return RB_E_INVALID;
+    if (pr.mode & ~(uint32_t)(RB_PAIRS_ORIENT | RB_PAIRS_FILTER)) return fail(ctx, RB_E_INVALID, "mode %u: RB_PAIRS_ORIENT | RB_PAIRS_FILTER", pr.mode);
+    if (pr.n_keys) memset(pr.key_flip, 0, (size_t)pr.n_keys);
+    return host_lift_text(ctx, text_route::brk(max_size, policy, &pr), c, {}, o);
 }
 extern "C" int rb_host_break_pairs_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
                                         const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
@@ -2013,9 +2072,10 @@ extern "C" int rb_host_break_pairs_text(rb_ctx *ctx, uint64_t n_rec, const uint8
                                         rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, uint64_t **row_text_off, uint8_t **row_text,
                                         rb_counters *counters, const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_keys, uint32_t mode,
                                         uint64_t paired_len, uint64_t min_aln, uint64_t min_query, uint8_t *key_flip, int *declined) {
-    return break_pairs_text(ctx, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, max_size, policy, cig_status, reduce_out, norm_out,
-                            rows, n_rows, row_text_off, row_text, nullptr, counters, rec_key, rec_q_len, n_keys, mode, paired_len, min_aln, min_query, key_flip,
-                            declined);
+    const text_cols c{n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand}; // (no contig: every record on contig 0)
+    text_outs o{cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, nullptr, counters};
+    const pairs_text pr{rec_key, rec_q_len, n_keys, mode, paired_len, min_aln, min_query, key_flip, declined};
+    return break_pairs_text(ctx, c, max_size, policy, o, pr);
 }
 extern "C" int rb_host_break_pairs_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
                                               const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
@@ -2024,16 +2084,18 @@ extern "C" int rb_host_break_pairs_stats_text(rb_ctx *ctx, uint64_t n_rec, const
                                               rb_counters *counters, const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_keys, uint32_t mode,
                                               uint64_t paired_len, uint64_t min_aln, uint64_t min_query, uint8_t *key_flip, int *declined) {
     if (!stats) return RB_E_INVALID;
-    return break_pairs_text(ctx, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, max_size, policy, cig_status, reduce_out, norm_out,
-                            rows, n_rows, nullptr, nullptr, stats, counters, rec_key, rec_q_len, n_keys, mode, paired_len, min_aln, min_query, key_flip,
-                            declined);
+    const text_cols c{n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand}; // (no contig: every record on contig 0)
+    text_outs o{cig_status, reduce_out, norm_out, rows, n_rows, nullptr, nullptr, stats, counters};
+    const pairs_text pr{rec_key, rec_q_len, n_keys, mode, paired_len, min_aln, min_query, key_flip, declined};
+    return break_pairs_text(ctx, c, max_size, policy, o, pr);
 }
 extern "C" int rb_host_scan_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
                                  const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
                                  const uint64_t *q_en, const uint8_t *strand, uint8_t *cig_status, rb_reduce_row *reduce_out,
                                  rb_norm_row *norm_out) {
-    return host_lift_text(ctx, false, 0, true, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, nullptr, 0, nullptr,
-                          nullptr, nullptr, 0, cig_status, reduce_out, norm_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+    const text_cols c{n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand};
+    text_outs o{cig_status, reduce_out, norm_out}; // (no rows, no text, no counters: the pack's own storage stands in)
+    return host_lift_text(ctx, text_route::scan(), c, {}, o);
 }
 
 // ---- `rb break-paf --max-size N in.paf | rb liftover --bed W -` as one device pipeline (rb_host_break_liftover_text / _stats_text) ------
@@ -2041,52 +2103,31 @@ extern "C" int rb_host_scan_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *tex
 // pieces (its check_integrity and aligned_pairs' remove_trailing_indels), a plan over the pieces, liftover in descriptor mode on the piece
 // batch, and the tail of host_lift_text.  The first clip call's rows, descriptors and workspace are freed before the second call sizes its
 // own.  Whatever only the record route prints right -- a panic in either stage, a piece whose own id would be _TO.<..> -- sets *declined.
-static int host_break_lift_text(rb_ctx *ctx, uint32_t max_size, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
-                                const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
-                                const uint8_t *strand, const uint32_t *contig, uint64_t n_win, const uint32_t *w_contig, const uint64_t *w_st,
-                                const uint64_t *w_en, int policy, uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows,
-                                uint64_t *n_rows, uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters, uint32_t **row_piece, int *declined,
-                                rb_reduce_row **stats) {
-    if (!ctx || !rows || !n_rows || !row_piece || !declined || (n_rec && (!cig_off || !cig_end || !cig_status))) return RB_E_INVALID;
-    if (!stats && (!row_text_off || !row_text)) return RB_E_INVALID;
+static int host_break_lift_text(rb_ctx *ctx, uint32_t max_size, int policy, const text_cols &c, const text_wins &w, text_outs &o, uint32_t **row_piece,
+                                int *declined) {
+    if (!text_args_ok(ctx, c, o) || !o.rows || !o.n_rows || !row_piece || !declined) return RB_E_INVALID;
+    if (!o.stats && (!o.row_text_off || !o.row_text)) return RB_E_INVALID;
     if (policy & RB_LIFT_QBED) return fail(ctx, RB_E_INVALID, "RB_LIFT_QBED: the break-paf | liftover pipeline lifts over target windows only");
-    uint64_t *off_dummy = nullptr;
-    uint8_t *text_dummy = nullptr;
-    if (stats) *stats = nullptr, row_text_off = &off_dummy, row_text = &text_dummy;
-    *rows = nullptr, *n_rows = 0, *row_text_off = nullptr, *row_text = nullptr, *row_piece = nullptr, *declined = 0;
-    if (counters) memset(counters, 0, sizeof *counters);
-    auto empty = [&]() -> int { // no record reaches the second command: no rows, no text
-        if (!stats && !(*row_text_off = (uint64_t *)calloc(2, 8))) return fail(ctx, RB_E_NOMEM, "malloc");
-        return RB_OK;
-    };
-    if (n_rec == 0) return empty();
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    *row_piece = nullptr, *declined = 0;
     DevBatch b(ctx), pb(ctx); // the input batch; the piece batch
-    int rc;
-    double tl = rb_now_s();
-    std::vector<uint64_t> op_off;
-    std::vector<uint32_t> zc;
-    bool parsed = false;
     // (break-paf's rows come in record order: its plan sees every record on contig 0, as rb_host_break_text's does; the records' own contigs
     //  go to the device beside the batch, for the pieces to inherit)
-    const uint32_t *no_contig = nullptr, *d_contig = nullptr;
-    if ((rc = text_to_batch(ctx, b, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, &no_contig, zc, cig_status, op_off, &parsed, tl))) return rc;
-    if (!parsed) return RB_OK;
-    if (contig && (rc = b.up(contig, (size_t)n_rec, &d_contig))) return rc;
+    text_front f;
+    int rc = text_front_of(ctx, c, o, false, true, b, f);
+    if (rc || f.done) return rc;
+    const uint64_t n_rec = c.n_rec;
+    double &tl = f.tl;
     rb_batch_view sv = b.v; // what rb_dev_rows_to_batch reads strand and contig from
-    if (d_contig) sv.contig = d_contig;
+    if (f.d_contig) sv.contig = f.d_contig;
     // ---- the first command: Paf::from_file's check_integrity, aligned_pairs, break_paf_on_indels ----
-    rb_norm_row *d_norm = nullptr;
-    rb_reduce_row *d_red = nullptr;
+    rb_norm_row *d_norm = f.d_norm;
     std::vector<rb_norm_row> norm((size_t)n_rec);
     std::vector<rb_reduce_row> red((size_t)n_rec);
-    if ((rc = b.alloc(n_rec, &d_norm))) return rc;
-    if ((rc = b.alloc(n_rec, &d_red))) return rc;
-    if ((rc = rb_dev_scan_records(ctx, &b.v, d_red, d_norm))) return rc;
+    if ((rc = rb_dev_scan_records(ctx, &b.v, f.d_red, d_norm))) return rc;
     if ((rc = rb_dev_download(ctx, norm.data(), d_norm, n_rec * sizeof(rb_norm_row)))) return rc;
-    if ((rc = rb_dev_download(ctx, red.data(), d_red, n_rec * sizeof(rb_reduce_row)))) return rc;
-    if (norm_out) memcpy(norm_out, norm.data(), n_rec * sizeof(rb_norm_row));
-    if (reduce_out) memcpy(reduce_out, red.data(), n_rec * sizeof(rb_reduce_row));
+    if ((rc = rb_dev_download(ctx, red.data(), f.d_red, n_rec * sizeof(rb_reduce_row)))) return rc;
+    if (o.norm_out) memcpy(o.norm_out, norm.data(), n_rec * sizeof(rb_norm_row));
+    if (o.reduce_out) memcpy(o.reduce_out, red.data(), n_rec * sizeof(rb_reduce_row));
     rb_lap("scan_records + rows D2H", tl);
     for (uint64_t r = 0; r < n_rec; r++)
         if (red[r].status != RB_ST_OK || norm[r].status != RB_ST_OK) { // the first command panics: before it prints (from_file), or part-way
@@ -2101,7 +2142,7 @@ static int host_break_lift_text(rb_ctx *ctx, uint32_t max_size, uint64_t n_rec, 
     rb_counters hc;
     rb_hit_row *d_rows = nullptr;
     uint32_t *d_out = nullptr;
-    if ((rc = lift_sized(ctx, b, op_off.data(), no_contig, 0, nullptr, nullptr, nullptr, d_norm, true, max_size, policy | RB_LIFT_DESCRIPTORS, &d_rows, &d_out, &hc, tl)))
+    if ((rc = lift_sized(ctx, b, f.op_off.data(), f.contig, 0, nullptr, nullptr, nullptr, d_norm, true, max_size, policy | RB_LIFT_DESCRIPTORS, &d_rows, &d_out, &hc, tl)))
         return rc;
     // ---- the pieces as a batch ----
     rb_pieces_info info, *d_info = nullptr;
@@ -2116,7 +2157,10 @@ static int host_break_lift_text(rb_ctx *ctx, uint32_t max_size, uint64_t n_rec, 
         return RB_OK;
     }
     const uint64_t n_p = info.n_pieces;
-    if (n_p == 0) return empty();
+    if (n_p == 0) { // no record reaches the second command: no rows, no text, as for an empty file
+        if (!o.stats && !(*o.row_text_off = (uint64_t *)calloc(2, 8))) return fail(ctx, RB_E_NOMEM, "malloc");
+        return RB_OK;
+    }
     uint32_t *p_ops = nullptr, *p_contig = nullptr, *p_parent = nullptr;
     uint64_t *p_off = nullptr, *p_c[4] = {nullptr, nullptr, nullptr, nullptr};
     uint8_t *p_strand = nullptr;
@@ -2154,15 +2198,17 @@ static int host_break_lift_text(rb_ctx *ctx, uint32_t max_size, uint64_t n_rec, 
         }
     rb_hit_row *d_rows2 = nullptr;
     uint32_t *d_out2 = nullptr;
-    rc = lift_sized(ctx, pb, pop_off.data(), pcontig.data(), n_win, w_contig, w_st, w_en, d_pnorm, false, 0, policy | RB_LIFT_DESCRIPTORS, &d_rows2, &d_out2, &hc, tl);
-    rc = lift_text_tail(ctx, pb, pb.v, pop_off.data(), rc, d_rows2, d_out2, d_rows2, d_out2, hc.n_hits, hc, false, rows, n_rows, row_text_off, row_text, counters,
-                        stats, tl);
+    rc = lift_sized(ctx, pb, pop_off.data(), pcontig.data(), w.n_win, w.w_contig, w.w_st, w.w_en, d_pnorm, false, 0, policy | RB_LIFT_DESCRIPTORS, &d_rows2, &d_out2, &hc, tl);
+    rc = lift_text_tail(ctx, pb, pop_off.data(), rc, {d_rows2, d_out2, d_rows2, d_out2, hc.n_hits}, hc, false, o, tl);
     if (rc) return rc;
     // ---- rows back in the input's terms: rec = the parent record, row_piece = the piece ----
-    *row_piece = (uint32_t *)malloc(((size_t)*n_rows + 1) * 4);
-    if (!*row_piece) return fail(ctx, RB_E_NOMEM, "malloc(row_piece)");
-    for (uint64_t k = 0; k < *n_rows; k++) {
-        rb_hit_row &h = (*rows)[k];
+    *row_piece = (uint32_t *)malloc(((size_t)*o.n_rows + 1) * 4);
+    if (!*row_piece) {
+        o.drop();
+        return fail(ctx, RB_E_NOMEM, "malloc(row_piece)");
+    }
+    for (uint64_t k = 0; k < *o.n_rows; k++) {
+        rb_hit_row &h = (*o.rows)[k];
         if (h.status >= RB_ST_PANIC_NOTFOUND) *declined = 1; // the second command panics inside trim_paf_by_rgns
         (*row_piece)[k] = h.rec;
         h.rec = parent[h.rec];
@@ -2175,8 +2221,9 @@ extern "C" int rb_host_break_liftover_text(rb_ctx *ctx, uint64_t n_rec, const ui
                                            const uint32_t *w_contig, const uint64_t *w_st, const uint64_t *w_en, uint32_t max_size, int policy,
                                            uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows,
                                            uint64_t **row_text_off, uint8_t **row_text, rb_counters *counters, uint32_t **row_piece, int *declined) {
-    return host_break_lift_text(ctx, max_size, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig, n_win, w_contig, w_st, w_en,
-                                policy, cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, counters, row_piece, declined, nullptr);
+    const text_cols c{n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig};
+    text_outs o{cig_status, reduce_out, norm_out, rows, n_rows, row_text_off, row_text, nullptr, counters};
+    return host_break_lift_text(ctx, max_size, policy, c, {n_win, w_contig, w_st, w_en}, o, row_piece, declined);
 }
 extern "C" int rb_host_break_liftover_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off,
                                                  const uint64_t *cig_end, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st,
@@ -2185,8 +2232,9 @@ extern "C" int rb_host_break_liftover_stats_text(rb_ctx *ctx, uint64_t n_rec, co
                                                  uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out, rb_hit_row **rows,
                                                  uint64_t *n_rows, rb_reduce_row **stats, rb_counters *counters, uint32_t **row_piece, int *declined) {
     if (!stats) return RB_E_INVALID;
-    return host_break_lift_text(ctx, max_size, n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig, n_win, w_contig, w_st, w_en,
-                                policy, cig_status, reduce_out, norm_out, rows, n_rows, nullptr, nullptr, counters, row_piece, declined, stats);
+    const text_cols c{n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, contig};
+    text_outs o{cig_status, reduce_out, norm_out, rows, n_rows, nullptr, nullptr, stats, counters};
+    return host_break_lift_text(ctx, max_size, policy, c, {n_win, w_contig, w_st, w_en}, o, row_piece, declined);
 }
 
 extern "C" int rb_host_swap(rb_ctx *ctx, uint64_t n_rec, const uint32_t *ops, const uint64_t *op_off, const uint8_t *strand,

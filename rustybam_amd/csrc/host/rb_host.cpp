@@ -26,6 +26,7 @@
 #include <unordered_map>
 #include <unordered_set>
 #include <thread>
+#include <tuple>
 
 namespace rb {
 
@@ -1255,6 +1256,52 @@ std::vector<std::string> assemble_lines(const TextFile &f, const std::vector<rb_
     });
     return out_text;
 }
+// what every text route allocates around its call, for a loaded file
+struct TextCall {
+    TextFile &f;
+    std::vector<uint8_t> cig_status;
+    std::vector<rb_reduce_row> red;
+    std::vector<rb_norm_row> norm;
+    TextRows R;
+    rb_counters cnt{};
+    int declined = 0;
+    explicit TextCall(TextFile &f_) : f(f_), cig_status(f_.recs.size() ? f_.recs.size() : 1), red(f_.recs.size()), norm(f_.recs.size()) {}
+    bool loaded() const { return f.check_loaded(cig_status, red); } // (throws the panics of Paf::from_file, in the reference's order of checks)
+    void panic_on_norm() const { for (size_t i = 0; i < norm.size(); i++) panic_on(norm[i].status, "aligned_pairs", i); }
+};
+// the columns every text entry point starts with
+auto text_columns(const Engine &eng, const TextFile &f) {
+    return std::make_tuple(eng.ctx(), f.recs.size(), (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
+                           f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data());
+}
+#define RB_ENTRY(fn) fn, #fn // an entry point and its name, stated once: what Engine::check reports and what the RB_TIMING lap is called
+// One call of a text entry point: the shared columns, the route's own `mid` arguments (contig + windows, max_size, or both), the policy and
+// the shared outputs -- &R.stats in place of &R.toff, &R.text for a *_stats_text form --, the counters, the route's own `tail` arguments
+// (none, the largest keys, the pairs arguments, or &row_piece, &declined).  tl: the clock of the lap that follows (NULL: none).
+template <bool StatsForm, typename Fn, typename Mid, typename Tail = std::tuple<>>
+void text_call(Engine &eng, Fn fn, const char *name, TextCall &c, int policy, double *tl, const Mid &mid, const Tail &tail = Tail()) {
+    TextRows &R = c.R;
+    const auto head = std::tuple_cat(text_columns(eng, c.f), mid, std::make_tuple(policy, c.cig_status.data(), c.red.data(), c.norm.data(), &R.rows, &R.n_rows));
+    const auto end = std::tuple_cat(std::make_tuple(&c.cnt), tail);
+    if constexpr (StatsForm) eng.check(std::apply(fn, std::tuple_cat(head, std::make_tuple(&R.stats), end)), name);
+    else eng.check(std::apply(fn, std::tuple_cat(head, std::make_tuple(&R.toff, &R.text), end)), name);
+    if (tl) lap(name, *tl);
+}
+// the windows of `rgns` as the ABI wants them; a name no record is on gets an id of its own in f.contig_id
+struct Windows {
+    std::vector<uint32_t> contig;
+    std::vector<uint64_t> st, en;
+    auto args(const TextFile &f) const { return std::make_tuple(f.contig.data(), (uint64_t)st.size(), contig.data(), st.data(), en.data()); } // the records' contigs, the windows
+};
+Windows windows_of(TextFile &f, const std::vector<Region> &rgns) {
+    Windows w{std::vector<uint32_t>(rgns.size()), std::vector<uint64_t>(rgns.size()), std::vector<uint64_t>(rgns.size())};
+    for (size_t i = 0; i < rgns.size(); i++) {
+        auto it = f.contig_id.find(std::string_view(rgns[i].name));
+        if (it == f.contig_id.end()) it = f.contig_id.emplace(std::string_view(rgns[i].name), (uint32_t)f.contig_id.size()).first; // no record there
+        w.contig[i] = it->second, w.st[i] = rgns[i].st, w.en[i] = rgns[i].en;
+    }
+    return w;
+}
 } // namespace
 
 // largest: main.rs:200-208 on the device (rb_host_liftover_largest_text) -- the rows that come back are the one record per id, in id order
@@ -1272,24 +1319,12 @@ static bool lift_file_text(Engine &eng, const std::string &paf_path, const std::
     if (!f.load(paf_path, nullptr, qbed)) return false; // the caller takes the general path
     const int policy = eng.bsearch_policy | (qbed ? RB_LIFT_QBED : 0);
     double tl = now_s();
-    const size_t n = f.recs.size();
     if (runs) { // the records' contigs by first appearance (before windows on other names get ids of their own below)
         runs->contigs.assign(f.contig_id.size(), std::string());
         for (const auto &kv : f.contig_id) runs->contigs[kv.second].assign(kv.first.data(), kv.first.size());
     }
-    std::vector<uint32_t> w_contig(rgns.size());
-    std::vector<uint64_t> w_st(rgns.size()), w_en(rgns.size());
-    for (size_t i = 0; i < rgns.size(); i++) {
-        auto it = f.contig_id.find(std::string_view(rgns[i].name));
-        if (it == f.contig_id.end()) it = f.contig_id.emplace(std::string_view(rgns[i].name), (uint32_t)f.contig_id.size()).first; // no record there
-        w_contig[i] = it->second, w_st[i] = rgns[i].st, w_en[i] = rgns[i].en;
-    }
-    std::vector<uint8_t> cig_status(n ? n : 1);
-    std::vector<rb_reduce_row> red(n);
-    std::vector<rb_norm_row> norm(n);
-    TextRows &R = *new TextRows;
-    rb_counters cnt;
-    int declined = 0;
+    const Windows w = windows_of(f, rgns);
+    TextCall &c = *new TextCall(f);
     if (largest) {
         // the ids as keys: the window ids and "" (the id of a record that lies inside its window, liftover.rs:23-25), numbered in ascending
         // bytewise order -- Rust's String order, the order of main.rs:201's sort -- so the rows come back in the order they are printed in
@@ -1299,37 +1334,21 @@ static bool lift_file_text(Engine &eng, const std::string &paf_path, const std::
         ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
         std::vector<uint32_t> win_key(rgns.size());
         for (size_t i = 0; i < rgns.size(); i++) win_key[i] = (uint32_t)(std::lower_bound(ids.begin(), ids.end(), std::string_view(rgns[i].id)) - ids.begin());
-        eng.check(rb_host_liftover_largest_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(),
-                                                f.t_st.data(), f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(),
-                                                w_contig.data(), w_st.data(), w_en.data(), policy, cig_status.data(), red.data(),
-                                                norm.data(), &R.rows, &R.n_rows, &R.toff, &R.text, &cnt, win_key.data(), ids.size(), 0u, &declined),
-                  "rb_host_liftover_largest_text");
-        lap("rb_host_liftover_largest_text", tl);
-    } else if (st) {
-        eng.check(rb_host_liftover_stats_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
-                                              f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(), w_contig.data(),
-                                              w_st.data(), w_en.data(), policy, cig_status.data(), red.data(), norm.data(), &R.rows,
-                                              &R.n_rows, &R.stats, &cnt),
-                  "rb_host_liftover_stats_text");
-        lap("rb_host_liftover_stats_text", tl);
+        text_call<false>(eng, RB_ENTRY(rb_host_liftover_largest_text), c, policy, &tl, w.args(f), std::make_tuple(win_key.data(), ids.size(), 0u, &c.declined));
     } else {
-        eng.check(rb_host_liftover_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
-                                        f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(), w_contig.data(),
-                                        w_st.data(), w_en.data(), policy, cig_status.data(), red.data(), norm.data(), &R.rows,
-                                        &R.n_rows, &R.toff, &R.text, &cnt),
-                  "rb_host_liftover_text");
-        lap("rb_host_liftover_text", tl);
+        st ? text_call<true>(eng, RB_ENTRY(rb_host_liftover_stats_text), c, policy, &tl, w.args(f))
+           : text_call<false>(eng, RB_ENTRY(rb_host_liftover_text), c, policy, &tl, w.args(f));
     }
-    if (!f.check_loaded(cig_status, red)) return false; // (qbed: the reduce rows are the records' as read, the norm rows the swapped records')
-    for (size_t i = 0; i < n; i++) panic_on(norm[i].status, "aligned_pairs", i); // liftover.rs:119-121
-    if (declined) return false; // a stripped record inside a window, or a hit row that panics: the record route knows its id / replays the panic
+    if (!c.loaded()) return false; // (qbed: the reduce rows are the records' as read, the norm rows the swapped records')
+    c.panic_on_norm(); // liftover.rs:119-121
+    if (c.declined) return false; // a stripped record inside a window, or a hit row that panics: the record route knows its id / replays the panic
     if (st) {
-        out_text = stats_lines_of_file(f, R, qbed, st->stats_qbed, *st->trailing);
+        out_text = stats_lines_of_file(f, c.R, qbed, st->stats_qbed, *st->trailing);
         lap("stats lines", tl);
         return true;
     }
     RunMarks marks;
-    out_text = assemble_lines(f, norm, R, &rgns, runs ? &marks : nullptr, qbed);
+    out_text = assemble_lines(f, c.norm, c.R, &rgns, runs ? &marks : nullptr, qbed);
     if (runs) marks_to_runs(marks, out_text, *runs);
     lap("assemble lines", tl);
     return true;
@@ -1354,26 +1373,13 @@ static bool break_file_text_impl(Engine &eng, const std::string &paf_path, uint3
     TextFile &f = *new TextFile;
     if (!f.load(paf_path)) return false;
     double tl = now_s();
-    const size_t n = f.recs.size();
-    std::vector<uint8_t> cig_status(n ? n : 1);
-    std::vector<rb_reduce_row> red(n);
-    std::vector<rb_norm_row> norm(n);
-    TextRows &R = *new TextRows;
-    rb_counters cnt;
-    if (st)
-        eng.check(rb_host_break_stats_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
-                                           f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), break_length, eng.bsearch_policy,
-                                           cig_status.data(), red.data(), norm.data(), &R.rows, &R.n_rows, &R.stats, &cnt),
-                  "rb_host_break_stats_text");
-    else
-        eng.check(rb_host_break_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
-                                     f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), break_length, eng.bsearch_policy, cig_status.data(),
-                                     red.data(), norm.data(), &R.rows, &R.n_rows, &R.toff, &R.text, &cnt),
-                  "rb_host_break_text");
-    lap(st ? "rb_host_break_stats_text" : "rb_host_break_text", tl);
-    if (!f.check_loaded(cig_status, red)) return false;
-    for (size_t i = 0; i < n; i++) panic_on(norm[i].status, "aligned_pairs", i); // main.rs:275
-    out_text = st ? stats_lines_of_file(f, R, false, st->stats_qbed, *st->trailing) : assemble_lines(f, norm, R, nullptr);
+    TextCall &c = *new TextCall(f);
+    const auto mid = std::make_tuple(break_length);
+    st ? text_call<true>(eng, RB_ENTRY(rb_host_break_stats_text), c, eng.bsearch_policy, &tl, mid)
+       : text_call<false>(eng, RB_ENTRY(rb_host_break_text), c, eng.bsearch_policy, &tl, mid);
+    if (!c.loaded()) return false;
+    c.panic_on_norm(); // main.rs:275
+    out_text = st ? stats_lines_of_file(f, c.R, false, st->stats_qbed, *st->trailing) : assemble_lines(f, c.norm, c.R, nullptr);
     lap(st ? "stats lines" : "assemble lines", tl);
     return true;
 }
@@ -1412,32 +1418,18 @@ bool break_pairs_file_text(Engine &eng, const std::string &paf_path, uint32_t br
     }
     std::vector<uint8_t> key_flip(ids.size() + 1, 0);
     lap("pair keys", tl);
-    std::vector<uint8_t> cig_status(n ? n : 1);
-    std::vector<rb_reduce_row> red(n);
-    std::vector<rb_norm_row> norm(n);
-    TextRows &R = *new TextRows;
-    rb_counters cnt;
-    int declined = 0;
+    TextCall &c = *new TextCall(f);
     const uint32_t mode = (orient ? RB_PAIRS_ORIENT : 0) | (filter ? RB_PAIRS_FILTER : 0);
-    if (stats_mode)
-        eng.check(rb_host_break_pairs_stats_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
-                                                 f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), break_length, eng.bsearch_policy, cig_status.data(),
-                                                 red.data(), norm.data(), &R.rows, &R.n_rows, &R.stats, &cnt, rec_key.data(), rec_q_len.data(), ids.size(), mode,
-                                                 paired_len, min_aln, min_query, key_flip.data(), &declined),
-                  "rb_host_break_pairs_stats_text");
-    else
-        eng.check(rb_host_break_pairs_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
-                                           f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), break_length, eng.bsearch_policy, cig_status.data(),
-                                           red.data(), norm.data(), &R.rows, &R.n_rows, &R.toff, &R.text, &cnt, rec_key.data(), rec_q_len.data(), ids.size(), mode,
-                                           paired_len, min_aln, min_query, key_flip.data(), &declined),
-                  "rb_host_break_pairs_text");
-    lap(stats_mode ? "rb_host_break_pairs_stats_text" : "rb_host_break_pairs_text", tl);
-    if (!f.check_loaded(cig_status, red)) return false;
-    for (size_t i = 0; i < n; i++)
-        if (norm[i].status != RB_ST_OK) return false; // (the first command panics part-way: the record route knows what reached the second)
-    if (declined) return false;
+    const auto mid = std::make_tuple(break_length);
+    const auto pairs = std::make_tuple(rec_key.data(), rec_q_len.data(), ids.size(), mode, paired_len, min_aln, min_query, key_flip.data(), &c.declined);
+    stats_mode ? text_call<true>(eng, RB_ENTRY(rb_host_break_pairs_stats_text), c, eng.bsearch_policy, &tl, mid, pairs)
+               : text_call<false>(eng, RB_ENTRY(rb_host_break_pairs_text), c, eng.bsearch_policy, &tl, mid, pairs);
+    if (!c.loaded()) return false;
+    for (const rb_norm_row &nr : c.norm)
+        if (nr.status != RB_ST_OK) return false; // (the first command panics part-way: the record route knows what reached the second)
+    if (c.declined) return false;
     const PairNames pn{&rec_key, &key_flip, orient};
-    out_text = stats_mode ? stats_lines_of_file(f, R, false, stats_mode == 2, trailing_panic, &pn) : assemble_lines(f, norm, R, nullptr, nullptr, false, &pn);
+    out_text = stats_mode ? stats_lines_of_file(f, c.R, false, stats_mode == 2, trailing_panic, &pn) : assemble_lines(f, c.norm, c.R, nullptr, nullptr, false, &pn);
     lap(stats_mode ? "stats lines" : "assemble lines", tl);
     return true;
 }
@@ -1480,43 +1472,22 @@ bool break_liftover_file_text(Engine &eng, const std::string &paf_path, const st
     TextFile &f = *new TextFile; // (one-shot command, as lift_file_text)
     if (!f.load(paf_path)) return false;
     double tl = now_s();
-    const size_t n = f.recs.size();
-    std::vector<uint32_t> w_contig(rgns.size());
-    std::vector<uint64_t> w_st(rgns.size()), w_en(rgns.size());
-    for (size_t i = 0; i < rgns.size(); i++) {
-        auto it = f.contig_id.find(std::string_view(rgns[i].name));
-        if (it == f.contig_id.end()) it = f.contig_id.emplace(std::string_view(rgns[i].name), (uint32_t)f.contig_id.size()).first; // no record there
-        w_contig[i] = it->second, w_st[i] = rgns[i].st, w_en[i] = rgns[i].en;
-    }
-    std::vector<uint8_t> cig_status(n ? n : 1);
-    std::vector<rb_reduce_row> red(n);
-    std::vector<rb_norm_row> norm(n);
-    TextRows &R = *new TextRows;
+    const Windows w = windows_of(f, rgns);
+    TextCall &c = *new TextCall(f);
     uint32_t *row_piece = nullptr;
-    rb_counters cnt;
-    int declined = 0;
-    if (stats_mode)
-        eng.check(rb_host_break_liftover_stats_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
-                                                    f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(), w_contig.data(),
-                                                    w_st.data(), w_en.data(), break_length, eng.bsearch_policy, cig_status.data(), red.data(), norm.data(), &R.rows,
-                                                    &R.n_rows, &R.stats, &cnt, &row_piece, &declined),
-                  "rb_host_break_liftover_stats_text");
-    else
-        eng.check(rb_host_break_liftover_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
-                                              f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), f.contig.data(), rgns.size(), w_contig.data(),
-                                              w_st.data(), w_en.data(), break_length, eng.bsearch_policy, cig_status.data(), red.data(), norm.data(), &R.rows,
-                                              &R.n_rows, &R.toff, &R.text, &cnt, &row_piece, &declined),
-                  "rb_host_break_liftover_text");
+    const auto mid = std::tuple_cat(w.args(f), std::make_tuple(break_length));
+    const auto pieces = std::make_tuple(&row_piece, &c.declined);
+    stats_mode ? text_call<true>(eng, RB_ENTRY(rb_host_break_liftover_stats_text), c, eng.bsearch_policy, &tl, mid, pieces)
+               : text_call<false>(eng, RB_ENTRY(rb_host_break_liftover_text), c, eng.bsearch_policy, &tl, mid, pieces);
     rb_host_free(row_piece); // (which piece a row came from is not printed)
-    lap(stats_mode ? "rb_host_break_liftover_stats_text" : "rb_host_break_liftover_text", tl);
-    if (!f.check_loaded(cig_status, red)) return false; // (throws the panics of the first command's Paf::from_file, in its order of checks)
-    if (declined) return false;
-    if (stats_mode) {
-        out_text = stats_lines_of_file(f, R, false, stats_mode == 2, trailing_panic);
+    if (!c.loaded()) return false; // (throws the panics of the first command's Paf::from_file, in its order of checks)
+    if (c.declined) return false;
+    if (stats_mode) { // (no lap of its own: the RB_TIMING lines of this route end with the call's)
+        out_text = stats_lines_of_file(f, c.R, false, stats_mode == 2, trailing_panic);
         return true;
     }
-    const std::vector<rb_norm_row> own_id(n); // (all zero: a piece has no id of its own, and none that was stripped got here)
-    out_text = assemble_lines(f, own_id, R, &rgns);
+    const std::vector<rb_norm_row> own_id(f.recs.size()); // (all zero: a piece has no id of its own, and none that was stripped got here)
+    out_text = assemble_lines(f, own_id, c.R, &rgns);
     lap("assemble lines", tl);
     return true;
 }
@@ -1615,40 +1586,20 @@ bool lift_file_text_pipelined(int device, int bsearch_policy, bool is_break, uin
                     if (!f.load(paf_path, &range)) {
                         R.general = true;
                     } else {
-                        const size_t n = f.recs.size();
+                        // the records' contigs by first appearance, before windows on other names get ids of their own
                         R.runs.contigs.assign(f.contig_id.size(), std::string());
                         for (const auto &kv : f.contig_id) R.runs.contigs[kv.second].assign(kv.first.data(), kv.first.size());
-                        std::vector<uint32_t> w_contig(rgns.size());
-                        std::vector<uint64_t> w_st(rgns.size()), w_en(rgns.size());
-                        for (size_t i = 0; i < rgns.size(); i++) {
-                            auto it = f.contig_id.find(std::string_view(rgns[i].name));
-                            if (it == f.contig_id.end()) it = f.contig_id.emplace(std::string_view(rgns[i].name), (uint32_t)f.contig_id.size()).first;
-                            w_contig[i] = it->second, w_st[i] = rgns[i].st, w_en[i] = rgns[i].en;
-                        }
-                        std::vector<uint8_t> cig_status(n ? n : 1);
-                        std::vector<rb_reduce_row> red(n);
-                        std::vector<rb_norm_row> norm(n);
-                        TextRows TR;
-                        rb_counters cnt;
-                        if (is_break)
-                            eng->check(rb_host_break_text(eng->ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(),
-                                                          f.t_st.data(), f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), break_length,
-                                                          bsearch_policy, cig_status.data(), red.data(), norm.data(), &TR.rows, &TR.n_rows, &TR.toff,
-                                                          &TR.text, &cnt),
-                                       "rb_host_break_text");
-                        else
-                            eng->check(rb_host_liftover_text(eng->ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(),
-                                                             f.cig_end.data(), f.t_st.data(), f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(),
-                                                             f.contig.data(), rgns.size(), w_contig.data(), w_st.data(), w_en.data(), bsearch_policy,
-                                                             cig_status.data(), red.data(), norm.data(), &TR.rows, &TR.n_rows, &TR.toff, &TR.text, &cnt),
-                                       "rb_host_liftover_text");
-                        if (!f.check_loaded(cig_status, red)) {
+                        const Windows w = windows_of(f, rgns);
+                        TextCall c(f);
+                        if (is_break) text_call<false>(*eng, RB_ENTRY(rb_host_break_text), c, bsearch_policy, nullptr, std::make_tuple(break_length));
+                        else text_call<false>(*eng, RB_ENTRY(rb_host_liftover_text), c, bsearch_policy, nullptr, w.args(f));
+                        if (!c.loaded()) {
                             R.general = true;
                         } else {
                             loaded = true;
-                            for (size_t i = 0; i < n; i++) panic_on(norm[i].status, "aligned_pairs", i);
+                            c.panic_on_norm();
                             RunMarks marks;
-                            R.text = assemble_lines(f, norm, TR, is_break ? nullptr : &rgns, &marks);
+                            R.text = assemble_lines(f, c.norm, c.R, is_break ? nullptr : &rgns, &marks);
                             marks_to_runs(marks, R.text, R.runs);
                             if (is_break) { // (record order: one run)
                                 uint64_t total = 0;
@@ -1997,8 +1948,7 @@ bool stats_file_text(Engine &eng, const std::string &paf_path, bool qbed, std::v
     const size_t n = f.recs.size();
     std::vector<uint8_t> cig_status(n ? n : 1);
     std::vector<rb_reduce_row> red(n);
-    eng.check(rb_host_scan_text(eng.ctx(), n, (const uint8_t *)f.all.data(), f.text_bytes, f.cig_off.data(), f.cig_end.data(), f.t_st.data(),
-                                f.t_en.data(), f.q_st.data(), f.q_en.data(), f.strand.data(), cig_status.data(), red.data(), nullptr),
+    eng.check(std::apply(rb_host_scan_text, std::tuple_cat(text_columns(eng, f), std::make_tuple(cig_status.data(), red.data(), (rb_norm_row *)nullptr))),
               "rb_host_scan_text");
     if (!f.check_loaded(cig_status, red)) return false;
     for (size_t i = 0; i < n; i++)

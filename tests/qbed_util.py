@@ -1,6 +1,7 @@
 """Inputs and bindings for the liftover --qbed tests: the record sets rb_dev_swap is run in place on (tests/test_gpu_swap_inplace.py), the
-batch and windows of the RB_LIFT_QBED wrapper test (tests/test_gpu_qbed_text.py), ctypes bindings of the two text wrappers, and the oracle's
-answer for that batch.  tests/test_qbed_inputs.py holds these inputs to what the GPU tests say they contain, with the oracle alone."""
+batch and windows of the RB_LIFT_QBED wrapper test (tests/test_gpu_qbed_text.py), ctypes bindings of the text wrappers -- every rb_host_*_text
+entry point, with sentinel-filled outputs (tests/test_gpu_text_entry_points.py) -- and the oracle's answer for that batch.
+tests/test_qbed_inputs.py holds these inputs to what the GPU tests say they contain, with the oracle alone."""
 import ctypes as C
 import zlib
 
@@ -241,35 +242,128 @@ def _take(L, ptr, n, dt):
     return r
 
 
-def _text_call(eng, fn, d, policy, head, tail=()):
+SENTINEL = 0xEE             # every caller-owned output is filled with this byte before a call, so "untouched" shows
+UNTOUCHED = 0xEEEEEEEEEEEEEEEE  # ... and so is every out-pointer and *n_rows
+INT_UNTOUCHED = -0x11111112  # (0xEEEEEEEE as an int)
+
+
+def _filled(k, dt):
+    return np.frombuffer(bytes([SENTINEL]) * (k * np.dtype(dt).itemsize), dt).copy()
+
+
+def untouched(a):
+    return bool((np.ascontiguousarray(a).view(np.uint8) == SENTINEL).all())
+
+
+def _text_call(eng, fn, d, policy, head, tail=(), form="text", null=()):
+    """One call of a text entry point: the shared leading columns of `d`, the route's own `head` (contig + windows, max_size, or both), the
+    shared outputs, the route's own `tail`.  form: "text" (row_text_off, row_text), "stats" (one reduce row per row in their place), "scan"
+    (rb_host_scan_text: no policy, no rows).  null: names among rows / row_text_off / row_text / stats passed as NULL.
+    -> dict(rc, error, cig_status, red, norm, counters, n_rows, ptr = {name: "null" | "untouched" | "set"}, rows, off, text, stats); rows, off
+    (row_text_off: n_rows + 1 words, two of an empty result), text [bytes per row] and stats hold what the pointers gave (empty where they gave nothing)"""
     from rustybam_amd import capi
     n = len(d["strand"])
-    st = np.full(max(n, 1), 0xEE, np.uint8)
-    red, norm, cnt = np.zeros(n, capi.REDUCE_DT), np.zeros(n, capi.NORM_DT), np.zeros(1, capi.COUNTERS_DT)
-    rows, toff, text, nr = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+    st, red, norm, cnt = _filled(max(n, 1), np.uint8), _filled(n, capi.REDUCE_DT), _filled(n, capi.NORM_DT), _filled(1, capi.COUNTERS_DT)
+    out = {k: C.c_void_p(UNTOUCHED) for k in ("rows", "row_text_off", "row_text", "stats")}
+    ref = lambda k: C.c_void_p(0) if k in null else C.byref(out[k])  # noqa: E731
+    nr = C.c_uint64(UNTOUCHED)
+    last = {"text": ("row_text_off", "row_text"), "stats": ("stats",), "scan": ()}[form]
+    outs = () if form == "scan" else (ref("rows"), C.byref(nr), *map(ref, last), _p(cnt))
     rc = fn(eng.ctx, C.c_uint64(n), _p(d["text"]), C.c_uint64(d["text_bytes"]), _p(d["cig_off"]), _p(d["cig_end"]), _p(d["t_st"]), _p(d["t_en"]),
-            _p(d["q_st"]), _p(d["q_en"]), _p(d["strand"]), *head, C.c_int(policy), _p(st), _p(red), _p(norm), C.byref(rows), C.byref(nr),
-            C.byref(toff), C.byref(text), _p(cnt), *tail)
-    if rc != 0:
-        return dict(rc=int(rc), error=eng.L.rb_ctx_last_error(eng.ctx).decode())
-    k = int(nr.value)
-    off = _take(eng.L, toff, k + 1, np.uint64)
-    txt = _take(eng.L, text, int(off[k]) if k else 0, np.uint8).tobytes()
-    return dict(rc=0, cig_status=st[:n], red=red, norm=norm, rows=_take(eng.L, rows, k, capi.HIT_DT),
-                text=[txt[int(off[i]):int(off[i + 1])] for i in range(k)])
+            _p(d["q_st"]), _p(d["q_en"]), _p(d["strand"]), *head, *(() if form == "scan" else (C.c_int(policy),)), _p(st), _p(red), _p(norm),
+            *outs, *tail)
+    ptr = {k: "null" if p.value is None else "untouched" if p.value == UNTOUCHED else "set" for k, p in out.items()}
+    r = dict(rc=int(rc), error=eng.L.rb_ctx_last_error(eng.ctx).decode() if rc != 0 else "", cig_status=st[:n], red=red, norm=norm,
+             counters=cnt, n_rows=int(nr.value), ptr=ptr)
+    k = r["n_rows"] if rc == 0 and r["n_rows"] != UNTOUCHED else 0
+    take = lambda key, m, dt: _take(eng.L, out[key], m, dt) if ptr[key] == "set" else np.zeros(0, dt)  # noqa: E731
+    r["off"] = off = take("row_text_off", max(k + 1, 2), np.uint64)  # (an empty result still has two words)
+    txt = take("row_text", int(off[k]) if k and len(off) > k else 0, np.uint8).tobytes()
+    r["rows"], r["stats"] = take("rows", k, capi.HIT_DT), take("stats", k, capi.REDUCE_DT)
+    r["text"] = [txt[int(off[i]):int(off[i + 1])] for i in range(k)] if len(off) > k else []
+    return r
+
+
+def _windows(d):
+    return (_p(d["contig"]), C.c_uint64(len(d["w_st"])), _p(d["w_contig"]), _p(d["w_st"]), _p(d["w_en"]))
+
+
+# the text entry points: name -> (form, what stands between the columns and the policy, what stands behind the counters)
+TEXT_ENTRY_POINTS = {
+    "rb_host_liftover_text": ("text", "windows", None),
+    "rb_host_liftover_largest_text": ("text", "windows", "largest"),
+    "rb_host_liftover_stats_text": ("stats", "windows", None),
+    "rb_host_break_text": ("text", "max_size", None),
+    "rb_host_break_stats_text": ("stats", "max_size", None),
+    "rb_host_break_pairs_text": ("text", "max_size", "pairs"),
+    "rb_host_break_pairs_stats_text": ("stats", "max_size", "pairs"),
+    "rb_host_break_liftover_text": ("text", "both", "pieces"),
+    "rb_host_break_liftover_stats_text": ("stats", "both", "pieces"),
+    "rb_host_scan_text": ("scan", None, None),
+}
+
+
+def text_entry(eng, name, d, policy=0, max_size=10, largest=None, pairs=None, null=()):
+    """Entry point `name` on the batch `d` (text, text_bytes, cig_off, cig_end, the columns, contig, w_contig, w_st, w_en).
+    largest = (win_key, n_keys, inside_key); pairs = dict(rec_key, rec_q_len, n_keys, mode, paired_len, min_aln, min_query).
+    -> what _text_call gives, and declined / key_flip / row_piece (None: NULL, "untouched", or the pieces) where the entry point has them"""
+    form, mid, end = TEXT_ENTRY_POINTS[name]
+    head = {"windows": lambda: _windows(d), "max_size": lambda: (C.c_uint32(max_size),), "both": lambda: (*_windows(d), C.c_uint32(max_size)),
+            None: lambda: ()}[mid]()
+    declined, piece, key_flip, keep = C.c_int(INT_UNTOUCHED), C.c_void_p(UNTOUCHED), None, []
+    tail = ()
+    if end == "largest":
+        keep = [np.ascontiguousarray(largest[0], np.uint32)]
+        tail = (_p(keep[0]), C.c_uint64(largest[1]), C.c_uint32(largest[2]), C.byref(declined))
+    elif end == "pairs":
+        keep = [np.ascontiguousarray(pairs["rec_key"], np.uint32), np.ascontiguousarray(pairs["rec_q_len"], np.uint64)]
+        key_flip = _filled(pairs["n_keys"] + 1, np.uint8)
+        tail = (_p(keep[0]), _p(keep[1]), C.c_uint64(pairs["n_keys"]), C.c_uint32(pairs["mode"]), C.c_uint64(pairs.get("paired_len", 0)),
+                C.c_uint64(pairs.get("min_aln", 0)), C.c_uint64(pairs.get("min_query", 0)), _p(key_flip), C.byref(declined))
+    elif end == "pieces":
+        tail = (C.byref(piece), C.byref(declined))
+    r = _text_call(eng, getattr(eng.L, name), d, policy, head, tail, form, null)
+    if end:
+        r["declined"] = declined.value
+    if end == "pairs":
+        r["key_flip"] = key_flip[:pairs["n_keys"]]
+    if end == "pieces":
+        r["row_piece"] = None if piece.value is None else "untouched" if piece.value == UNTOUCHED else _take(eng.L, piece, len(r["rows"]), np.uint32)
+    return r
+
+
+def text_batch(cigars, t_st, q_st, strands, contig, windows):
+    """records with the CIGAR strings `cigars` (they need not parse) as they lie in a file, other bytes between the values; the spans are
+    those of whatever ops the strings hold.  windows: [(contig, st, en)] -> the dict text_entry takes, with ops / op_off for the oracle"""
+    from rbtest_util import pack
+    ops = [pack(c) for c in cigars]
+    text, cig_off, cig_end = b"", [], []
+    for i, c in enumerate(cigars):
+        text += b"x" * (i % 7 + 1)
+        cig_off.append(len(text))
+        text += c.encode()
+        cig_end.append(len(text))
+    text += b"\n" + b"\0" * 32
+    span = [sums(o) if len(o) else (0, 0) for o in ops]
+    u64 = lambda x: np.array(x, np.uint64)  # noqa: E731
+    op_off = np.zeros(len(ops) + 1, np.uint64)
+    op_off[1:] = np.cumsum([len(o) for o in ops])
+    return dict(text=np.frombuffer(text, np.uint8).copy(), text_bytes=len(text) - 32, cig_off=u64(cig_off), cig_end=u64(cig_end),
+                ops=np.concatenate(ops).astype(np.uint32) if ops else np.zeros(0, np.uint32), op_off=op_off, t_st=u64(t_st),
+                t_en=u64([a + s[0] for a, s in zip(t_st, span)]), q_st=u64(q_st), q_en=u64([a + s[1] for a, s in zip(q_st, span)]),
+                strand=np.array([ord(s) for s in strands], np.uint8), contig=np.array(contig, np.uint32),
+                w_contig=np.array([w[0] for w in windows], np.uint32), w_st=u64([w[1] for w in windows]), w_en=u64([w[2] for w in windows]))
 
 
 def host_liftover_text(eng, d, policy):
     """rb_host_liftover_text on the batch of qbed_batch() -> dict(rc, cig_status, red, norm, rows, text [bytes per row]) or dict(rc, error)"""
-    head = (_p(d["contig"]), C.c_uint64(len(d["w_st"])), _p(d["w_contig"]), _p(d["w_st"]), _p(d["w_en"]))
-    return _text_call(eng, eng.L.rb_host_liftover_text, d, policy, head)
+    return _text_call(eng, eng.L.rb_host_liftover_text, d, policy, _windows(d))
 
 
 def host_liftover_largest_text(eng, d, policy, win_key, n_keys, inside_key):
-    head = (_p(d["contig"]), C.c_uint64(len(d["w_st"])), _p(d["w_contig"]), _p(d["w_st"]), _p(d["w_en"]))
     declined = C.c_int(-1)
     wk = np.ascontiguousarray(win_key, np.uint32)
-    r = _text_call(eng, eng.L.rb_host_liftover_largest_text, d, policy, head, (_p(wk), C.c_uint64(n_keys), C.c_uint32(inside_key), C.byref(declined)))
+    r = _text_call(eng, eng.L.rb_host_liftover_largest_text, d, policy, _windows(d), (_p(wk), C.c_uint64(n_keys), C.c_uint32(inside_key), C.byref(declined)))
     r["declined"] = declined.value
     return r
 
