@@ -299,6 +299,8 @@ int rb_ctx_scan_route(rb_ctx *ctx, uint64_t out[2]);
  *     records keep the per-record kernel, and a tile the tile kernel does not take (an irregular or stripped record, an integrity failure,
  *     more than 64 hits, ...) is handed to it record by record.  Same rows, same clips either way; counters.phase[3..4] tell how it went.
  *     RB_TILE=0 in the environment switches the tiles off, RB_SHORT_MAX=<ops> moves the line (both read here, per plan).
+ *     rb_dev_liftover runs the tile kernel on the context's side stream, beside the per-record kernel, when the batch has records of both
+ *     kinds; RB_TILE_BESIDE=0 (read per call) keeps the call on one stream.
  * `windows` may be NULL (break-paf / stats only).  */
 int rb_plan_create(rb_ctx *ctx, uint64_t n_rec, const uint64_t *op_off_host, const uint32_t *contig_host,
                    uint64_t n_win, const uint32_t *w_contig_host, const uint64_t *w_st_host, const uint64_t *w_en_host,

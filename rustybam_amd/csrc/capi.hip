@@ -65,6 +65,9 @@ struct rb_ctx {
     bool timing = false;
     std::vector<hipEvent_t> ev_a, ev_b;
     uint64_t timed_calls = 0;
+    // liftover: the stream the tile kernel runs on beside the per-record kernel (lift_common), and the two events that tie it to `stream`
+    hipStream_t side = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // trim-paf: slabs of device memory for pairs whose overlap region does not fit LDS (allocated at the first rb_dev_overlap_split)
     void *trim_scratch = nullptr;
     uint32_t trim_scratch_blocks = 0;
@@ -152,11 +155,28 @@ extern "C" int rb_ctx_create(int device, void *hip_stream, rb_ctx **out) {
         }
         c->own_stream = true;
     }
+    // the side stream at the lowest priority: its waves go where a wave of the main stream's kernel does not fit, and take no place
+    // from one (profiles/tile_beside_summary.md has normal priority beside it)
+    int prio_least = 0, prio_greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess ||
+        hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, prio_least) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        rb_ctx_destroy(c);
+        return RB_E_HIP;
+    }
     *out = c;
     return RB_OK;
 }
 extern "C" void rb_ctx_destroy(rb_ctx *ctx) {
     if (!ctx) return;
+    if (ctx->side) {
+        (void)hipStreamSynchronize(ctx->side); // (what it still runs writes the caller's buffers)
+        hipStreamDestroy(ctx->side);
+    }
+    if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
+    if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
     for (auto e : ctx->ev_a) hipEventDestroy(e);
     for (auto e : ctx->ev_b) hipEventDestroy(e);
     for (int k = 0; k < 2; k++) {
@@ -1081,16 +1101,47 @@ static int lift_common(rb_ctx *ctx, const rb_plan *plan, const rb_batch_view *b,
     } else {
         HIPCHK(ctx, rb_launch_count_and_scan(&p, block_sums, true, ctx->stream));
     }
+    // The clip kernels.  Liftover with long AND short records runs the tile kernel BESIDE the per-record kernel, on the context's side
+    // stream: four waves of rb_k_liftover_stream per SIMD take 416 of the 512 vector registers and four of its workgroups 116,800 of a
+    // CU's 163,840 bytes of LDS, which leaves room for exactly one workgroup of rb_k_liftover_tile (96 registers, 29,696 bytes) that
+    // the per-record kernel cannot use.  Order: fork event | side stream: wait, tiles, list kernel over what the
+    // tiles hand back, join event | main stream: per-record kernel, wait for the join, the rest.  The side stream's launches are
+    // issued first, so that both queues hold work when the large grid arrives.  The two kernels share no output line (a tile's clips
+    // lie in the slot lines of its own records, slot_stride_of) and append to the lists and arena cursors with atomics only, so rows
+    // and clip contents are the single-stream call's; the order of list entries, hence out_off of arena clips, may differ.  The
+    // timing bracket covers max(per-record kernel, tiles + list).  Everything else (no tiles, no long records, break-paf -- its
+    // per-record build runs five waves of 96 registers per SIMD and leaves no room --, diagnostics builds, RB_TILE=0, and
+    // RB_TILE_BESIDE=0 in the environment, read per call: tests, A/B runs, callers who capture the call in a graph and want no
+    // branch in it) is one stream, launch for launch as before.
+    const char *tb = getenv("RB_TILE_BESIDE");
+    const bool beside = use_tiles && !is_break && stream_end != 0 && !(tb && atoi(tb) == 0);
+    if (use_tiles && !is_break) HIPCHK(ctx, rb_fill_async(p.fb_count, 0, 8, ctx->stream)); // (the last call's list kernel is done: that call joined)
     HIPCHK(ctx, rb_launch_make_jobs(&p, ctx->stream));
     const size_t slot = (size_t)(ctx->timed_calls % RB_TIMING_RING);
+    if (beside) HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
     if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev_a[slot], ctx->stream));
     p.wave0 = 0;
     p.wave_end = stream_end;
-    HIPCHK(ctx, rb_launch_liftover_stream(&p, ctx->stream));
-    if (use_tiles) {
-        HIPCHK(ctx, rb_fill_async(p.fb_count, 0, 8, ctx->stream));
-        HIPCHK(ctx, rb_launch_liftover_tiles(&p, ctx->stream));
-        HIPCHK(ctx, rb_launch_liftover_stream_list(&p, ctx->stream));
+    if (beside) {
+        // from here to the join the side stream may write the caller's buffers: no return before it is idle or the main stream waits for it
+        hipError_t e = hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0);
+        const char *what = "hipStreamWaitEvent(fork)";
+        if (e == hipSuccess) e = rb_launch_liftover_tiles(&p, ctx->side), what = "rb_launch_liftover_tiles";
+        if (e == hipSuccess) e = rb_launch_liftover_stream_list(&p, ctx->side), what = "rb_launch_liftover_stream_list";
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev_join, ctx->side), what = "hipEventRecord(join)";
+        if (e == hipSuccess) e = rb_launch_liftover_stream(&p, ctx->stream), what = "rb_launch_liftover_stream";
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), what = "hipStreamWaitEvent(join)";
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->side);
+            return fail(ctx, RB_E_HIP, "%s: %s", what, hipGetErrorString(e));
+        }
+    } else {
+        HIPCHK(ctx, rb_launch_liftover_stream(&p, ctx->stream));
+        if (use_tiles) {
+            if (is_break) HIPCHK(ctx, rb_fill_async(p.fb_count, 0, 8, ctx->stream));
+            HIPCHK(ctx, rb_launch_liftover_tiles(&p, ctx->stream));
+            HIPCHK(ctx, rb_launch_liftover_stream_list(&p, ctx->stream));
+        }
     }
     if (p.fused) { // the full record scan for the records the clip kernel handed back (usually none)
         sp.list = p.pend_list;
