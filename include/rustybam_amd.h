@@ -485,6 +485,47 @@ int rb_host_pairs_rows(const rb_hit_row *rows, uint64_t n_rows, const uint32_t *
                        uint64_t n_rec, uint64_t n_keys, uint32_t mode, uint64_t paired_len, uint64_t min_aln, uint64_t min_query,
                        rb_hit_row *rows_out, uint64_t rows_cap, uint8_t *key_flip, rb_pairs_info *info);
 
+/* ---- orient [--scaffold] / filter over the RECORDS of a batch (`rb orient`, `rb filter` on a file's records) ---- *
+ * <- Paf::orient (paf.rs:114-157) with the order column that --scaffold sorts by, and main.rs:242-244 (the three filters), over the records of
+ *    a batch: the sums, the flags and the placement of rb_dev_pairs_rows, a record where that call has a hit row.  rec_key as there: the host's
+ *    dense u32 key of each record's (target name, query name) pair.
+ *   takes part   a record with rec_key[r] < n_keys.  A record with another key counts nowhere, is not kept, and DECLINES (_KEY).
+ *   orient       (RB_PAIRS_ORIENT) per key, over the records that take part: orient = i64 sum of +(q_en - q_st) where strand[r] is not '-' and
+ *                -(q_en - q_st) where it is; tspan = sum of w = t_en - t_st; order = sum of (w * (t_st + t_en)) / 2 -- product and sums mod
+ *                2^64, as a release build of the reference.  key_flip[k] = orient < 0 (strict); key_order[k] = order / tspan where tspan != 0,
+ *                else 0 (a record's `order`, paf.rs:143).  A key that has records and tspan == 0 is the reference's divide-by-zero panic: _ZERO_SPAN.
+ *                q_st_out / q_en_out [n_rec]: q_len - q_en, q_len - q_st (mod 2^64) for the records of flipped keys, the input's for all others
+ *                (a flipped record with q_len < q_en: _WRAP, the outputs are still the values mod 2^64).  Without the bit key_flip and
+ *                key_order are all zero.
+ *   filter       (RB_PAIRS_FILTER) a record passes if rec_q_len[r] > min_query and t_en - t_st > min_aln; fspan[key] = sum of t_en - t_st over
+ *                the records that PASS; a record is kept if it passes and paired_len < fspan[key].  All three strict.  Without the bit every
+ *                record that takes part is kept.  Orient's sums see every record that takes part, whatever the filter says.
+ *   kept         [kept_cap] the indices of the kept records, ascending.
+ *   info         as rb_dev_pairs_rows: n_kept and n_flipped_rows (kept records of flipped keys) EXACT whatever kept_cap; overflow != 0: kept_cap
+ *                was too small (kept_cap == 0 with kept == NULL is allowed); declined = the OR of RB_PAIRS_DECL_KEY / _WRAP / _ZERO_SPAN.
+ *   CAPACITY (tests/test_gpu_pairs_records.py): nothing is written at or behind kept[kept_cap], key_flip[n_keys], key_order[n_keys],
+ *       q_*_out[n_rec] or the end of the scratch (rb_pairs_records_scratch_bytes(n_keys, n_rec) bytes, 256-byte aligned; the sums in it are
+ *       zeroed by the call itself, every time); a second call with exactly n_kept fits.
+ *   q_st_out / q_en_out may both be NULL, key_order may be NULL.  n_rec == 0 and n_keys == 0 are valid.  n_rec >= 2^32, an unknown mode bit or a
+ *   misaligned pointer (u64 columns and info 8 bytes, u32 columns 4, the scratch 256): RB_E_INVALID before anything is enqueued.
+ *   Enqueues on the context's stream, does not synchronise.  Two calls on the same input write the same bytes: integer sums, and nothing is
+ *   placed or counted by an atomic.
+ * rb_pairs_records_shape: out[0] = consecutive records one wavefront sums (it carries an open run of one key through them), out[1] = records
+ *   per workgroup; no device needed.
+ * rb_host_pairs_records: the same rules in plain C++ on HOST arrays, no context and no scratch; same outputs, byte for byte. */
+size_t rb_pairs_records_scratch_bytes(uint64_t n_keys, uint64_t n_rec);
+void rb_pairs_records_shape(uint32_t out[2]);
+int rb_dev_pairs_records(rb_ctx *ctx, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
+                         const uint8_t *strand, const uint32_t *rec_key, const uint64_t *rec_q_len /* each [n_rec], device */,
+                         uint64_t n_rec, uint64_t n_keys, uint32_t mode /* RB_PAIRS_ORIENT | RB_PAIRS_FILTER */,
+                         uint64_t paired_len, uint64_t min_aln, uint64_t min_query,
+                         uint32_t *kept /* [kept_cap] OUT */, uint64_t kept_cap, uint64_t *q_st_out, uint64_t *q_en_out /* [n_rec] OUT, may both be NULL */,
+                         uint8_t *key_flip /* [n_keys] OUT */, uint64_t *key_order /* [n_keys] OUT, may be NULL */, rb_pairs_info *info, void *scratch);
+int rb_host_pairs_records(const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand,
+                          const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_rec, uint64_t n_keys, uint32_t mode, uint64_t paired_len,
+                          uint64_t min_aln, uint64_t min_query, uint32_t *kept, uint64_t kept_cap, uint64_t *q_st_out, uint64_t *q_en_out,
+                          uint8_t *key_flip, uint64_t *key_order, rb_pairs_info *info);
+
 /* ---- break-paf -------------------------------------------------------------------------------- *
  * Pieces between indels longer than max_size, record order then piece order; same row shape,
  * rb_hit_row.win = piece ordinal among the candidate windows of the record. */
@@ -698,6 +739,21 @@ int rb_host_break_pairs_stats_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *t
                                    rb_norm_row *norm_out, rb_hit_row **rows, uint64_t *n_rows, rb_reduce_row **stats, rb_counters *counters,
                                    const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_keys, uint32_t mode, uint64_t paired_len,
                                    uint64_t min_aln, uint64_t min_query, uint8_t *key_flip, int *declined);
+/* `rb orient [--scaffold] in.paf` and `rb filter --paired-len L --aln A --query Q in.paf` on the records of a file: the first eleven arguments as
+ * every text entry point, then those of rb_dev_pairs_records (rec_key / rec_q_len [n_rec]: the caller's interning of the (target name, query
+ * name) pairs, and column 2).  Flow: parse, rb_dev_scan_records (reduce_out [n_rec]: Paf::from_file's check_integrity, nmatch and aln_len),
+ * rb_dev_pairs_records with room for every record, rb_dev_format_cigars over the KEPT records only -- one item per kept record, in record order.
+ * Out: cig_status [n_rec]; reduce_out [n_rec]; *kept [*n_kept] the kept records' indices, ascending (malloc'ed, rb_host_free); q_st_out /
+ * q_en_out [n_rec] the records' query coordinates, flipped where their key is; key_flip / key_order [n_keys]; *row_text and *row_text_off
+ * [*n_kept + 1] (malloc'ed): kept record k's CIGAR is row_text[row_text_off[k] .. row_text_off[k + 1]).  The caller appends + / - to the query
+ * name and turns the strand by key_flip[rec_key[r]]; --scaffold sorts an index array by (target name, key_order[rec_key[r]], q_st_out[r]).
+ * A CIGAR that did not parse: RB_OK, cig_status says which, nothing else is produced.  *declined != 0 (RB_OK, no kept records and no text come
+ * back; the columns and the key arrays are what the rules say): rb_pairs_info.declined -- the caller replays the file on the record route. */
+int rb_host_pairs_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end,
+                       const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand,
+                       const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_keys, uint32_t mode, uint64_t paired_len, uint64_t min_aln,
+                       uint64_t min_query, uint8_t *cig_status, rb_reduce_row *reduce_out, uint32_t **kept, uint64_t *n_kept, uint64_t *q_st_out,
+                       uint64_t *q_en_out, uint8_t *key_flip, uint64_t *key_order, uint64_t **row_text_off, uint8_t **row_text, int *declined);
 /* `rb break-paf --max-size N in.paf | rb liftover --bed W -` (and the same with `| rb stats --paf` behind it) as ONE device pipeline: the
  * pieces are never printed, read back, parsed or uploaded.  Arguments as rb_host_liftover_text / rb_host_liftover_stats_text plus max_size;
  * RB_LIFT_QBED is refused (RB_E_INVALID).  Flow: parse, rb_dev_scan_records, rb_dev_break in descriptor mode, rb_dev_rows_to_batch (the

@@ -149,6 +149,36 @@ def host_pairs_rows(rows, rec_key, rec_q_len, strand, n_keys, mode, paired_len=0
     return out[:min(int(info[0]["n_kept"]), cap)], flip, info[0]
 
 
+def pairs_records_shape():
+    """(consecutive records one wavefront of rb_dev_pairs_records' sum kernel walks, records per workgroup) (rb_pairs_records_shape: no device needed)"""
+    out = (C.c_uint32 * 2)()
+    f = lib().rb_pairs_records_shape
+    f.restype = None
+    f(out)
+    return tuple(int(x) for x in out)
+
+
+def _pairs_records_cols(t_st, t_en, q_st, q_en, strand, rec_key, rec_q_len):
+    cols = [_arr(x, np.uint64) for x in (t_st, t_en, q_st, q_en)] + [_arr(strand, np.uint8), _arr(rec_key, np.uint32), _arr(rec_q_len, np.uint64)]
+    assert len({len(c) for c in cols}) == 1, "the seven columns have one length"
+    return cols
+
+
+def host_pairs_records(t_st, t_en, q_st, q_en, strand, rec_key, rec_q_len, n_keys, mode, paired_len=0, min_aln=0, min_query=0, kept_cap=None):
+    """rb_host_pairs_records: orient / filter over the records of a batch in plain C++ on host arrays (no device, no context)
+    -> dict(kept u32 [min(n_kept, kept_cap)], q_st, q_en u64 [n_rec], key_flip u8 [n_keys], key_order u64 [n_keys], info PAIRS_INFO_DT)"""
+    cols = _pairs_records_cols(t_st, t_en, q_st, q_en, strand, rec_key, rec_q_len)
+    n, n_keys = len(cols[0]), int(n_keys)
+    cap = n if kept_cap is None else int(kept_cap)
+    kept, qs, qe = np.zeros(cap, np.uint32), np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    flip, order, info = np.zeros(n_keys, np.uint8), np.zeros(n_keys, np.uint64), np.zeros(1, PAIRS_INFO_DT)
+    rc = lib().rb_host_pairs_records(*map(_p, cols), C.c_uint64(n), C.c_uint64(n_keys), C.c_uint32(mode), C.c_uint64(paired_len), C.c_uint64(min_aln),
+                                     C.c_uint64(min_query), _p(kept) if cap else None, C.c_uint64(cap), _p(qs), _p(qe), _p(flip), _p(order), _p(info))
+    if rc != 0:
+        raise RbError(f"rb_host_pairs_records failed with {rc}")
+    return dict(kept=kept[:min(int(info[0]["n_kept"]), cap)], q_st=qs, q_en=qe, key_flip=flip, key_order=order, info=info[0])
+
+
 def _p(a):
     return C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(0)
 
@@ -494,6 +524,81 @@ class Engine:
             self.sync()
             for b in bufs:
                 self.dev_free(b)
+
+    def pairs_records_scratch_bytes(self, n_keys, n_rec):
+        f = self.L.rb_pairs_records_scratch_bytes
+        f.restype = C.c_size_t
+        return int(f(C.c_uint64(n_keys), C.c_uint64(n_rec)))
+
+    def dev_pairs_records(self, t_st, t_en, q_st, q_en, strand, rec_key, rec_q_len, n_rec, n_keys, mode, paired_len, min_aln, min_query, kept, kept_cap,
+                          q_st_out, q_en_out, key_flip, key_order, info, scratch):
+        """orient / filter over the records of a resident batch (every pointer a device address; kept, q_st_out / q_en_out, key_order may be 0);
+        enqueues on the context's stream -> the return code (RB_E_INVALID = -1 for what the call refuses): the caller checks it"""
+        v = C.c_void_p
+        return int(self.L.rb_dev_pairs_records(self.ctx, v(t_st or 0), v(t_en or 0), v(q_st or 0), v(q_en or 0), v(strand or 0), v(rec_key or 0),
+                                               v(rec_q_len or 0), C.c_uint64(n_rec), C.c_uint64(n_keys), C.c_uint32(mode), C.c_uint64(paired_len),
+                                               C.c_uint64(min_aln), C.c_uint64(min_query), v(kept or 0), C.c_uint64(kept_cap), v(q_st_out or 0),
+                                               v(q_en_out or 0), v(key_flip or 0), v(key_order or 0), v(info or 0), v(scratch or 0)))
+
+    def pairs_records(self, t_st, t_en, q_st, q_en, strand, rec_key, rec_q_len, n_keys, mode, paired_len=0, min_aln=0, min_query=0):
+        """rb_dev_pairs_records on host arrays: uploads, runs with room for every record, downloads
+        -> dict(kept u32 [n_kept], q_st, q_en u64 [n_rec], key_flip u8 [n_keys], key_order u64 [n_keys], info PAIRS_INFO_DT)"""
+        cols = _pairs_records_cols(t_st, t_en, q_st, q_en, strand, rec_key, rec_q_len)
+        n, n_keys = len(cols[0]), int(n_keys)
+        bufs = []
+
+        def dev(n_bytes, src=None):
+            bufs.append(self.dev_alloc(max(n_bytes, 256)))
+            if src is not None and src.nbytes:
+                self._chk(self.L.rb_dev_upload(self.ctx, C.c_void_p(bufs[-1]), _p(src), C.c_size_t(src.nbytes)), "rb_dev_upload")
+            return bufs[-1]
+
+        def down(ptr, k, dt):
+            a = np.zeros(k, dt)
+            if a.nbytes:
+                self._chk(self.L.rb_dev_download(self.ctx, _p(a), C.c_void_p(ptr), C.c_size_t(a.nbytes)), "rb_dev_download")
+            return a
+        try:
+            d_cols = [dev(c.nbytes, c) for c in cols]
+            d_kept, d_qs, d_qe, d_flip, d_ord, d_info = dev(4 * n), dev(8 * n), dev(8 * n), dev(n_keys), dev(8 * n_keys), dev(64)
+            d_scr = dev(self.pairs_records_scratch_bytes(n_keys, n))
+            self._chk(self.dev_pairs_records(*d_cols, n, n_keys, mode, paired_len, min_aln, min_query, d_kept, n, d_qs, d_qe, d_flip, d_ord, d_info, d_scr),
+                      "rb_dev_pairs_records")
+            info = down(d_info, 1, PAIRS_INFO_DT)[0]
+            return dict(kept=down(d_kept, int(info["n_kept"]), np.uint32), q_st=down(d_qs, n, np.uint64), q_en=down(d_qe, n, np.uint64),
+                        key_flip=down(d_flip, n_keys, np.uint8), key_order=down(d_ord, n_keys, np.uint64), info=info)
+        finally:
+            self.sync()
+            for b in bufs:
+                self.dev_free(b)
+
+    def pairs_text(self, text, cig_off, cig_end, t_st, t_en, q_st, q_en, strand, rec_key, rec_q_len, n_keys, mode, paired_len=0, min_aln=0, min_query=0):
+        """rb_host_pairs_text: `rb orient` / `rb filter` on the records of a file whose text is `text` (bytes; record r's cg:Z: value is
+        text[cig_off[r]:cig_end[r]]) -> dict(cig_status u8 [n_rec], reduce REDUCE_DT [n_rec], kept u32 [n_kept], q_st, q_en u64 [n_rec],
+        key_flip u8, key_order u64 [n_keys], cigars: list of bytes per kept record, declined int)"""
+        cols = _pairs_records_cols(t_st, t_en, q_st, q_en, strand, rec_key, rec_q_len)
+        coff, cend = _arr(cig_off, np.uint64), _arr(cig_end, np.uint64)
+        n, n_keys = len(cols[0]), int(n_keys)
+        buf = np.frombuffer(bytes(text) + b"\0" * 32, dtype=np.uint8).copy()
+        status, red = np.zeros(max(n, 1), np.uint8), np.zeros(n, REDUCE_DT)
+        qs, qe, flip, order = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n_keys, np.uint8), np.zeros(n_keys, np.uint64)
+        kept, toff, out = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nk, declined = C.c_uint64(), C.c_int()
+        t_st_, t_en_, q_st_, q_en_, strand_, key_, qlen_ = cols
+        self._chk(self.L.rb_host_pairs_text(self.ctx, C.c_uint64(n), _p(buf), C.c_uint64(len(text)), _p(coff), _p(cend), _p(t_st_), _p(t_en_), _p(q_st_),
+                                            _p(q_en_), _p(strand_), _p(key_), _p(qlen_), C.c_uint64(n_keys), C.c_uint32(mode), C.c_uint64(paired_len),
+                                            C.c_uint64(min_aln), C.c_uint64(min_query), _p(status), _p(red), C.byref(kept), C.byref(nk), _p(qs), _p(qe),
+                                            _p(flip), _p(order), C.byref(toff), C.byref(out), C.byref(declined)), "rb_host_pairs_text")
+
+        def take(ptr, k, dt):
+            r = np.frombuffer((C.c_char * (k * np.dtype(dt).itemsize)).from_address(ptr.value), dtype=dt).copy() if k and ptr.value else np.zeros(0, dt)
+            self.L.rb_host_free(ptr)
+            return r
+        k = int(nk.value)
+        offs = take(toff, k + 1, np.uint64)
+        body = take(out, int(offs[k]) if len(offs) > k else 0, np.uint8).tobytes()
+        return dict(cig_status=status[:n], reduce=red, kept=take(kept, k, np.uint32), q_st=qs, q_en=qe, key_flip=flip, key_order=order,
+                    cigars=[body[int(offs[i]):int(offs[i + 1])] for i in range(k)], declined=int(declined.value))
 
     def largest_scratch_bytes(self, n_keys):
         f = self.L.rb_largest_scratch_bytes

@@ -2149,6 +2149,107 @@ extern "C" int rb_host_scan_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *tex
     return host_lift_text(ctx, text_route::scan(), c, {}, o);
 }
 
+// ---- `rb orient [--scaffold]` / `rb filter` on the records of a file (rb_host_pairs_text) -----------------------------------------------
+// text_front_of (parse, the batch), rb_dev_scan_records for Paf::from_file's check_integrity and nmatch / aln_len, rb_dev_pairs_records with
+// room for every record, then rb_dev_format_cigars over the kept records only -- an item per kept record: its whole CIGAR, as parsed.  There
+// are no hit rows, no norm rows, no policy and no counters here, so the pack's row outputs point at its own storage.
+extern "C" int rb_host_pairs_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end,
+                                  const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand,
+                                  const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_keys, uint32_t mode, uint64_t paired_len, uint64_t min_aln,
+                                  uint64_t min_query, uint8_t *cig_status, rb_reduce_row *reduce_out, uint32_t **kept, uint64_t *n_kept, uint64_t *q_st_out,
+                                  uint64_t *q_en_out, uint8_t *key_flip, uint64_t *key_order, uint64_t **row_text_off, uint8_t **row_text, int *declined) {
+    const text_cols c{n_rec, text, text_bytes, cig_off, cig_end, t_st, t_en, q_st, q_en, strand}; // (no contig: every record on contig 0)
+    text_outs o{cig_status, reduce_out, nullptr, nullptr, nullptr, row_text_off, row_text, nullptr, nullptr};
+    o.rows = &o.own_rows, o.n_rows = &o.own_n;
+    if (!text_args_ok(ctx, c, o) || !kept || !n_kept || !row_text_off || !row_text || !declined ||
+        (n_rec && (!rec_key || !rec_q_len || !strand || !t_st || !t_en || !q_st || !q_en || !reduce_out || !q_st_out || !q_en_out)) ||
+        (n_keys && (!key_flip || !key_order)))
+        return RB_E_INVALID;
+    if (mode & ~(uint32_t)(RB_PAIRS_ORIENT | RB_PAIRS_FILTER)) return fail(ctx, RB_E_INVALID, "mode %u: RB_PAIRS_ORIENT | RB_PAIRS_FILTER", mode);
+    *kept = nullptr, *n_kept = 0, *declined = 0;
+    if (n_keys) memset(key_flip, 0, (size_t)n_keys), memset(key_order, 0, (size_t)n_keys * 8);
+    DevBatch b(ctx);
+    text_front f;
+    int rc = text_front_of(ctx, c, o, false, false, b, f);
+    if (rc || f.done) return rc;
+    double &tl = f.tl;
+    if ((rc = rb_dev_scan_records(ctx, &b.v, f.d_red, nullptr))) return rc;
+    if ((rc = rb_dev_download(ctx, reduce_out, f.d_red, n_rec * sizeof(rb_reduce_row)))) return rc;
+    rb_lap("scan_records + rows D2H", tl);
+    const uint32_t *d_key = nullptr;
+    const uint64_t *d_qlen = nullptr;
+    uint32_t *d_kept = nullptr;
+    uint64_t *d_qs = nullptr, *d_qe = nullptr, *d_order = nullptr;
+    uint8_t *d_flip = nullptr, *d_pscr = nullptr;
+    rb_pairs_info *d_info = nullptr, info;
+    rc = b.up(rec_key, (size_t)n_rec, &d_key);
+    if (!rc) rc = b.up(rec_q_len, (size_t)n_rec, &d_qlen);
+    if (!rc) rc = b.alloc((size_t)n_rec + 1, &d_kept);
+    if (!rc) rc = b.alloc((size_t)n_rec + 1, &d_qs);
+    if (!rc) rc = b.alloc((size_t)n_rec + 1, &d_qe);
+    if (!rc) rc = b.alloc((size_t)n_keys + 1, &d_flip);
+    if (!rc) rc = b.alloc((size_t)n_keys + 1, &d_order);
+    if (!rc) rc = b.alloc(1, &d_info);
+    if (!rc) rc = b.alloc(rb_pairs_records_scratch_bytes(n_keys, n_rec), &d_pscr);
+    if (!rc) rc = rb_dev_pairs_records(ctx, b.v.t_st, b.v.t_en, b.v.q_st, b.v.q_en, b.v.strand, d_key, d_qlen, n_rec, n_keys, mode, paired_len, min_aln, min_query,
+                                       d_kept, n_rec, d_qs, d_qe, d_flip, d_order, d_info, d_pscr);
+    if (!rc) rc = rb_dev_download(ctx, &info, d_info, sizeof info);
+    if (!rc && n_keys) rc = rb_dev_download(ctx, key_flip, d_flip, (size_t)n_keys);
+    if (!rc && n_keys) rc = rb_dev_download(ctx, key_order, d_order, (size_t)n_keys * 8);
+    if (!rc) rc = rb_dev_download(ctx, q_st_out, d_qs, (size_t)n_rec * 8);
+    if (!rc) rc = rb_dev_download(ctx, q_en_out, d_qe, (size_t)n_rec * 8);
+    if (rc) return rc;
+    if (info.declined || info.overflow) { // (kept_cap = every record: no overflow) the record route replays the file
+        *declined = info.declined ? (int)info.declined : -1;
+        return RB_OK;
+    }
+    const uint64_t nk = info.n_kept;
+    *kept = (uint32_t *)malloc((size_t)(nk + 1) * 4);
+    *row_text_off = (uint64_t *)malloc((size_t)(nk + 2) * 8);
+    if (!*kept || !*row_text_off) rc = fail(ctx, RB_E_NOMEM, "malloc(kept)");
+    if (!rc && nk) rc = rb_dev_download(ctx, *kept, d_kept, (size_t)nk * 4);
+    rb_lap("pairs records + columns D2H", tl);
+    // ---- the kept records' CIGARs as format items, text out ----
+    uint64_t *d_first = nullptr, *d_toff = nullptr;
+    uint32_t *d_cnt = nullptr;
+    uint8_t *d_rtext = nullptr;
+    void *d_scr2 = nullptr;
+    if (!rc) {
+        std::vector<uint64_t> first((size_t)nk + 1, 0);
+        std::vector<uint32_t> count((size_t)nk + 1, 0);
+        for (uint64_t k = 0; k < nk; k++) {
+            const uint32_t r = (*kept)[k];
+            first[k] = f.op_off[r], count[k] = (uint32_t)(f.op_off[r + 1] - f.op_off[r]);
+        }
+        rc = b.alloc((size_t)nk + 1, &d_first);
+        if (!rc) rc = b.alloc((size_t)nk + 1, &d_cnt);
+        if (!rc) rc = b.alloc((size_t)nk + 2, &d_toff);
+        if (!rc) rc = b.alloc(rb_text_scratch_bytes(nk), (uint8_t **)&d_scr2);
+        if (!rc && nk) rc = rb_dev_upload(ctx, d_first, first.data(), (size_t)nk * 8);
+        if (!rc && nk) rc = rb_dev_upload(ctx, d_cnt, count.data(), (size_t)nk * 4);
+        if (!rc) rc = rb_ctx_sync(ctx);
+    }
+    if (!rc) rc = format_cigars_impl(ctx, b.v.ops, nullptr, nk, d_first, d_cnt, nullptr, nullptr, d_toff, nullptr, 0, d_scr2, false, true);
+    if (!rc) rc = rb_dev_download(ctx, *row_text_off, d_toff, ((size_t)nk + 1) * 8);
+    const uint64_t bytes = rc ? 0 : (*row_text_off)[nk];
+    if (!rc) rc = b.alloc((size_t)bytes + 16, &d_rtext);
+    if (!rc) rc = format_cigars_impl(ctx, b.v.ops, nullptr, nk, d_first, d_cnt, nullptr, nullptr, d_toff, d_rtext, bytes, d_scr2, true, true);
+    if (!rc) {
+        *row_text = (uint8_t *)malloc((size_t)bytes + 16);
+        if (!*row_text) rc = fail(ctx, RB_E_NOMEM, "malloc(%llu text bytes)", (unsigned long long)bytes);
+        else rb_advise_huge(*row_text, (size_t)bytes);
+    }
+    if (!rc && bytes) rc = rb_dev_download(ctx, *row_text, d_rtext, (size_t)bytes);
+    rb_lap("format cigars + text D2H", tl);
+    if (rc) {
+        free(*kept), free(*row_text_off), free(*row_text);
+        *kept = nullptr, *row_text_off = nullptr, *row_text = nullptr;
+    } else {
+        *n_kept = nk;
+    }
+    return rc;
+}
+
 // ---- `rb break-paf --max-size N in.paf | rb liftover --bed W -` as one device pipeline (rb_host_break_liftover_text / _stats_text) ------
 // parse, scan, break in descriptor mode, rb_dev_rows_to_batch (the pieces as a batch: the second command's Paf::from_file), scan of the
 // pieces (its check_integrity and aligned_pairs' remove_trailing_indels), a plan over the pieces, liftover in descriptor mode on the piece
@@ -2557,6 +2658,107 @@ extern "C" int rb_host_pairs_rows(const rb_hit_row *rows, uint64_t n_rows, const
         else info->overflow = 1;
         info->n_kept++;
         if (key_flip[key]) info->n_flipped_rows++;
+    }
+    return RB_OK;
+}
+
+// ---- orient / filter over the records of a batch (k_pairs.hip) ------------------------------------------
+// scratch of rb_dev_pairs_records: [orient][tspan][fspan][order] n_keys u64 each, [1 per kept record (n_rec + 1) u64][block sums of the scan]
+extern "C" size_t rb_pairs_records_scratch_bytes(uint64_t n_keys, uint64_t n_rec) {
+    return 4 * pairs_sum_bytes(n_keys) + pairs_cnt_bytes(n_rec) + (rb_scan_block_sums_count(n_rec) + 4) * 8;
+}
+extern "C" void rb_pairs_records_shape(uint32_t out[2]) { out[0] = rb_pairs_wave_rows(), out[1] = rb_pairs_block_rows(); }
+// what both forms refuse; *why: what rb_ctx_last_error says (NULL: a null pointer)
+static bool pairs_records_args_ok(const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand,
+                                  const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_rec, uint64_t n_keys, uint32_t mode, const uint32_t *kept,
+                                  uint64_t kept_cap, const uint64_t *q_st_out, const uint64_t *q_en_out, const uint8_t *key_flip, const uint64_t *key_order,
+                                  const rb_pairs_info *info, const char **why) {
+    *why = nullptr;
+    if (!info || (n_rec && (!t_st || !t_en || !q_st || !q_en || !strand || !rec_key || !rec_q_len)) || (n_keys && !key_flip) || (kept_cap && !kept) ||
+        (!q_st_out != !q_en_out))
+        return false;
+    if (mode & ~(uint32_t)(RB_PAIRS_ORIENT | RB_PAIRS_FILTER)) return *why = "an unknown mode bit (RB_PAIRS_ORIENT | RB_PAIRS_FILTER)", false;
+    if (n_rec >> 32) return *why = "2^32 records and more (kept and flipped records are counted in the halves of one u64)", false;
+    const uintptr_t a8 = (uintptr_t)t_st | (uintptr_t)t_en | (uintptr_t)q_st | (uintptr_t)q_en | (uintptr_t)rec_q_len | (uintptr_t)q_st_out |
+                         (uintptr_t)q_en_out | (uintptr_t)key_order | (uintptr_t)info;
+    if ((a8 & 7u) || (((uintptr_t)rec_key | (uintptr_t)kept) & 3u)) return *why = "a misaligned pointer (u64 columns and info: 8 bytes, u32 columns: 4)", false;
+    return true;
+}
+extern "C" int rb_dev_pairs_records(rb_ctx *ctx, const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en,
+                                    const uint8_t *strand, const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_rec, uint64_t n_keys,
+                                    uint32_t mode, uint64_t paired_len, uint64_t min_aln, uint64_t min_query, uint32_t *kept, uint64_t kept_cap,
+                                    uint64_t *q_st_out, uint64_t *q_en_out, uint8_t *key_flip, uint64_t *key_order, rb_pairs_info *info, void *scratch) {
+    const char *why;
+    if (!ctx) return RB_E_INVALID;
+    if (!pairs_records_args_ok(t_st, t_en, q_st, q_en, strand, rec_key, rec_q_len, n_rec, n_keys, mode, kept, kept_cap, q_st_out, q_en_out, key_flip, key_order,
+                               info, &why))
+        return why ? fail(ctx, RB_E_INVALID, "rb_dev_pairs_records: %s", why) : RB_E_INVALID;
+    if ((n_rec || n_keys) && !scratch) return RB_E_INVALID;
+    if ((uintptr_t)scratch & 255u) return fail(ctx, RB_E_INVALID, "rb_dev_pairs_records: the scratch must be 256-byte aligned");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    rb_pairs_rec_params p;
+    memset(&p, 0, sizeof p);
+    char *sc = (char *)scratch;
+    const size_t sb = pairs_sum_bytes(n_keys);
+    p.t_st = t_st, p.t_en = t_en, p.q_st = q_st, p.q_en = q_en, p.strand = strand, p.rec_key = rec_key, p.rec_q_len = rec_q_len;
+    p.n_rec = n_rec, p.n_keys = n_keys, p.mode = mode, p.paired_len = paired_len, p.min_aln = min_aln, p.min_query = min_query;
+    p.orient = (unsigned long long *)sc, p.tspan = (unsigned long long *)(sc + sb), p.fspan = (unsigned long long *)(sc + 2 * sb);
+    p.order = (unsigned long long *)(sc + 3 * sb);
+    p.cnt = (uint64_t *)(sc + 4 * sb);
+    p.kept = kept, p.kept_cap = kept_cap, p.q_st_out = q_st_out, p.q_en_out = q_en_out, p.key_flip = key_flip, p.key_order = key_order, p.info = info;
+    HIPCHK(ctx, rb_fill_async(info, 0, sizeof *info, ctx->stream));
+    if (n_keys) HIPCHK(ctx, rb_fill_async(sc, 0, 4 * sb, ctx->stream)); // (every call: nothing of the last one counts)
+    HIPCHK(ctx, rb_launch_pairs_records(&p, (uint64_t *)(sc + 4 * sb + pairs_cnt_bytes(n_rec)), ctx->stream));
+    return RB_OK;
+}
+// the same rules on host arrays, in the reference's order of steps (no device: the tests' second opinion)
+extern "C" int rb_host_pairs_records(const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand,
+                                     const uint32_t *rec_key, const uint64_t *rec_q_len, uint64_t n_rec, uint64_t n_keys, uint32_t mode,
+                                     uint64_t paired_len, uint64_t min_aln, uint64_t min_query, uint32_t *kept, uint64_t kept_cap, uint64_t *q_st_out,
+                                     uint64_t *q_en_out, uint8_t *key_flip, uint64_t *key_order, rb_pairs_info *info) {
+    const char *why;
+    if (!pairs_records_args_ok(t_st, t_en, q_st, q_en, strand, rec_key, rec_q_len, n_rec, n_keys, mode, kept, kept_cap, q_st_out, q_en_out, key_flip, key_order,
+                               info, &why))
+        return RB_E_INVALID;
+    memset(info, 0, sizeof *info);
+    std::vector<int64_t> orient((size_t)n_keys, 0);
+    std::vector<uint64_t> tspan((size_t)n_keys, 0), fspan((size_t)n_keys, 0), order((size_t)n_keys, 0);
+    std::vector<uint8_t> has((size_t)n_keys, 0);
+    const bool do_orient = (mode & RB_PAIRS_ORIENT) != 0, do_filter = (mode & RB_PAIRS_FILTER) != 0;
+    auto passes = [&](uint64_t r) { return !do_filter || (rec_q_len[r] > min_query && t_en[r] - t_st[r] > min_aln); }; // main.rs:242-243
+    for (uint64_t r = 0; r < n_rec; r++) {
+        const uint32_t key = rec_key[r];
+        if (key >= n_keys) {
+            info->declined |= RB_PAIRS_DECL_KEY;
+            continue;
+        }
+        has[key] = 1;
+        const uint64_t q = q_en[r] - q_st[r], w = t_en[r] - t_st[r];
+        if (do_orient) {
+            orient[key] = (int64_t)((uint64_t)orient[key] + (strand[r] == (uint8_t)'-' ? 0 - q : q)); // paf.rs:124-128
+            order[key] += (w * (t_st[r] + t_en[r])) / 2;                                              // paf.rs:133
+        }
+        tspan[key] += w;
+        if (do_filter && passes(r)) fspan[key] += w; // paf.rs:97, behind main.rs:242-243
+    }
+    for (uint64_t i = 0; i < n_keys; i++) {
+        key_flip[i] = orient[i] < 0 ? 1 : 0; // paf.rs:146
+        if (key_order) key_order[i] = do_orient && tspan[i] ? order[i] / tspan[i] : 0; // paf.rs:143
+        if (do_orient && has[i] && tspan[i] == 0) info->declined |= RB_PAIRS_DECL_ZERO_SPAN;
+    }
+    for (uint64_t r = 0; r < n_rec; r++) {
+        const uint32_t key = rec_key[r];
+        const bool part = key < n_keys, flip = part && key_flip[key];
+        if (flip && rec_q_len[r] < q_en[r]) info->declined |= RB_PAIRS_DECL_WRAP;
+        if (q_st_out) {
+            q_st_out[r] = flip ? rec_q_len[r] - q_en[r] : q_st[r]; // paf.rs:148-151
+            q_en_out[r] = flip ? rec_q_len[r] - q_st[r] : q_en[r];
+        }
+        if (!part || !(passes(r) && (!do_filter || paired_len < fspan[key]))) continue; // paf.rs:100
+        if (info->n_kept < kept_cap) kept[info->n_kept] = (uint32_t)r;
+        else info->overflow = 1;
+        info->n_kept++;
+        if (flip) info->n_flipped_rows++;
     }
     return RB_OK;
 }

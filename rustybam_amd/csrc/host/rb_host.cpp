@@ -1293,6 +1293,26 @@ struct Windows {
     std::vector<uint64_t> st, en;
     auto args(const TextFile &f) const { return std::make_tuple(f.contig.data(), (uint64_t)st.size(), contig.data(), st.data(), en.data()); } // the records' contigs, the windows
 };
+// the (target name, query name) pairs of a loaded file as dense keys per record, in order of first appearance, and column 2
+struct PairKeys {
+    std::vector<uint32_t> rec_key;
+    std::vector<uint64_t> rec_q_len;
+    uint64_t n_keys = 0;
+    explicit PairKeys(const TextFile &f) : rec_key(f.recs.size()), rec_q_len(f.recs.size()) {
+        struct PairHash {
+            size_t operator()(const std::pair<std::string_view, std::string_view> &k) const {
+                return std::hash<std::string_view>()(k.first) * 1000003u ^ std::hash<std::string_view>()(k.second);
+            }
+        };
+        std::unordered_map<std::pair<std::string_view, std::string_view>, uint32_t, PairHash> ids;
+        for (size_t i = 0; i < f.recs.size(); i++) {
+            const HeaderOnly &h = f.recs[i];
+            rec_key[i] = ids.emplace(std::make_pair(f.name(h.t_name, h.t_name_n), f.name(h.q_name, h.q_name_n)), (uint32_t)ids.size()).first->second;
+            rec_q_len[i] = h.q_len;
+        }
+        n_keys = ids.size();
+    }
+};
 Windows windows_of(TextFile &f, const std::vector<Region> &rgns) {
     Windows w{std::vector<uint32_t>(rgns.size()), std::vector<uint64_t>(rgns.size()), std::vector<uint64_t>(rgns.size())};
     for (size_t i = 0; i < rgns.size(); i++) {
@@ -1401,27 +1421,14 @@ bool break_pairs_file_text(Engine &eng, const std::string &paf_path, uint32_t br
     TextFile &f = *new TextFile; // (one-shot command, as in break_file_text_impl)
     if (!f.load(paf_path)) return false;
     double tl = now_s();
-    const size_t n = f.recs.size();
-    // the (target name, query name) pairs as dense keys, in order of first appearance
-    struct PairHash {
-        size_t operator()(const std::pair<std::string_view, std::string_view> &k) const {
-            return std::hash<std::string_view>()(k.first) * 1000003u ^ std::hash<std::string_view>()(k.second);
-        }
-    };
-    std::unordered_map<std::pair<std::string_view, std::string_view>, uint32_t, PairHash> ids;
-    std::vector<uint32_t> rec_key(n);
-    std::vector<uint64_t> rec_q_len(n);
-    for (size_t i = 0; i < n; i++) {
-        const HeaderOnly &h = f.recs[i];
-        rec_key[i] = ids.emplace(std::make_pair(f.name(h.t_name, h.t_name_n), f.name(h.q_name, h.q_name_n)), (uint32_t)ids.size()).first->second;
-        rec_q_len[i] = h.q_len;
-    }
-    std::vector<uint8_t> key_flip(ids.size() + 1, 0);
+    const PairKeys pk(f);
+    const std::vector<uint32_t> &rec_key = pk.rec_key;
+    std::vector<uint8_t> key_flip(pk.n_keys + 1, 0);
     lap("pair keys", tl);
     TextCall &c = *new TextCall(f);
     const uint32_t mode = (orient ? RB_PAIRS_ORIENT : 0) | (filter ? RB_PAIRS_FILTER : 0);
     const auto mid = std::make_tuple(break_length);
-    const auto pairs = std::make_tuple(rec_key.data(), rec_q_len.data(), ids.size(), mode, paired_len, min_aln, min_query, key_flip.data(), &c.declined);
+    const auto pairs = std::make_tuple(rec_key.data(), pk.rec_q_len.data(), pk.n_keys, mode, paired_len, min_aln, min_query, key_flip.data(), &c.declined);
     stats_mode ? text_call<true>(eng, RB_ENTRY(rb_host_break_pairs_stats_text), c, eng.bsearch_policy, &tl, mid, pairs)
                : text_call<false>(eng, RB_ENTRY(rb_host_break_pairs_text), c, eng.bsearch_policy, &tl, mid, pairs);
     if (!c.loaded()) return false;
@@ -1461,6 +1468,146 @@ std::vector<std::string> break_pairs_text(Engine &eng, const std::vector<PafReco
     std::vector<std::string> text(1);
     for (const Stats &s : stats_from_paf(eng, p.records)) text[0] += cigar_stats_line(s, stats_mode == 2);
     return text;
+}
+
+// `rb orient [--scaffold --insert I]` and `rb filter` (main.rs:234-267), text in -> text out (rb_host_pairs_text): the CIGARs are parsed and the
+// kept records' printed on the device, the sums per (target name, query name) pair are rb_dev_pairs_records', the lines are assembled here.
+// false = take the record route, nothing was produced: two cg tags, a CIGAR the device left to the host, a pair of target span 0 (orient's
+// divide by zero) or a flipped record that ends behind its query's length.  The panics of Paf::from_file are thrown, in its order.
+// --scaffold (paf.rs:160-207) needs (target name, order, q_st') per record and nothing of the CIGARs, which stay addressable by their text
+// offsets: a stable sort of an index array, then the one linear pass over the header words that are here anyway to be printed.
+static bool pairs_file_text(Engine &eng, const std::string &paf_path, uint32_t mode, uint64_t paired_len, uint64_t min_aln, uint64_t min_query,
+                            bool scaffold, uint64_t spacer, std::vector<std::string> &out_text) {
+    TextFile &f = *new TextFile; // (one-shot command, as in break_file_text_impl)
+    if (!f.load(paf_path)) return false;
+    double tl = now_s();
+    const size_t n = f.recs.size();
+    const PairKeys pk(f);
+    lap("pair keys", tl);
+    const bool orient = (mode & RB_PAIRS_ORIENT) != 0;
+    std::vector<uint8_t> cig_status(n ? n : 1), key_flip(pk.n_keys + 1, 0);
+    std::vector<rb_reduce_row> red(n);
+    std::vector<uint64_t> q_st(n + 1), q_en(n + 1), key_order(pk.n_keys + 1, 0);
+    struct Kept {
+        uint32_t *idx = nullptr;
+        uint64_t n = 0, *toff = nullptr;
+        uint8_t *text = nullptr;
+        ~Kept() { rb_host_free(idx), rb_host_free(toff), rb_host_free(text); }
+    } K;
+    int declined = 0;
+    const auto cols = text_columns(eng, f);
+    const auto tail = std::make_tuple(pk.rec_key.data(), pk.rec_q_len.data(), pk.n_keys, mode, paired_len, min_aln, min_query, cig_status.data(), red.data(), &K.idx,
+                                      &K.n, q_st.data(), q_en.data(), key_flip.data(), key_order.data(), &K.toff, &K.text, &declined);
+    // (no policy, no rows, no norm rows, no counters: not text_call's shape -- the entry point and its lap are still named once)
+    const auto call = [&](auto fn, const char *name) {
+        eng.check(std::apply(fn, std::tuple_cat(cols, tail)), name);
+        lap(name, tl);
+    };
+    call(RB_ENTRY(rb_host_pairs_text));
+    if (!f.check_loaded(cig_status, red)) return false; // (throws the panics of Paf::from_file, in the reference's order of checks)
+    if (declined) return false;
+    const PairNames pn{&pk.rec_key, &key_flip, orient};
+    // what --scaffold changes, per printed line: the place in the output, q_st / q_en, and the scaffold (name, length) of the line's target
+    std::vector<uint32_t> order_idx, line_scaf;
+    std::vector<std::string> scaf_name;
+    std::vector<uint64_t> scaf_len;
+    if (scaffold) { // (orient keeps every record: K.idx is 0 .. n - 1)
+        // targets by name, bytewise (Rust's String order): the rank of every contig id
+        std::vector<std::string_view> names(f.contig_id.size());
+        for (const auto &kv : f.contig_id) names[kv.second] = kv.first;
+        std::vector<uint32_t> by_name(names.size()), rank(names.size());
+        for (uint32_t i = 0; i < by_name.size(); i++) by_name[i] = i;
+        std::sort(by_name.begin(), by_name.end(), [&](uint32_t a, uint32_t b) { return names[a] < names[b]; });
+        for (uint32_t i = 0; i < by_name.size(); i++) rank[by_name[i]] = i;
+        order_idx.resize(K.n);
+        for (uint64_t k = 0; k < K.n; k++) order_idx[k] = (uint32_t)k;
+        std::stable_sort(order_idx.begin(), order_idx.end(), [&](uint32_t a, uint32_t b) { // paf.rs:162-168
+            const uint32_t ra = K.idx[a], rb_ = K.idx[b];
+            if (rank[f.contig[ra]] != rank[f.contig[rb_]]) return rank[f.contig[ra]] < rank[f.contig[rb_]];
+            const uint64_t oa = key_order[pk.rec_key[ra]], ob = key_order[pk.rec_key[rb_]];
+            if (oa != ob) return oa < ob;
+            return q_st[ra] < q_st[rb_];
+        });
+        line_scaf.resize(K.n);
+        // paf.rs:170-205.  Within a target a query name (with its sign) is a pair key: runs of one name are runs of one key
+        std::vector<uint8_t> seen(pk.n_keys + 1, 0);
+        for (size_t g0 = 0; g0 < order_idx.size();) {
+            size_t g1 = g0;
+            const uint32_t t = f.contig[K.idx[order_idx[g0]]];
+            while (g1 < order_idx.size() && f.contig[K.idx[order_idx[g1]]] == t) g1++;
+            std::string name;
+            uint64_t len = 0;
+            for (size_t q0 = g0; q0 < g1;) {
+                const uint32_t key = pk.rec_key[K.idx[order_idx[q0]]];
+                if (!seen[key]) {
+                    seen[key] = 1;
+                    const HeaderOnly &h = f.recs[K.idx[order_idx[q0]]];
+                    if (!name.empty()) name += "::";
+                    name.append(f.all.data() + h.q_name, h.q_name_n);
+                    name += key_flip[key] ? '-' : '+';
+                }
+                size_t q1 = q0;
+                uint64_t q_min = UINT64_MAX, q_max = 0;
+                for (; q1 < g1 && pk.rec_key[K.idx[order_idx[q1]]] == key; q1++) {
+                    q_min = std::min(q_min, q_st[K.idx[order_idx[q1]]]);
+                    q_max = std::max(q_max, q_en[K.idx[order_idx[q1]]]);
+                }
+                for (size_t i = q0; i < q1; i++) {
+                    const uint32_t r = K.idx[order_idx[i]];
+                    q_st[r] = q_st[r] - q_min + len, q_en[r] = q_en[r] - q_min + len;
+                }
+                len += (q_max - q_min) + spacer;
+                q0 = q1;
+            }
+            len -= spacer;
+            for (size_t i = g0; i < g1; i++) line_scaf[i] = (uint32_t)scaf_name.size();
+            scaf_name.push_back(std::move(name)), scaf_len.push_back(len);
+            g0 = g1;
+        }
+        lap("scaffold: sort + pass", tl);
+    }
+    const unsigned TO = parallel_chunk_count((size_t)K.n);
+    out_text.assign(TO, std::string());
+    parallel_chunks((size_t)K.n, [&](unsigned t, size_t lo, size_t hi) {
+        std::string &o = out_text[t];
+        size_t est = 0;
+        for (size_t i = lo; i < hi; i++) {
+            const size_t k = scaffold ? order_idx[i] : i;
+            est += 160 + (size_t)(K.toff[k + 1] - K.toff[k]) + (scaffold ? scaf_name[line_scaf[i]].size() : 0);
+        }
+        o.reserve(est);
+        advise_huge(o.data(), est);
+        char nb[24];
+        auto num = [&](uint64_t v) {
+            auto r = std::to_chars(nb, nb + sizeof nb, v);
+            o.append(nb, r.ptr);
+        };
+        for (size_t i = lo; i < hi; i++) {
+            const size_t k = scaffold ? order_idx[i] : i;
+            const uint32_t r = K.idx[k];
+            const HeaderOnly &s = f.recs[r];
+            if (scaffold) {
+                o += scaf_name[line_scaf[i]]; o += '\t'; num(scaf_len[line_scaf[i]]);
+            } else {
+                o.append(f.all.data() + s.q_name, s.q_name_n);
+                if (orient) o += pn.flipped(r) ? '-' : '+';
+                o += '\t'; num(s.q_len);
+            }
+            o += '\t'; num(q_st[r]); o += '\t'; num(q_en[r]); o += '\t'; o += pn.strand(r, s.strand); o += '\t';
+            o.append(f.all.data() + s.t_name, s.t_name_n); o += '\t'; num(s.t_len); o += '\t'; num(s.t_st); o += '\t'; num(s.t_en); o += '\t';
+            num(red[r].nmatch); o += '\t'; num(red[r].aln_len); o += '\t'; num(s.mapq); o += "\tid:Z:\tcg:Z:"; // (input tags are dropped, the id is empty)
+            o.append((const char *)K.text + K.toff[k], (size_t)(K.toff[k + 1] - K.toff[k]));
+            o += '\n';
+        }
+    });
+    lap("assemble lines", tl);
+    return true;
+}
+bool orient_file_text(Engine &eng, const std::string &paf_path, bool scaffold, uint64_t spacer, std::vector<std::string> &out_text) {
+    return pairs_file_text(eng, paf_path, RB_PAIRS_ORIENT, 0, 0, 0, scaffold, spacer, out_text);
+}
+bool filter_file_text(Engine &eng, const std::string &paf_path, uint64_t paired_len, uint64_t min_aln, uint64_t min_query, std::vector<std::string> &out_text) {
+    return pairs_file_text(eng, paf_path, RB_PAIRS_FILTER, paired_len, min_aln, min_query, false, 0, out_text);
 }
 
 // `rb liftover --break N`, text in -> text out: break-paf, the pieces read back as records and lifted over the windows in one device

@@ -152,6 +152,11 @@ bool break_pairs_file_text(Engine &eng, const std::string &paf_path, uint32_t br
                            uint64_t min_query, int stats_mode, std::vector<std::string> &out_text, std::string &trailing_panic);
 std::vector<std::string> break_pairs_text(Engine &eng, const std::vector<PafRecord> &paf_recs, uint32_t break_length, bool orient, bool filter,
                                           uint64_t paired_len, uint64_t min_aln, uint64_t min_query, int stats_mode, std::string &first_panic);
+// `rb orient [--scaffold --insert I]` / `rb filter -p L -a A -q Q` (main.rs:234-267), text in -> text out for a file or stdin
+// (rb_host_pairs_text: rb_dev_pairs_records on the records, the kept records' CIGARs printed on the device; --scaffold sorts an index array
+// on the host); false = take the record route (Paf::from_file, Paf::orient / scaffold / filter_*, records_to_text), nothing was produced
+bool orient_file_text(Engine &eng, const std::string &paf_path, bool scaffold, uint64_t spacer, std::vector<std::string> &out_text);
+bool filter_file_text(Engine &eng, const std::string &paf_path, uint64_t paired_len, uint64_t min_aln, uint64_t min_query, std::vector<std::string> &out_text);
 // the same two routes as a pipeline over chunks of a big plain file (a few host threads, each with its own context on `device`):
 // the sink receives the chunks' outputs in file order while later chunks are still being read / clipped / printed.  A chunk's text
 // is contig-major within the chunk (runs); false = not applicable or a line needs the general parser (pipeline_started(): the

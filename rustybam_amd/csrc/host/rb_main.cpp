@@ -1170,16 +1170,24 @@ int main(int argc, char **argv) {
             }
             emit(text);
         } else if (filter) { // main.rs:234-249
-            rb::Paf paf = rb::Paf::from_file(eng, paf_path);
-            paf.filter_query_len(min_query);
-            paf.filter_aln_len(min_aln);
-            paf.filter_aln_pairs(paired_len);
-            put(rb::records_to_text(paf.records));
+            std::vector<std::string> text;
+            if (!(text_path && rb::filter_file_text(eng, paf_path, paired_len, min_aln, min_query, text))) {
+                rb::Paf paf = rb::Paf::from_file(eng, paf_path);
+                paf.filter_query_len(min_query);
+                paf.filter_aln_len(min_aln);
+                paf.filter_aln_pairs(paired_len);
+                text = rb::records_to_text(paf.records);
+            }
+            emit(text);
         } else if (orient) { // main.rs:253-267
-            rb::Paf paf = rb::Paf::from_file(eng, paf_path);
-            paf.orient();
-            if (do_scaffold) paf.scaffold(insert);
-            put(rb::records_to_text(paf.records));
+            std::vector<std::string> text;
+            if (!(text_path && rb::orient_file_text(eng, paf_path, do_scaffold, insert, text))) {
+                rb::Paf paf = rb::Paf::from_file(eng, paf_path);
+                paf.orient();
+                if (do_scaffold) paf.scaffold(insert);
+                text = rb::records_to_text(paf.records);
+            }
+            emit(text);
         } else if (trim) {
             std::vector<std::string> ttext;
             if (text_path && rb::trim_file_text(eng, paf_path, ms, ds, is, remove_contained, ttext)) {

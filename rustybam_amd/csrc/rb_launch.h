@@ -209,6 +209,25 @@ extern "C" hipError_t rb_launch_pairs(const rb_pairs_params *p, uint64_t *block_
 extern "C" hipError_t rb_launch_pairs_desc(const rb_hit_row *rows, uint64_t n_rows, const uint32_t *out_ops, uint32_t *desc /* [4 * n_rows] */, hipStream_t stream);
 extern "C" uint32_t rb_pairs_wave_rows(void);
 extern "C" uint32_t rb_pairs_block_rows(void);
+// the same over the RECORDS of a batch (rb_dev_pairs_records): the columns instead of rows, a fourth sum (order), the kept records' indices out
+struct rb_pairs_rec_params {
+    const uint64_t *t_st, *t_en, *q_st, *q_en; // [n_rec]
+    const uint8_t *strand;     // [n_rec]
+    const uint32_t *rec_key;   // [n_rec]
+    const uint64_t *rec_q_len; // [n_rec]
+    uint64_t n_rec, n_keys;
+    uint32_t mode;             // RB_PAIRS_ORIENT | RB_PAIRS_FILTER
+    uint64_t paired_len, min_aln, min_query;
+    unsigned long long *orient, *tspan, *fspan, *order; // [n_keys] each, zeroed: the four sums
+    uint64_t *cnt;             // [n_rec + 1]: 1 per kept record, then the exclusive prefix
+    uint32_t *kept;            // [kept_cap] OUT
+    uint64_t kept_cap;
+    uint64_t *q_st_out, *q_en_out; // [n_rec] OUT, or both NULL
+    uint8_t *key_flip;         // [n_keys] OUT
+    uint64_t *key_order;       // [n_keys] OUT, or NULL
+    rb_pairs_info *info;       // zeroed
+};
+extern "C" hipError_t rb_launch_pairs_records(const rb_pairs_rec_params *p, uint64_t *block_sums, hipStream_t stream);
 
 // ---- k_hitstats.hip: stats of every hit row's clip ----
 struct rb_hitstats_params {
