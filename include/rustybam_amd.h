@@ -24,6 +24,8 @@
  *   rb_dev_stats_rows     <- bamstats::stats_from_paf / add_stats_from_cigar              bamstats.rs:91-105, :107-154
  *                            + PafRecord::check_integrity (paf.rs:825-857) of every record that trim_paf_by_rgns /
  *                            break_paf_on_indels returned (the second command of `rb liftover .. | rb stats --paf`)
+ *   rb_dev_parse_md       <- bamstats::parse_md_for_stats                                 bamstats.rs:48-79
+ *   rb_dev_aln_stats      <- bamstats::cigar_stats minus the names: query span, strand flip, MD refinement   bamstats.rs:129-142, :190-207
  *
  * Conventions
  *   - Plain C types only.  Every `rb_dev_*` pointer argument is a DEVICE pointer (HBM) owned by
@@ -786,6 +788,67 @@ int rb_host_stats_rows(rb_ctx *ctx, uint64_t n_rec, const uint32_t *ops, const u
 int rb_host_scan_text(rb_ctx *ctx, uint64_t n_rec, const uint8_t *text, uint64_t text_bytes, const uint64_t *cig_off, const uint64_t *cig_end,
                       const uint64_t *t_st, const uint64_t *t_en, const uint64_t *q_st, const uint64_t *q_en, const uint8_t *strand,
                       uint8_t *cig_status, rb_reduce_row *reduce_out, rb_norm_row *norm_out);
+
+/* ---- stats of ALIGNMENT records (`rb stats` on SAM / BAM, main.rs:60-77): MD strings and query spans -------------------------- *
+ *
+ * rb_dev_parse_md   <- bamstats::parse_md_for_stats (bamstats.rs:48-79) for n strings: the regex (\d+)|([A-Z])|(\^[A-Z]+) applied left
+ *                      to right, restated as runs: every maximal digit run adds its value; every maximal run of A-Z whose preceding
+ *                      byte (inside the string) is '^' is one deletion event of that many bases; every other A-Z byte is one mismatch;
+ *                      every other byte -- a lone '^', lower case, anything else -- is skipped.  Sums wrap in u32.
+ *     text      device bytes that hold the strings (the `MD:Z:` values, without the tag); 16-byte aligned.  SLACK: the call reads whole
+ *               aligned 16-byte groups that hold at least one byte of a string, so text must be readable up to the next multiple of 16
+ *               behind the last string's end; bytes outside a string are never looked at, whatever they are.
+ *     md_off    [n] start of every string;  md_end [n] its end (an end at or in front of the start: the empty string, nothing is read)
+ *     out       [4 n] OUT u32, 16-byte aligned: match_count, mismatch_count, deletion events, deletion bases of string r at out[4 r ..]
+ *     status    [n] OUT  RB_MD_OK, or RB_MD_UNUSUAL: a digit run of ten or more digits (zero padded, or past u32) -- not decided on
+ *               the device, as rb_dev_parse_cigars does with such lengths; out[4 r ..] is then four zeros, parse the string on the host
+ *     Enqueues on the context's stream, does not synchronise.  n == 0 is valid.  Writes out[0 .. 4 n) and status[0 .. n), nothing else.
+ *     Two calls on the same input write the same bytes.
+ * rb_md_shape: the kernel's thresholds, for tests (no device needed): out[0] = bytes per step of a row of 16 lanes, out[1] = the
+ *     longest string a row takes (longer ones are walked by the whole wavefront), out[2] = bytes per step of the wavefront.
+ * rb_host_parse_md: the same on HOST arrays (text [text_bytes], no slack or alignment asked of it): uploads, runs, downloads.
+ *
+ * rb_dev_aln_stats  <- bamstats::cigar_stats (bamstats.rs:129-142, :190-207) minus the names, for the n = batch->n_rec alignments of a
+ *                      batch: one rb_aln_row each.
+ *     batch        only ops and op_off [n + 1] are read (aligned packed ops, as every kernel takes them); of a record's ops a few at both
+ *                  ends: leading H / P, and from the last op back to the last M / = / X
+ *     reduce_rows  [n] what rb_dev_scan_records wrote for that batch with all coordinates zero (their status is therefore not looked at)
+ *     pos [n] i64 0-based leftmost position;  flag [n] u32 (only bit 16 is read);  l_seq [n] u32 (0 for a SEQ of `*`)
+ *     md [4 n], md_status [n]  the outputs of rb_dev_parse_md, record r's at [4 r ..] / [r];  has_md [n] u8, != 0: the record has an MD tag.
+ *                  has_md NULL: no record has one (md and md_status may then be NULL too); md_status NULL: all RB_MD_OK
+ *     rows [n] OUT r_en = pos + t_bases;  q_st = leading H + leading S (also H S);  q_en = leading H + 1 + (q_bases - trailing S / I - 1);
+ *                  q_len = leading H + l_seq + trailing H;  with flag & 16: q_st, q_en = q_len - q_en, q_len - q_st;  the seven counters
+ *                  and three identities of the reduce row -- unless equal == 0 && matches > 0 and the record has an MD: then equal =
+ *                  md[0], diff = md[1] and the identities are recomputed from them;  flags = RB_ALN_WARN_M for matches > 0 without MD
+ *                  (the reference's warning);  status, in the reference's order of checks:
+ *                    RB_ALN_PANIC_DEL_FIRST  rust-htslib read_pos: D / N before any op that describes read sequence
+ *                    RB_ALN_PANIC_HARDCLIP   ... H between operations
+ *                    RB_ALN_PANIC_NONE       read_pos is None: the span ends in D / N, there is no M / = / X, or t_bases == 0
+ *                    RB_ALN_MD_STATUS | s    the MD is needed and its md_status s is not RB_MD_OK (the host parses that string)
+ *                    RB_ALN_PANIC_MD_ASSERT  md[0] + md[1] != diff (bamstats.rs:133)
+ *                  A row whose status is not RB_ALN_OK is all zero otherwise.
+ *     Enqueues on the context's stream, does not synchronise.  n == 0 is valid.  Reads no text: no slack.  Writes rows[0 .. n) only.
+ * rb_host_aln_stats: the same on HOST arrays (ops / op_off as rb_host_scan_records takes them, reduce_rows as it returned them). */
+enum { RB_MD_OK = 0, RB_MD_UNUSUAL = 3 };
+enum { RB_ALN_OK = 0, RB_ALN_PANIC_DEL_FIRST = 32, RB_ALN_PANIC_HARDCLIP = 33, RB_ALN_PANIC_NONE = 34, RB_ALN_PANIC_MD_ASSERT = 35,
+       RB_ALN_MD_STATUS = 64 };
+enum { RB_ALN_WARN_M = 1 };
+typedef struct rb_aln_row { /* 80 B */
+    int64_t r_en, q_st, q_en, q_len;
+    uint32_t equal, diff, ins, del, matches, ins_events, del_events;
+    float id_by_all, id_by_events, id_by_matches;
+    uint32_t status, flags;
+} rb_aln_row;
+void rb_md_shape(uint32_t out[3]);
+int rb_dev_parse_md(rb_ctx *ctx, const uint8_t *text, const uint64_t *md_off, const uint64_t *md_end, uint64_t n, uint32_t *out /* [4 n] */,
+                    uint8_t *status /* [n] */);
+int rb_host_parse_md(rb_ctx *ctx, const uint8_t *text, uint64_t text_bytes, const uint64_t *md_off, const uint64_t *md_end, uint64_t n,
+                     uint32_t *out, uint8_t *status);
+int rb_dev_aln_stats(rb_ctx *ctx, const rb_batch_view *batch, const rb_reduce_row *reduce_rows, const int64_t *pos, const uint32_t *flag,
+                     const uint32_t *l_seq, const uint32_t *md, const uint8_t *md_status, const uint8_t *has_md, rb_aln_row *rows);
+int rb_host_aln_stats(rb_ctx *ctx, uint64_t n, const uint32_t *ops, const uint64_t *op_off, const rb_reduce_row *reduce_rows, const int64_t *pos,
+                      const uint32_t *flag, const uint32_t *l_seq, const uint32_t *md, const uint8_t *md_status, const uint8_t *has_md,
+                      rb_aln_row *rows);
 
 /* ---- nucfreq: A/C/G/T counts at every covered reference position -----------------
  *

@@ -45,6 +45,14 @@ assert PIECES_INFO_DT.itemsize == 64
 PAIRS_INFO_DT = np.dtype([("n_kept", "<u8"), ("n_flipped_rows", "<u8"), ("overflow", "<u4"), ("declined", "<u4"), ("_reserved", "<u8", 5)])  # rb_pairs_info
 assert PAIRS_INFO_DT.itemsize == 64
 PAIRS_ORIENT, PAIRS_FILTER = 1, 2  # rb_dev_pairs_rows: mode
+ALN_DT = np.dtype(
+    [("r_en", "<i8"), ("q_st", "<i8"), ("q_en", "<i8"), ("q_len", "<i8"), ("equal", "<u4"), ("diff", "<u4"), ("ins", "<u4"), ("del", "<u4"),
+     ("matches", "<u4"), ("ins_events", "<u4"), ("del_events", "<u4"), ("id_by_all", "<f4"), ("id_by_events", "<f4"), ("id_by_matches", "<f4"),
+     ("status", "<u4"), ("flags", "<u4")])  # rb_aln_row
+assert ALN_DT.itemsize == 80
+MD_OK, MD_UNUSUAL = 0, 3  # rb_dev_parse_md: status
+ALN_OK, ALN_PANIC_DEL_FIRST, ALN_PANIC_HARDCLIP, ALN_PANIC_NONE, ALN_PANIC_MD_ASSERT, ALN_MD_STATUS = 0, 32, 33, 34, 35, 64  # rb_aln_row.status
+ALN_WARN_M = 1  # rb_aln_row.flags
 PAIRS_DECL_PANIC, PAIRS_DECL_KEY, PAIRS_DECL_WRAP, PAIRS_DECL_ZERO_SPAN = 1, 2, 4, 8  # rb_pairs_info.declined
 
 
@@ -120,6 +128,16 @@ def rows_to_batch_shape():
     (rb_rows_to_batch_shape: no device needed)"""
     out = (C.c_uint32 * 3)()
     f = lib().rb_rows_to_batch_shape
+    f.restype = None
+    f(out)
+    return tuple(int(x) for x in out)
+
+
+def md_shape():
+    """(bytes per step of a row of 16 lanes, longest string a row takes, bytes per step of the wavefront) of rb_dev_parse_md's kernel
+    (rb_md_shape: no device needed)"""
+    out = (C.c_uint32 * 3)()
+    f = lib().rb_md_shape
     f.restype = None
     f(out)
     return tuple(int(x) for x in out)
@@ -414,6 +432,95 @@ class Engine:
             self.sync()
             for b in bufs:
                 self.dev_free(b)
+
+    # ---- MD strings and query spans of alignment records (k_alnstats.hip) ----
+    def _up(self, bufs, a, n_bytes=None):
+        """a device buffer of n_bytes (at least the array's; tracked in bufs) holding the host array; -> address"""
+        bufs.append(self.dev_alloc(max(a.nbytes if n_bytes is None else n_bytes, 256)))
+        if a.nbytes:
+            self._chk(self.L.rb_dev_upload(self.ctx, C.c_void_p(bufs[-1]), _p(a), C.c_size_t(a.nbytes)), "rb_dev_upload")
+        return bufs[-1]
+
+    def _down(self, a, ptr):
+        if a.nbytes:
+            self._chk(self.L.rb_dev_download(self.ctx, _p(a), C.c_void_p(ptr), C.c_size_t(a.nbytes)), "rb_dev_download")
+        return a
+
+    def dev_parse_md(self, text_ptr, md_off_ptr, md_end_ptr, n, out_ptr, status_ptr):
+        """rb_dev_parse_md on device addresses; enqueues on the context's stream"""
+        v = C.c_void_p
+        self._chk(self.L.rb_dev_parse_md(self.ctx, v(text_ptr or 0), v(md_off_ptr or 0), v(md_end_ptr or 0), C.c_uint64(n), v(out_ptr or 0),
+                                         v(status_ptr or 0)), "rb_dev_parse_md")
+
+    def dev_aln_stats(self, view, reduce_ptr, pos_ptr, flag_ptr, l_seq_ptr, md_ptr, md_status_ptr, has_md_ptr, rows_ptr):
+        """rb_dev_aln_stats on device addresses (view: ops and op_off of the batch); enqueues on the context's stream"""
+        v = C.c_void_p
+        self._chk(self.L.rb_dev_aln_stats(self.ctx, C.byref(view), v(reduce_ptr or 0), v(pos_ptr or 0), v(flag_ptr or 0), v(l_seq_ptr or 0),
+                                          v(md_ptr or 0), v(md_status_ptr or 0), v(has_md_ptr or 0), v(rows_ptr or 0)), "rb_dev_aln_stats")
+
+    def parse_md(self, text, md_off, md_end, guard=0):
+        """rb_dev_parse_md on host arrays: text (bytes-like; padded here to the slack the call asks for), the strings' extents
+        -> (out u32 [n + guard, 4], status u8 [n + guard]); the `guard` entries behind the n results were filled with 0xA5 before the call
+        (the tests look at them afterwards)"""
+        text = np.frombuffer(bytes(text), np.uint8)
+        text = np.concatenate([text, np.full(-len(text) % 16, 0x5E, np.uint8)])  # (slack bytes: carets, which the call must not see)
+        md_off, md_end = _arr(md_off, np.uint64), _arr(md_end, np.uint64)
+        n = len(md_off)
+        out, status = np.full((n + guard, 4), 0xA5A5A5A5, np.uint32), np.full(n + guard, 0xA5, np.uint8)
+        bufs = []
+        try:
+            d = [self._up(bufs, a) for a in (text, md_off, md_end, out, status)]
+            self.dev_parse_md(d[0], d[1], d[2], n, d[3], d[4])
+            return self._down(out, d[3]), self._down(status, d[4])
+        finally:
+            self.sync()
+            for b in bufs:
+                self.dev_free(b)
+
+    def host_parse_md(self, text, md_off, md_end):
+        """rb_host_parse_md -> (out u32 [n, 4], status u8 [n])"""
+        text = np.frombuffer(bytes(text), np.uint8)
+        md_off, md_end = _arr(md_off, np.uint64), _arr(md_end, np.uint64)
+        n = len(md_off)
+        out, status = np.zeros((n, 4), np.uint32), np.zeros(n, np.uint8)
+        self._chk(self.L.rb_host_parse_md(self.ctx, _p(text), C.c_uint64(len(text)), _p(md_off), _p(md_end), C.c_uint64(n), _p(out), _p(status)),
+                  "rb_host_parse_md")
+        return out, status
+
+    def _aln_cols(self, n, pos, flag, l_seq, md, md_status, has_md):
+        cols = [_arr(pos, np.int64), _arr(flag, np.uint32), _arr(l_seq, np.uint32)]
+        cols += [None if has_md is None else _arr(md, np.uint32).reshape(-1), None if has_md is None or md_status is None else _arr(md_status, np.uint8),
+                 None if has_md is None else _arr(has_md, np.uint8)]
+        assert all(c is None or len(c) == (4 * n if i == 3 else n) for i, c in enumerate(cols)), "one entry per alignment (four per MD)"
+        return cols
+
+    def aln_stats(self, ops, op_off, reduce_rows, pos, flag, l_seq, md=None, md_status=None, has_md=None, guard=0):
+        """rb_dev_aln_stats on host arrays (reduce_rows: REDUCE_DT, the record scan's rows of the batch with all coordinates zero; md [n, 4] /
+        md_status / has_md: rb_dev_parse_md's outputs, or has_md None: no record has an MD) -> ALN_DT [n + guard]; the guard rows were
+        filled with 0xA5 before the call"""
+        ops, op_off, red = _arr(ops, np.uint32), _arr(op_off, np.uint64), _arr(reduce_rows, REDUCE_DT)
+        n = len(op_off) - 1
+        cols = self._aln_cols(n, pos, flag, l_seq, md, md_status, has_md)
+        rows = np.frombuffer(np.full((n + guard) * ALN_DT.itemsize, 0xA5, np.uint8).tobytes(), ALN_DT).copy()
+        bufs = []
+        try:
+            d = [0 if a is None else self._up(bufs, a) for a in [ops, op_off, red] + cols + [rows]]
+            view = self.batch_view(n, len(ops), d[0], d[1], 0, 0, 0, 0, 0, 0)
+            self.dev_aln_stats(view, *d[2:10])
+            return self._down(rows, d[9])
+        finally:
+            self.sync()
+            for b in bufs:
+                self.dev_free(b)
+
+    def host_aln_stats(self, ops, op_off, reduce_rows, pos, flag, l_seq, md=None, md_status=None, has_md=None):
+        """rb_host_aln_stats -> ALN_DT [n]"""
+        ops, op_off, red = _arr(ops, np.uint32), _arr(op_off, np.uint64), _arr(reduce_rows, REDUCE_DT)
+        n = len(op_off) - 1
+        cols = self._aln_cols(n, pos, flag, l_seq, md, md_status, has_md)
+        rows = np.zeros(n, ALN_DT)
+        self._chk(self.L.rb_host_aln_stats(self.ctx, C.c_uint64(n), _p(ops), _p(op_off), _p(red), *map(_p, cols), _p(rows)), "rb_host_aln_stats")
+        return rows
 
     def rows_to_batch_scratch_bytes(self, n_rows):
         f = self.L.rb_rows_to_batch_scratch_bytes

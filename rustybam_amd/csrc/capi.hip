@@ -2542,6 +2542,94 @@ extern "C" int rb_host_stats_rows(rb_ctx *ctx, uint64_t n_rec, const uint32_t *o
     return rc ? rc : rb_ctx_sync(ctx);
 }
 
+// ---- MD strings and query spans of alignment records (k_alnstats.hip) ----------------------------------
+extern "C" void rb_md_shape(uint32_t out[3]) { out[0] = rb_md_row_step(), out[1] = rb_md_row_max(), out[2] = rb_md_wave_step(); }
+extern "C" int rb_dev_parse_md(rb_ctx *ctx, const uint8_t *text, const uint64_t *md_off, const uint64_t *md_end, uint64_t n, uint32_t *out,
+                               uint8_t *status) {
+    if (!ctx || (n && (!text || !md_off || !md_end || !out || !status))) return RB_E_INVALID;
+    if ((((uintptr_t)text | (uintptr_t)out) & 15u) != 0) return fail(ctx, RB_E_INVALID, "text and out must be 16-byte aligned");
+    rb_md_params p;
+    p.n = n;
+    p.text = text;
+    p.md_off = md_off;
+    p.md_end = md_end;
+    p.out = out;
+    p.status = status;
+    HIPCHK(ctx, rb_launch_parse_md(&p, ctx->stream));
+    return RB_OK;
+}
+extern "C" int rb_dev_aln_stats(rb_ctx *ctx, const rb_batch_view *batch, const rb_reduce_row *reduce_rows, const int64_t *pos,
+                                const uint32_t *flag, const uint32_t *l_seq, const uint32_t *md, const uint8_t *md_status, const uint8_t *has_md,
+                                rb_aln_row *rows) {
+    if (!ctx || !batch) return RB_E_INVALID;
+    const uint64_t n = batch->n_rec;
+    if (n && (!batch->op_off || !reduce_rows || !pos || !flag || !l_seq || !rows || (has_md && !md))) return RB_E_INVALID;
+    if (n && batch->n_ops && !batch->ops) return RB_E_INVALID;
+    rb_alnstats_params p;
+    p.n = n;
+    p.ops = batch->ops;
+    p.op_off = batch->op_off;
+    p.reduce_rows = reduce_rows;
+    p.pos = pos;
+    p.flag = flag;
+    p.l_seq = l_seq;
+    p.md = md;
+    p.md_status = md_status;
+    p.has_md = has_md;
+    p.rows = rows;
+    HIPCHK(ctx, rb_launch_aln_stats(&p, ctx->stream));
+    return RB_OK;
+}
+extern "C" int rb_host_parse_md(rb_ctx *ctx, const uint8_t *text, uint64_t text_bytes, const uint64_t *md_off, const uint64_t *md_end, uint64_t n,
+                                uint32_t *out, uint8_t *status) {
+    if (!ctx || (n && (!md_off || !md_end || !out || !status)) || (text_bytes && !text)) return RB_E_INVALID;
+    for (uint64_t r = 0; r < n; r++)
+        if (md_end[r] > md_off[r] && md_end[r] > text_bytes) return fail(ctx, RB_E_INVALID, "string %llu: MD range outside the text", (unsigned long long)r);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBatch b(ctx);
+    uint8_t *d_text = nullptr, *d_status = nullptr;
+    const uint64_t *d_off = nullptr, *d_end = nullptr;
+    uint32_t *d_out = nullptr;
+    int rc = b.alloc((size_t)text_bytes + 32, &d_text); // (the slack the device call asks for)
+    if (!rc && text_bytes) rc = rb_dev_upload(ctx, d_text, text, (size_t)text_bytes);
+    if (!rc) rc = b.up(md_off, (size_t)n, &d_off);
+    if (!rc) rc = b.up(md_end, (size_t)n, &d_end);
+    if (!rc) rc = b.alloc(4 * (size_t)n + 4, &d_out);
+    if (!rc) rc = b.alloc((size_t)n + 1, &d_status);
+    if (!rc) rc = rb_dev_parse_md(ctx, d_text, d_off, d_end, n, d_out, d_status);
+    if (!rc && n) rc = rb_dev_download(ctx, out, d_out, 16 * (size_t)n);
+    if (!rc && n) rc = rb_dev_download(ctx, status, d_status, (size_t)n);
+    return rc ? rc : rb_ctx_sync(ctx);
+}
+extern "C" int rb_host_aln_stats(rb_ctx *ctx, uint64_t n, const uint32_t *ops, const uint64_t *op_off, const rb_reduce_row *reduce_rows,
+                                 const int64_t *pos, const uint32_t *flag, const uint32_t *l_seq, const uint32_t *md, const uint8_t *md_status,
+                                 const uint8_t *has_md, rb_aln_row *rows) {
+    if (!ctx || (n && (!op_off || !reduce_rows || !pos || !flag || !l_seq || !rows || (has_md && !md)))) return RB_E_INVALID;
+    if (n && op_off[n] && !ops) return RB_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBatch b(ctx);
+    b.v.n_rec = n;
+    b.v.n_ops = n ? op_off[n] : 0;
+    const rb_reduce_row *d_red = nullptr;
+    const int64_t *d_pos = nullptr;
+    const uint32_t *d_flag = nullptr, *d_lseq = nullptr, *d_md = nullptr;
+    const uint8_t *d_mst = nullptr, *d_has = nullptr;
+    rb_aln_row *d_rows = nullptr;
+    int rc = b.up(ops, (size_t)b.v.n_ops, &b.v.ops);
+    if (!rc) rc = b.up(op_off, (size_t)n + 1, &b.v.op_off);
+    if (!rc) rc = b.up(reduce_rows, (size_t)n, &d_red);
+    if (!rc) rc = b.up(pos, (size_t)n, &d_pos);
+    if (!rc) rc = b.up(flag, (size_t)n, &d_flag);
+    if (!rc) rc = b.up(l_seq, (size_t)n, &d_lseq);
+    if (!rc && has_md) rc = b.up(md, 4 * (size_t)n, &d_md);
+    if (!rc && has_md && md_status) rc = b.up(md_status, (size_t)n, &d_mst);
+    if (!rc && has_md) rc = b.up(has_md, (size_t)n, &d_has);
+    if (!rc) rc = b.alloc((size_t)n + 1, &d_rows);
+    if (!rc) rc = rb_dev_aln_stats(ctx, &b.v, d_red, d_pos, d_flag, d_lseq, d_md, d_mst, d_has, d_rows);
+    if (!rc && n) rc = rb_dev_download(ctx, rows, d_rows, (size_t)n * sizeof(rb_aln_row));
+    return rc ? rc : rb_ctx_sync(ctx);
+}
+
 // ---- the hit rows of a clip call as a dense batch (k_rows_batch.hip) ----------------------------------
 // scratch of rb_dev_rows_to_batch: [ops per row (n_rows + 1) u64][1 per OK row (n_rows + 1) u64][block sums of the scans]
 static size_t rtb_cnt_bytes(uint64_t n_rows) { return ((size_t)(n_rows + 1) * 8 + 255) & ~(size_t)255; }

@@ -1,6 +1,7 @@
 // rb_host.cpp -- see rb_host.hpp.  No CIGAR is walked on the CPU here: counting, clipping, splitting and
 // swapping all go through the C ABI to the device.
 #include "rb_host.hpp"
+#include "../rb_span.h"
 
 #include <zlib.h>
 
@@ -2257,6 +2258,50 @@ void parse_md_for_stats(const std::string &md, uint32_t out[4]) { // regex (\d+)
     out[0] = m, out[1] = mm, out[2] = ic, out[3] = ib;
 }
 
+// bamstats::cigar_stats (bamstats.rs:129-142, :190-207) for one alignment, names apart: the record route's twin of rb_dev_aln_stats
+// (rb_k_aln_stats), from the same statement of the span rules (rb_span.h).  cg[nc]: the packed CIGAR, red: the record scan's row of
+// it.  Fills the coordinates, the strand and the counters of s; throws the reference's panic; prints its warning for M without MD.
+static void aln_stats_record(const uint32_t *cg, size_t nc, const rb_reduce_row &red, int64_t pos, uint32_t flag, uint32_t l_seq, bool has_md,
+                             const std::string &md, const std::string &qname, Stats &s) {
+    const rb_span_ends sp = rb_span_ends_of(cg, nc, red.t_bases);
+    const bool scan = (sp.status == RB_ALN_OK || sp.status == RB_ALN_PANIC_NONE) && sp.e > sp.j;
+    switch (rb_span_status(sp, scan && rb_span_inner_clip(cg, sp.j, sp.e))) {
+    case RB_ALN_OK: break;
+    case RB_ALN_PANIC_DEL_FIRST: throw Panic("read_pos: 'deletion' found before any operation describing read sequence (" + qname + ")");
+    case RB_ALN_PANIC_HARDCLIP: throw Panic("read_pos: hard clip between operations (" + qname + ")");
+    default: throw Panic("called `Option::unwrap()` on a `None` value (read_pos) for " + qname);
+    }
+    s.r_st = pos;
+    s.r_en = pos + (int64_t)red.t_bases; // CigarStringView::end_pos = pos + reference-consuming lengths
+    const int64_t qpos = (int64_t)red.q_bases - sp.q_after - 1; // S and I count as read bases, H does not
+    s.q_st = sp.lead_h + sp.lead_s;
+    s.q_en = sp.lead_h + 1 + qpos;
+    s.q_len = sp.lead_h + (int64_t)l_seq + sp.trail_h;
+    s.strand = (flag & 16) ? '-' : '+';
+    if (flag & 16) { // bamstats.rs:203-207
+        const int64_t t = s.q_st;
+        s.q_st = s.q_len - s.q_en;
+        s.q_en = s.q_len - t;
+    }
+    s.equal = red.equal, s.diff = red.diff, s.ins = red.ins, s.del = red.del, s.matches = red.matches;
+    s.ins_events = red.ins_events, s.del_events = red.del_events;
+    s.id_by_all = red.id_by_all, s.id_by_events = red.id_by_events, s.id_by_matches = red.id_by_matches;
+    if (s.equal == 0 && s.matches > 0 && has_md) { // bamstats.rs:129-142
+        uint32_t m4[4];
+        parse_md_for_stats(md, m4);
+        if (m4[0] + m4[1] != s.diff) throw Panic("assertion failed: m_count + mm_count == stats.diff");
+        s.equal = m4[0];
+        s.diff = m4[1];
+        const volatile float e = (float)s.equal;
+        const volatile float num = 100.0f * e;
+        s.id_by_all = num / (float)(uint32_t)(s.equal + s.diff + s.del + s.ins);
+        s.id_by_events = num / (float)(uint32_t)(s.equal + s.diff + s.del_events + s.ins_events);
+        s.id_by_matches = num / (float)(uint32_t)(s.equal + s.diff);
+    } else if (s.matches > 0 && !has_md) { // bamstats.rs:145-153 (once per such record, like the reference)
+        fprintf(stderr, "\r⚠ warning: cigar string contains 'M', assuming mismatch since there is no MD tag.");
+    }
+}
+
 namespace {
 struct BamRec {
     std::string qname, md;
@@ -2276,8 +2321,15 @@ struct BamStream {
     std::unique_ptr<uint8_t[]> buf;
     size_t n = 0, pos = 0;
     explicit BamStream(const std::string &path) {
-        if (path != "-" && inflate_bgzf(path)) return;
-        gzFile f = path == "-" ? gzdopen(0, "rb") : gzopen(path.c_str(), "rb");
+        if (path == "-") { // (stdin is read once: `rb stats -` has looked at it to tell SAM from BAM)
+            const std::string &all = stdin_text();
+            n = all.size();
+            buf.reset(new uint8_t[n + 1]);
+            if (n) memcpy(buf.get(), all.data(), n);
+            return;
+        }
+        if (inflate_bgzf(path)) return;
+        gzFile f = gzopen(path.c_str(), "rb");
         if (!f) throw Panic("Failed to open " + path); // main.rs:63, nucfreq.rs:115
         gzbuffer(f, 1 << 20);
         std::vector<uint8_t> all, chunk(1 << 24);
@@ -2515,71 +2567,11 @@ std::vector<Stats> cigar_stats_bam(Engine &eng, const std::string &path, std::st
     std::vector<Stats> out(n);
     for (size_t i = 0; i < n; i++) try {
         const BamRec &r = recs[i];
-        const uint32_t *cg = ops.data() + r.cig0;
-        const size_t nc = r.ncig;
-        auto opc = [&](size_t k) { return cg[k] & 15u; };
-        auto len = [&](size_t k) { return (int64_t)(cg[k] >> 4); };
         Stats &s = out[i];
         s.r_nm = (r.ref_id >= 0 && (uint32_t)r.ref_id < n_ref) ? ref_nm[r.ref_id] : "*";
         s.r_len = (r.ref_id >= 0 && (uint32_t)r.ref_id < n_ref) ? ref_len[r.ref_id] : 0;
-        s.r_st = r.pos;
-        s.r_en = r.pos + (int64_t)red[i].t_bases; // CigarStringView::end_pos = pos + reference-consuming lengths
         s.q_nm = r.qname;
-        const int64_t lead_h = (nc && opc(0) == RB_OP_H) ? len(0) : 0;
-        int64_t lead_s = 0;
-        if (nc && opc(0) == RB_OP_S) lead_s = len(0);
-        else if (nc > 1 && opc(0) == RB_OP_H && opc(1) == RB_OP_S) lead_s = len(1);
-        const int64_t trail_h = (nc && opc(nc - 1) == RB_OP_H) ? len(nc - 1) : 0;
-        // read_pos(r_en - 1): position in the read of the last reference base = read bases consumed through the last
-        // M/=/X op, minus one; anything else at the end of the reference span makes the reference's unwrap() panic
-        int64_t q_after = 0;
-        size_t k = nc;
-        bool ok = false;
-        for (size_t j = 0; j < nc; j++) { // rust-htslib read_pos: D / N before any op that describes read sequence is an Err
-            const uint32_t o = opc(j);
-            if (o == RB_OP_D || o == RB_OP_N) throw Panic("read_pos: 'deletion' found before any operation describing read sequence (" + r.qname + ")");
-            if (o == RB_OP_H && j > 0 && j + 1 < nc) throw Panic("read_pos: hard clip between operations (" + r.qname + ")");
-            if (o != RB_OP_H && o != RB_OP_P) break;
-        }
-        while (k > 0) {
-            const uint32_t o = opc(k - 1);
-            if (o == RB_OP_M || o == RB_OP_EQ || o == RB_OP_X) {
-                ok = true;
-                break;
-            }
-            if (o == RB_OP_D || o == RB_OP_N) break;
-            if (o == RB_OP_H && !(k == nc || k == 1)) break;
-            if (o == RB_OP_S || o == RB_OP_I) q_after += len(k - 1);
-            k--;
-        }
-        if (!ok || red[i].t_bases == 0) throw Panic("called `Option::unwrap()` on a `None` value (read_pos) for " + r.qname);
-        const int64_t qpos = (int64_t)red[i].q_bases - q_after - 1; // S and I count as read bases, H does not
-        s.q_st = lead_h + lead_s;
-        s.q_en = lead_h + 1 + qpos;
-        s.q_len = lead_h + (int64_t)r.l_seq + trail_h;
-        s.strand = (r.flag & 16) ? '-' : '+';
-        if (r.flag & 16) { // bamstats.rs:203-207
-            const int64_t t = s.q_st;
-            s.q_st = s.q_len - s.q_en;
-            s.q_en = s.q_len - t;
-        }
-        s.equal = red[i].equal, s.diff = red[i].diff, s.ins = red[i].ins, s.del = red[i].del, s.matches = red[i].matches;
-        s.ins_events = red[i].ins_events, s.del_events = red[i].del_events;
-        s.id_by_all = red[i].id_by_all, s.id_by_events = red[i].id_by_events, s.id_by_matches = red[i].id_by_matches;
-        if (s.equal == 0 && s.matches > 0 && r.has_md) { // bamstats.rs:129-142
-            uint32_t m4[4];
-            parse_md_for_stats(r.md, m4);
-            if (m4[0] + m4[1] != s.diff) throw Panic("assertion failed: m_count + mm_count == stats.diff");
-            s.equal = m4[0];
-            s.diff = m4[1];
-            const volatile float e = (float)s.equal;
-            const volatile float num = 100.0f * e;
-            s.id_by_all = num / (float)(uint32_t)(s.equal + s.diff + s.del + s.ins);
-            s.id_by_events = num / (float)(uint32_t)(s.equal + s.diff + s.del_events + s.ins_events);
-            s.id_by_matches = num / (float)(uint32_t)(s.equal + s.diff);
-        } else if (s.matches > 0 && !r.has_md) { // bamstats.rs:145-153 (once per such record, like the reference)
-            fprintf(stderr, "\r⚠ warning: cigar string contains 'M', assuming mismatch since there is no MD tag.");
-        }
+        aln_stats_record(ops.data() + r.cig0, r.ncig, red[i], r.pos, r.flag, r.l_seq, r.has_md, r.md, r.qname, s);
     } catch (const Panic &e) { // the reference has printed the records before this one (main.rs:71-76)
         out.resize(i);
         pending = e.what();
@@ -2590,6 +2582,407 @@ std::vector<Stats> cigar_stats_bam(Engine &eng, const std::string &path, std::st
         *trailing_panic = pending;
     }
     return out;
+}
+
+// ---- SAM input of `rb stats` (main.rs:60-77 reads "sam/bam/cram" through htslib): the text is split on the host, the CIGAR text, the
+// MD strings and the spans are the device's (rb_dev_parse_cigars, rb_dev_scan_records, rb_dev_parse_md, rb_dev_aln_stats) ----
+int stats_input_kind(const std::string &path) {
+    char m[4] = {0, 0, 0, 0};
+    size_t got = 0;
+    if (path == "-") {
+        const std::string &all = stdin_text();
+        got = std::min<size_t>(4, all.size());
+        memcpy(m, all.data(), got);
+    } else {
+        gzFile f = gzopen(path.c_str(), "rb"); // (plain bytes pass through; gzip and BGZF are inflated)
+        if (!f) throw Panic("Failed to open " + path); // main.rs:63
+        const int r = gzread(f, m, 4);
+        got = r > 0 ? (size_t)r : 0;
+        gzclose(f);
+    }
+    if (got == 4 && memcmp(m, "BAM\1", 4) == 0) return STATS_INPUT_BAM;
+    if (got == 4 && memcmp(m, "CRAM", 4) == 0) return STATS_INPUT_CRAM;
+    return STATS_INPUT_TEXT;
+}
+
+namespace {
+struct SamRec {
+    size_t line;               // 1-based line of the file
+    size_t qname, qname_n;     // extents in the text
+    size_t cig, cig_n;         // (CIGAR `*`: empty)
+    size_t md, md_n;
+    bool has_md, has_seq;      // has_seq: SEQ is not `*`
+    int32_t ref;
+    int64_t pos;               // 0-based
+    uint32_t flag, l_seq;
+};
+// the text of a SAM file: the @SQ lines' names and lengths, and the columns `rb stats` needs of every mapped record.  A record the
+// front refuses ends the list: the reference dies there (htslib's parser gives up on the line, or its behaviour is version-dependent
+// and nothing pins it -- DESIGN.md), so `refusal` carries the panic of the record that would be recs[recs.size()].
+struct SamFile {
+    TextBuf all;
+    std::vector<std::string> ref_nm;
+    std::vector<int64_t> ref_len;
+    std::vector<SamRec> recs;
+    std::string refusal;
+    std::string_view sv(size_t off, size_t n) const { return std::string_view(all.data() + off, n); }
+
+    // false: the text is not SAM (first byte not '@', first line of fewer than 11 columns)
+    bool load(const std::string &path) {
+        double tl = now_s();
+        all = read_text(path);
+        const std::string_view text(all.data(), all.size());
+        if (text.empty()) return false;
+        if (text[0] != '@') {
+            const size_t e = std::min(text.find('\n'), text.size());
+            if (std::count(text.begin(), text.begin() + (ptrdiff_t)e, '\t') < 10) return false;
+        }
+        const std::vector<std::pair<size_t, size_t>> lines = split_lines(text);
+        size_t first = 0; // the header: @ lines in front of the first record
+        std::unordered_map<std::string_view, int32_t> ref_id;
+        for (; first < lines.size() && lines[first].second && text[lines[first].first] == '@'; first++) {
+            const std::string_view ln = text.substr(lines[first].first, lines[first].second);
+            if (ln.substr(0, 4) != "@SQ\t") continue;
+            std::string_view nm;
+            int64_t len = 0;
+            for (size_t a = 4; a <= ln.size();) {
+                const size_t b = std::min(ln.find('\t', a), ln.size());
+                const std::string_view f = ln.substr(a, b - a);
+                if (f.substr(0, 3) == "SN:") nm = f.substr(3);
+                if (f.substr(0, 3) == "LN:") len = strtoll(std::string(f.substr(3)).c_str(), nullptr, 10);
+                a = b + 1;
+            }
+            ref_id.emplace(nm, (int32_t)ref_nm.size()); // (the first @SQ of a name counts)
+            ref_nm.emplace_back(nm);
+            ref_len.push_back(len);
+        }
+        lap("read + split lines", tl);
+        const size_t n_lines = lines.size() - first;
+        const unsigned T = parallel_chunk_count(n_lines);
+        std::vector<std::vector<SamRec>> part(T);
+        std::vector<std::string> refused(T);
+        parallel_chunks(n_lines, [&](unsigned t, size_t lo, size_t hi) {
+            part[t].reserve(hi - lo);
+            for (size_t i = first + lo; i < first + hi && refused[t].empty(); i++) {
+                const size_t a0 = lines[i].first, n = lines[i].second;
+                if (n == 0) continue; // (an empty line: htslib skips none, but a file's last line often is one)
+                const std::string where = "line " + std::to_string(i + 1) + ": ";
+                size_t col[12]; // starts of the first eleven columns, and of what is behind them
+                unsigned nc = 1;
+                col[0] = a0;
+                for (size_t a = a0; nc < 12;) {
+                    const void *q = memchr(all.data() + a, '\t', a0 + n - a);
+                    if (!q) break;
+                    a = (size_t)((const char *)q - all.data()) + 1;
+                    col[nc++] = a;
+                }
+                if (nc < 11) {
+                    refused[t] = where + "a SAM record of fewer than 11 columns";
+                    break;
+                }
+                const size_t line_end = a0 + n;
+                auto col_end = [&](unsigned c) { return c + 1 < nc ? col[c + 1] - 1 : line_end; };
+                auto token = [&](unsigned c) { return std::string(all.data() + col[c], col_end(c) - col[c]); };
+                SamRec r{};
+                r.line = i + 1;
+                r.qname = col[0], r.qname_n = col_end(0) - col[0];
+                {
+                    const std::string f = token(1); // htslib: strtol(.., 0)
+                    char *end = nullptr;
+                    const long v = strtol(f.c_str(), &end, 0);
+                    if (f.empty() || *end || v < 0 || v > 0xFFFF) {
+                        refused[t] = where + "FLAG '" + f + "' cannot be parsed";
+                        break;
+                    }
+                    r.flag = (uint32_t)v;
+                }
+                if (r.flag & 4) continue; // main.rs:73 is_unmapped
+                {
+                    const std::string_view nm = sv(col[2], col_end(2) - col[2]);
+                    auto it = ref_id.find(nm);
+                    if (nm == "*" || it == ref_id.end()) {
+                        refused[t] = where + "a mapped record whose RNAME '" + std::string(nm) + "' is not a reference of the @SQ lines";
+                        break;
+                    }
+                    r.ref = it->second;
+                }
+                {
+                    const std::string f = token(3);
+                    char *end = nullptr;
+                    const long long v = strtoll(f.c_str(), &end, 10);
+                    if (f.empty() || *end || v < 1) {
+                        refused[t] = where + "a mapped record with POS '" + f + "' (not a position of 1 or more)";
+                        break;
+                    }
+                    r.pos = (int64_t)v - 1;
+                }
+                r.cig = col[5], r.cig_n = col_end(5) - col[5];
+                if (r.cig_n == 1 && all.data()[r.cig] == '*') r.cig_n = 0;
+                const size_t seq_n = col_end(9) - col[9];
+                r.has_seq = !(seq_n == 1 && all.data()[col[9]] == '*');
+                r.l_seq = r.has_seq ? (uint32_t)seq_n : 0u;
+                for (size_t a = nc == 12 ? col[11] : line_end; a < line_end;) { // the optional fields (QUAL is only stepped over)
+                    const void *q = memchr(all.data() + a, '\t', line_end - a);
+                    const size_t b = q ? (size_t)((const char *)q - all.data()) : line_end;
+                    if (b - a >= 5 && !r.has_md && memcmp(all.data() + a, "MD:Z:", 5) == 0) r.has_md = true, r.md = a + 5, r.md_n = b - a - 5;
+                    if (b - a >= 6 && memcmp(all.data() + a, "CG:B:I", 6) == 0) {
+                        refused[t] = where + "the CG:B:I long-CIGAR convention is not read from SAM";
+                        break;
+                    }
+                    a = b + 1;
+                }
+                if (!refused[t].empty()) break;
+                part[t].push_back(r);
+            }
+        });
+        for (unsigned t = 0; t < T; t++) {
+            recs.insert(recs.end(), part[t].begin(), part[t].end());
+            if (!refused[t].empty()) { // the first chunk's refusal = the first refused line in file order
+                refusal = refused[t];
+                break;
+            }
+        }
+        lap("SAM columns", tl);
+        return true;
+    }
+    // htslib (sam_parse1): "CIGAR and query sequence are of different length"
+    std::string seq_refusal(const SamRec &r, uint64_t nc, uint64_t q_bases) const {
+        if (!r.has_seq || nc == 0 || q_bases == r.l_seq) return std::string();
+        return "line " + std::to_string(r.line) + ": CIGAR and query sequence are of different length";
+    }
+    void names(const SamRec &r, Stats &s) const {
+        s.r_nm = ref_nm[r.ref], s.r_len = ref_len[r.ref];
+        s.q_nm.assign(all.data() + r.qname, r.qname_n);
+    }
+    // the packed CIGAR of a record, parsed on the host; a length htslib refuses (2^28 and more) or a malformed string: the panic
+    void host_cigar(const SamRec &r, std::vector<uint32_t> &cg) const {
+        try {
+            parse_cigar(all.data() + r.cig, r.cig_n, cg);
+        } catch (const Panic &) {
+            throw Panic("line " + std::to_string(r.line) + ": the CIGAR cannot be parsed");
+        }
+        for (uint32_t w : cg)
+            if ((w & 15u) == RB_OP_CONT) throw Panic("line " + std::to_string(r.line) + ": a CIGAR operation of 2^28 bases or more");
+    }
+};
+
+// the record route's work for the records `which` of f (ascending): CIGAR text parsed on the host, rb_host_scan_records, the host's
+// parse_md_for_stats inside aln_stats_record.  out[k] / err[k]: the stats of which[k], or the panic it is.
+void sam_records_on_host(Engine &eng, const SamFile &f, const std::vector<size_t> &which, std::vector<Stats> &out, std::vector<std::string> &err) {
+    const size_t n = which.size();
+    out.assign(n, Stats()), err.assign(n, std::string());
+    std::vector<uint32_t> ops, cg;
+    std::vector<uint64_t> op_off(n + 1, 0), zero(n, 0);
+    for (size_t k = 0; k < n; k++) {
+        try {
+            f.host_cigar(f.recs[which[k]], cg);
+            ops.insert(ops.end(), cg.begin(), cg.end());
+        } catch (const Panic &e) {
+            err[k] = e.what();
+        }
+        op_off[k + 1] = ops.size();
+    }
+    ops.resize(ops.size() + 4, 0);
+    std::vector<uint8_t> strand(n, (uint8_t)'+');
+    std::vector<rb_reduce_row> red(n);
+    if (n)
+        eng.check(rb_host_scan_records(eng.ctx(), n, ops.data(), op_off.data(), zero.data(), zero.data(), zero.data(), zero.data(), strand.data(),
+                                       red.data(), nullptr),
+                  "rb_host_scan_records");
+    for (size_t k = 0; k < n; k++) {
+        if (!err[k].empty()) continue;
+        const SamRec &r = f.recs[which[k]];
+        const size_t nc = (size_t)(op_off[k + 1] - op_off[k]);
+        err[k] = f.seq_refusal(r, nc, red[k].q_bases);
+        if (!err[k].empty()) continue;
+        try {
+            f.names(r, out[k]);
+            aln_stats_record(ops.data() + op_off[k], nc, red[k], r.pos, r.flag, r.l_seq, r.has_md, r.has_md ? std::string(f.sv(r.md, r.md_n)) : std::string(),
+                             out[k].q_nm, out[k]);
+        } catch (const Panic &e) {
+            err[k] = e.what();
+        }
+    }
+}
+
+// the lines of the records in front of the first one that panics (out_text: chunks in output order), and that panic
+void sam_finish(const std::vector<Stats> &stats, const std::vector<std::string> &err, const std::string &refusal, bool qbed, std::vector<std::string> &out_text,
+                std::string &trailing_panic) {
+    size_t k = 0;
+    while (k < stats.size() && err[k].empty()) k++;
+    trailing_panic = k < stats.size() ? err[k] : refusal;
+    const unsigned TO = parallel_chunk_count(k);
+    out_text.assign(TO, std::string());
+    parallel_chunks(k, [&](unsigned t, size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) out_text[t] += cigar_stats_line(stats[i], qbed);
+    });
+}
+struct DevBufs { // device buffers of one route, freed on the way out
+    rb_ctx *ctx;
+    std::vector<void *> owned;
+    explicit DevBufs(rb_ctx *c) : ctx(c) {}
+    ~DevBufs() {
+        (void)rb_ctx_sync(ctx);
+        for (void *q : owned) (void)rb_dev_free(ctx, q);
+    }
+    template <typename T>
+    T *alloc(Engine &eng, size_t n) {
+        void *d = nullptr;
+        eng.check(rb_dev_alloc(ctx, n * sizeof(T) + 256, &d), "rb_dev_alloc");
+        owned.push_back(d);
+        return (T *)d;
+    }
+    template <typename T>
+    T *up(Engine &eng, const std::vector<T> &v) {
+        T *d = alloc<T>(eng, v.size());
+        if (!v.empty()) eng.check(rb_dev_upload(ctx, d, v.data(), v.size() * sizeof(T)), "rb_dev_upload");
+        return d;
+    }
+};
+} // namespace
+
+bool stats_sam_records(Engine &eng, const std::string &path, bool qbed, std::vector<std::string> &out_text, std::string &trailing_panic) {
+    SamFile f;
+    if (!f.load(path)) return false;
+    std::vector<size_t> which(f.recs.size());
+    for (size_t i = 0; i < which.size(); i++) which[i] = i;
+    std::vector<Stats> stats;
+    std::vector<std::string> err;
+    sam_records_on_host(eng, f, which, stats, err);
+    sam_finish(stats, err, f.refusal, qbed, out_text, trailing_panic);
+    return true;
+}
+
+bool stats_sam_text(Engine &eng, const std::string &path, bool qbed, std::vector<std::string> &out_text, std::string &trailing_panic) {
+    static const bool timing = getenv("RB_TIMING") != nullptr;
+    if (timing) fprintf(stderr, "[rb timing] stats_sam_text: rb_dev_parse_cigars, rb_dev_scan_records, rb_dev_parse_md, rb_dev_aln_stats\n");
+    SamFile f;
+    if (!f.load(path)) return false;
+    double tl = now_s();
+    rb_ctx *ctx = eng.ctx();
+    size_t n = 0;
+    std::vector<uint8_t> cig_status;
+    std::vector<rb_aln_row> rows;
+    std::vector<rb_reduce_row> red;
+    std::vector<uint64_t> op_off;
+    // One visit of the device for the records of f.  false: a CIGAR is one the reference dies on (malformed, or an operation htslib
+    // refuses); the list now ends in front of that record and the visit is made again -- its ops are not fit to be scanned.
+    auto device_pass = [&]() -> bool {
+        n = f.recs.size();
+        std::vector<uint64_t> cig_off(n + 1, 0), cig_end(n, 0), md_off(n, 0), md_end(n, 0);
+        std::vector<int64_t> pos(n);
+        std::vector<uint32_t> flag(n), l_seq(n);
+        std::vector<uint8_t> has_md(n);
+        uint64_t cig_bytes = 0;
+        for (size_t i = 0; i < n; i++) {
+            const SamRec &r = f.recs[i];
+            cig_off[i] = r.cig, cig_end[i] = r.cig + r.cig_n, cig_bytes += r.cig_n;
+            if (r.has_md) md_off[i] = r.md, md_end[i] = r.md + r.md_n; // (every record that has an MD: the strings need nothing of the scan)
+            pos[i] = r.pos, flag[i] = r.flag, l_seq[i] = r.l_seq, has_md[i] = r.has_md ? 1 : 0;
+        }
+        cig_status.assign(n ? n : 1, 0), rows.assign(n, rb_aln_row()), red.assign(n, rb_reduce_row()), op_off.assign(n + 1, 0);
+        if (n == 0) return true;
+        DevBufs d(ctx);
+        // 1. the text, once
+        uint8_t *d_text = d.alloc<uint8_t>(eng, f.all.size() + 32);
+        eng.check(rb_dev_upload(ctx, d_text, f.all.data(), f.all.size() + 32), "rb_dev_upload"); // (read_text leaves 32 zero bytes behind the text)
+        const uint64_t *d_coff = d.up(eng, cig_off), *d_cend = d.up(eng, cig_end), *d_moff = d.up(eng, md_off), *d_mend = d.up(eng, md_end);
+        const int64_t *d_pos = d.up(eng, pos);
+        const uint32_t *d_flag = d.up(eng, flag), *d_lseq = d.up(eng, l_seq);
+        const uint8_t *d_has = d.up(eng, has_md);
+        lap("H2D text + columns", tl);
+        // 2. CIGAR text -> packed ops
+        const uint64_t ops_cap = cig_bytes / 2 + 8;
+        uint64_t *d_opoff = d.alloc<uint64_t>(eng, n + 2);
+        uint32_t *d_ops = d.alloc<uint32_t>(eng, (size_t)ops_cap + 32);
+        uint8_t *d_cst = d.alloc<uint8_t>(eng, n + 1);
+        void *d_scr = d.alloc<uint8_t>(eng, rb_text_scratch_bytes(n));
+        eng.check(rb_dev_parse_cigars(ctx, d_text, d_coff, d_cend, n, d_opoff, d_ops, ops_cap, d_cst, d_scr), "rb_dev_parse_cigars");
+        eng.check(rb_dev_download(ctx, cig_status.data(), d_cst, n), "rb_dev_download");
+        eng.check(rb_dev_download(ctx, op_off.data(), d_opoff, (n + 1) * 8), "rb_dev_download");
+        for (size_t i = 0; i < n; i++)
+            if (cig_status[i] != RB_TEXT_OK) try {
+                std::vector<uint32_t> cg;
+                f.host_cigar(f.recs[i], cg);
+            } catch (const Panic &e) {
+                f.refusal = e.what();
+                f.recs.resize(i);
+                return false;
+            }
+        lap("parse cigars + status D2H", tl);
+        // 3. the record scan, coordinates zero as the BAM route passes them
+        uint64_t *d_zero = d.alloc<uint64_t>(eng, n);
+        uint8_t *d_strand = d.alloc<uint8_t>(eng, n);
+        eng.check(rb_dev_memset(ctx, d_zero, 0, n * 8), "rb_dev_memset");
+        eng.check(rb_dev_memset(ctx, d_strand, '+', n), "rb_dev_memset");
+        rb_batch_view v{};
+        v.n_rec = n, v.n_ops = op_off[n];
+        v.ops = d_ops, v.op_off = d_opoff;
+        v.t_st = v.t_en = v.q_st = v.q_en = d_zero;
+        v.strand = d_strand;
+        rb_reduce_row *d_red = d.alloc<rb_reduce_row>(eng, n);
+        eng.check(rb_dev_scan_records(ctx, &v, d_red, nullptr), "rb_dev_scan_records");
+        // 4. the MD strings  5. the spans
+        uint32_t *d_md = d.alloc<uint32_t>(eng, 4 * n);
+        uint8_t *d_mst = d.alloc<uint8_t>(eng, n + 1);
+        eng.check(rb_dev_parse_md(ctx, d_text, d_moff, d_mend, n, d_md, d_mst), "rb_dev_parse_md");
+        rb_aln_row *d_rows = d.alloc<rb_aln_row>(eng, n);
+        eng.check(rb_dev_aln_stats(ctx, &v, d_red, d_pos, d_flag, d_lseq, d_md, d_mst, d_has, d_rows), "rb_dev_aln_stats");
+        // 6. the rows (and what the front's last check needs)
+        eng.check(rb_dev_download(ctx, rows.data(), d_rows, n * sizeof(rb_aln_row)), "rb_dev_download");
+        eng.check(rb_dev_download(ctx, red.data(), d_red, n * sizeof(rb_reduce_row)), "rb_dev_download");
+        lap("scan, MD, spans + rows D2H", tl);
+        return true;
+    };
+    while (!device_pass()) {}
+    // the records the device leaves to the host: a CIGAR number or an MD number of ten or more digits
+    std::vector<size_t> left;
+    for (size_t i = 0; i < n; i++)
+        if (cig_status[i] != RB_TEXT_OK || (rows[i].status & RB_ALN_MD_STATUS)) left.push_back(i);
+    std::vector<Stats> left_stats;
+    std::vector<std::string> left_err;
+    if (!left.empty()) sam_records_on_host(eng, f, left, left_stats, left_err);
+    if (timing) fprintf(stderr, "[rb timing]   stats_sam_text: records left to the host %zu of %zu\n", left.size(), n);
+    // 7. the lines
+    std::vector<Stats> stats(n);
+    std::vector<std::string> err(n);
+    parallel_chunks(n, [&](unsigned, size_t lo, size_t hi) {
+        size_t li = (size_t)(std::lower_bound(left.begin(), left.end(), lo) - left.begin());
+        for (size_t i = lo; i < hi; i++) {
+            if (li < left.size() && left[li] == i) {
+                stats[i] = std::move(left_stats[li]), err[i] = std::move(left_err[li]);
+                li++;
+                continue;
+            }
+            const SamRec &r = f.recs[i];
+            const rb_aln_row &w = rows[i];
+            err[i] = f.seq_refusal(r, op_off[i + 1] - op_off[i], red[i].q_bases);
+            if (!err[i].empty()) continue;
+            Stats &s = stats[i];
+            f.names(r, s);
+            switch (w.status) {
+            case RB_ALN_OK: break;
+            case RB_ALN_PANIC_DEL_FIRST: err[i] = "read_pos: 'deletion' found before any operation describing read sequence (" + s.q_nm + ")"; break;
+            case RB_ALN_PANIC_HARDCLIP: err[i] = "read_pos: hard clip between operations (" + s.q_nm + ")"; break;
+            case RB_ALN_PANIC_MD_ASSERT: err[i] = "assertion failed: m_count + mm_count == stats.diff"; break;
+            default: err[i] = "called `Option::unwrap()` on a `None` value (read_pos) for " + s.q_nm; break;
+            }
+            if (w.status != RB_ALN_OK) continue;
+            s.r_st = r.pos, s.r_en = w.r_en, s.q_st = w.q_st, s.q_en = w.q_en, s.q_len = w.q_len;
+            s.strand = (r.flag & 16) ? '-' : '+';
+            s.equal = w.equal, s.diff = w.diff, s.ins = w.ins, s.del = w.del, s.matches = w.matches;
+            s.ins_events = w.ins_events, s.del_events = w.del_events;
+            s.id_by_all = w.id_by_all, s.id_by_events = w.id_by_events, s.id_by_matches = w.id_by_matches;
+        }
+    });
+    sam_finish(stats, err, f.refusal, qbed, out_text, trailing_panic);
+    size_t printed = 0; // bamstats.rs:145-153: once per such record the reference got to
+    while (printed < n && err[printed].empty()) printed++;
+    for (size_t i = 0; i < printed; i++)
+        if (!std::binary_search(left.begin(), left.end(), i) && (rows[i].flags & RB_ALN_WARN_M))
+            fprintf(stderr, "\r⚠ warning: cigar string contains 'M', assuming mismatch since there is no MD tag.");
+    lap("stats lines", tl);
+    return true;
 }
 
 std::string cigar_stats_header(bool qbed) {

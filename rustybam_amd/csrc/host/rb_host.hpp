@@ -181,6 +181,19 @@ void parse_md_for_stats(const std::string &md, uint32_t out[4]);
 // trailing_panic: where the reference panics part-way through the file (a broken record, read_pos), the stats of the records
 // before it come back and the panic message goes here (NULL: thrown instead) -- the reference has printed them by then
 std::vector<Stats> cigar_stats_bam(Engine &eng, const std::string &bam_path, std::string *trailing_panic = nullptr);
+// `rb stats <in>` without --paf reads "sam/bam/cram" in the reference (cli.rs:49-60).  stats_input_kind looks at the first four
+// (decompressed) bytes of the file, or of stdin -- which is read once and kept --: BAM\1, CRAM, or text.
+// stats_sam_text: SAM text in, stats lines out (chunks in output order, without the header) on the device: the text uploaded once,
+// rb_dev_parse_cigars on the CIGAR columns, rb_dev_scan_records, rb_dev_parse_md on the MD:Z: values of every record that has one,
+// rb_dev_aln_stats, the rows back, the lines assembled on all host cores.  stats_sam_records: the record route (RB_GENERAL_PATH=1):
+// CIGAR text parsed on the host, rb_host_scan_records, the host's parse_md_for_stats.  Both: false = the text is not SAM (its first
+// byte is not '@' and its first line has fewer than 11 columns), nothing was produced.  The lines of the records in front of the first
+// one the reference dies on come back, its panic in trailing_panic (empty: none).  RB_TIMING=1: stats_sam_text names itself, its laps
+// and how many records it left to the host (a CIGAR or MD number of ten or more digits) on stderr.
+enum { STATS_INPUT_BAM = 0, STATS_INPUT_TEXT = 1, STATS_INPUT_CRAM = 2 };
+int stats_input_kind(const std::string &path);
+bool stats_sam_text(Engine &eng, const std::string &path, bool qbed, std::vector<std::string> &out_text, std::string &trailing_panic);
+bool stats_sam_records(Engine &eng, const std::string &path, bool qbed, std::vector<std::string> &out_text, std::string &trailing_panic);
 std::string cigar_stats_header(bool qbed);              // bamstats.rs:225-236
 // bed::parse_region (bed.rs:88-131): "name:st-en", 1-based inclusive start -> 0-based half-open; id = the same text
 Region parse_region(const std::string &region);

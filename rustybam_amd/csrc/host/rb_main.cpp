@@ -37,7 +37,7 @@ static void lap(const char *what, double &t) {
 static int usage() {
     fprintf(stderr,
             "usage: rb [--bsearch modern|legacy] [--device N] [--gpus N] <subcommand> ...\n"
-            "  stats [-q|--qbed] [-p|--paf] <PAF or BAM>\n"
+            "  stats [-q|--qbed] [-p|--paf] <PAF, BAM or SAM>\n"
             "  liftover -b|--bed <BED> [-q|--qbed] [-l|--largest] [--break N] [--stats|--stats-qbed] [PAF]\n"
             "  break-paf [-m|--max-size 100] [--orient] [--paired-len L] [--aln A] [--query Q] [--stats|--stats-qbed] [PAF]\n"
             "  trim-paf [-m|--match-score 1] [-d|--diff-score 1] [-i|--indel-score 1] [-r|--remove-contained] [PAF]\n"
@@ -1002,9 +1002,18 @@ int main(int argc, char **argv) {
             rb::nucfreq_bam(eng, paf_path, rgns, small, [&](const std::string &t) { put(t); });
         } else if (cmd == "stats") {
             if (!g_worker.on) put(rb::cigar_stats_header(qbed)); // (`--gpus`: the parent has printed it)
-            if (!is_paf) { // BAM input (main.rs:60-77)
+            if (!is_paf) { // BAM or SAM input (main.rs:60-77: htslib reads "sam/bam/cram", cli.rs:49-60)
                 std::string panic;
-                for (const rb::Stats &s : rb::cigar_stats_bam(eng, paf_path, &panic)) put(rb::cigar_stats_line(s, qbed));
+                std::vector<std::string> text;
+                const int kind = rb::stats_input_kind(paf_path);
+                if (kind == rb::STATS_INPUT_CRAM) throw rb::Panic(paf_path + " is a CRAM file: rb stats reads BAM and SAM");
+                // SAM: the text route parses the CIGAR and MD text and walks the spans on the device; RB_GENERAL_PATH=1 takes the record route
+                if (kind == rb::STATS_INPUT_TEXT && (text_path ? rb::stats_sam_text(eng, paf_path, qbed, text, panic) : rb::stats_sam_records(eng, paf_path, qbed, text, panic))) {
+                    emit(text);
+                    lap("stats (SAM)", tl);
+                } else { // (text that is not SAM ends where it always did: "... is not a BAM file")
+                    for (const rb::Stats &s : rb::cigar_stats_bam(eng, paf_path, &panic)) put(rb::cigar_stats_line(s, qbed));
+                }
                 if (!panic.empty()) throw rb::Panic(panic);
             } else {
                 std::vector<std::string> text;

@@ -20,6 +20,7 @@
 // Roofline: 64 B per row read, 72 B per row written, 4 B per clip op (+ 16 B per descriptor).
 #include "rb_device.h"
 #include "rb_launch.h"
+#include "rb_ratio.h"
 #include <type_traits>
 
 #define RB_HS_ROW_STEP 64u   // ops per step of a row of 16 lanes (4 per lane)
@@ -179,10 +180,7 @@ __device__ __forceinline__ void rb_hs_finish(unsigned long long (*hist)[64], con
     w.matches = (uint32_t)L[RB_OP_M];
     w.ins_events = ins_events;
     w.del_events = del_events;
-    const float num = 100.0f * (float)w.equal; // bamstats.rs:138-142: (100.0 * equal as f32) / (u32 sum) as f32
-    w.id_by_all = num / (float)(uint32_t)(w.equal + w.diff + w.del + w.ins);
-    w.id_by_events = num / (float)(uint32_t)(w.equal + w.diff + w.del_events + w.ins_events);
-    w.id_by_matches = num / (float)(uint32_t)(w.equal + w.diff);
+    rb_identity_ratios(w); // bamstats.rs:138-142
     uint32_t st = RB_ST_OK;
     if (U > 0xFFFFFFFFull)
         st = RB_ST_PANIC_OVERFLOW;

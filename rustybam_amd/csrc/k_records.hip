@@ -11,6 +11,7 @@
 // Roofline: HBM read, 4 B per op + 48 B header per record; 128 B of rows written per record.
 #include "rb_device.h"
 #include "rb_launch.h"
+#include "rb_ratio.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -142,11 +143,7 @@ __device__ __forceinline__ void rb_scan_finish(const rb_scan_params &p, const ui
         w.matches = (uint32_t)L[RB_OP_M];
         w.ins_events = ins_events;
         w.del_events = del_events;
-        // bamstats.rs:138-142: (100.0 * equal as f32) / (u32 sum) as f32
-        const float num = 100.0f * (float)w.equal;
-        w.id_by_all = num / (float)(uint32_t)(w.equal + w.diff + w.del + w.ins);
-        w.id_by_events = num / (float)(uint32_t)(w.equal + w.diff + w.del_events + w.ins_events);
-        w.id_by_matches = num / (float)(uint32_t)(w.equal + w.diff);
+        rb_identity_ratios(w); // bamstats.rs:138-142
         uint32_t st = RB_ST_OK;
         if (U > 0xFFFFFFFFull)
             st = RB_ST_PANIC_OVERFLOW;

@@ -240,6 +240,32 @@ struct rb_hitstats_params {
 };
 extern "C" hipError_t rb_launch_hitstats(const rb_hitstats_params *p, hipStream_t stream);
 
+// ---- k_alnstats.hip: MD strings and query spans of alignment records ----
+struct rb_md_params {
+    uint64_t n;
+    const uint8_t *text;    // 16-byte aligned, readable to the next multiple of 16 behind the last string
+    const uint64_t *md_off; // [n] string r is text[md_off[r] .. md_end[r])
+    const uint64_t *md_end; // [n]
+    uint32_t *out;          // [4 n] OUT match_count, mismatch_count, deletion events, deletion bases (16-byte aligned)
+    uint8_t *status;        // [n] OUT RB_MD_*
+};
+struct rb_alnstats_params {
+    uint64_t n;
+    const uint32_t *ops;
+    const uint64_t *op_off;            // [n + 1]
+    const rb_reduce_row *reduce_rows;  // [n] the record scan's rows (coordinates zero: their status is not looked at)
+    const int64_t *pos;                // [n]
+    const uint32_t *flag, *l_seq;      // [n]
+    const uint32_t *md;                // [4 n] or NULL
+    const uint8_t *md_status, *has_md; // [n] or NULL
+    rb_aln_row *rows;                  // [n] OUT
+};
+extern "C" hipError_t rb_launch_parse_md(const rb_md_params *p, hipStream_t stream);
+extern "C" hipError_t rb_launch_aln_stats(const rb_alnstats_params *p, hipStream_t stream);
+extern "C" uint32_t rb_md_row_step(void);
+extern "C" uint32_t rb_md_wave_step(void);
+extern "C" uint32_t rb_md_row_max(void);
+
 // ---- k_rows_batch.hip: the hit rows of a clip call as a dense batch ----
 struct rb_rows_batch_params {
     const uint32_t *ops;      // the source batch's packed ops (descriptor rows point into them)
