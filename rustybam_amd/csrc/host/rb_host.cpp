@@ -2260,7 +2260,8 @@ void parse_md_for_stats(const std::string &md, uint32_t out[4]) { // regex (\d+)
 
 // bamstats::cigar_stats (bamstats.rs:129-142, :190-207) for one alignment, names apart: the record route's twin of rb_dev_aln_stats
 // (rb_k_aln_stats), from the same statement of the span rules (rb_span.h).  cg[nc]: the packed CIGAR, red: the record scan's row of
-// it.  Fills the coordinates, the strand and the counters of s; throws the reference's panic; prints its warning for M without MD.
+// it.  Fills the coordinates, the strand and the counters of s; throws the reference's panic; s.warn_m: M without MD, the caller prints
+// the reference's warning if the reference got as far as this record.
 static void aln_stats_record(const uint32_t *cg, size_t nc, const rb_reduce_row &red, int64_t pos, uint32_t flag, uint32_t l_seq, bool has_md,
                              const std::string &md, const std::string &qname, Stats &s) {
     const rb_span_ends sp = rb_span_ends_of(cg, nc, red.t_bases);
@@ -2298,9 +2299,10 @@ static void aln_stats_record(const uint32_t *cg, size_t nc, const rb_reduce_row 
         s.id_by_events = num / (float)(uint32_t)(s.equal + s.diff + s.del_events + s.ins_events);
         s.id_by_matches = num / (float)(uint32_t)(s.equal + s.diff);
     } else if (s.matches > 0 && !has_md) { // bamstats.rs:145-153 (once per such record, like the reference)
-        fprintf(stderr, "\r⚠ warning: cigar string contains 'M', assuming mismatch since there is no MD tag.");
+        s.warn_m = true;
     }
 }
+static void warn_m_without_md() { fprintf(stderr, "\r⚠ warning: cigar string contains 'M', assuming mismatch since there is no MD tag."); }
 
 namespace {
 struct BamRec {
@@ -2572,6 +2574,7 @@ std::vector<Stats> cigar_stats_bam(Engine &eng, const std::string &path, std::st
         s.r_len = (r.ref_id >= 0 && (uint32_t)r.ref_id < n_ref) ? ref_len[r.ref_id] : 0;
         s.q_nm = r.qname;
         aln_stats_record(ops.data() + r.cig0, r.ncig, red[i], r.pos, r.flag, r.l_seq, r.has_md, r.md, r.qname, s);
+        if (s.warn_m) warn_m_without_md();
     } catch (const Panic &e) { // the reference has printed the records before this one (main.rs:71-76)
         out.resize(i);
         pending = e.what();
@@ -2805,7 +2808,8 @@ void sam_records_on_host(Engine &eng, const SamFile &f, const std::vector<size_t
     }
 }
 
-// the lines of the records in front of the first one that panics (out_text: chunks in output order), and that panic
+// the lines of the records in front of the first one that panics (out_text: chunks in output order), and that panic; the warning once
+// for every M-without-MD record among them (the reference takes the records one after the other: it never sees those behind the panic)
 void sam_finish(const std::vector<Stats> &stats, const std::vector<std::string> &err, const std::string &refusal, bool qbed, std::vector<std::string> &out_text,
                 std::string &trailing_panic) {
     size_t k = 0;
@@ -2816,6 +2820,8 @@ void sam_finish(const std::vector<Stats> &stats, const std::vector<std::string> 
     parallel_chunks(k, [&](unsigned t, size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; i++) out_text[t] += cigar_stats_line(stats[i], qbed);
     });
+    for (size_t i = 0; i < k; i++)
+        if (stats[i].warn_m) warn_m_without_md();
 }
 struct DevBufs { // device buffers of one route, freed on the way out
     rb_ctx *ctx;
@@ -2973,14 +2979,10 @@ bool stats_sam_text(Engine &eng, const std::string &path, bool qbed, std::vector
             s.equal = w.equal, s.diff = w.diff, s.ins = w.ins, s.del = w.del, s.matches = w.matches;
             s.ins_events = w.ins_events, s.del_events = w.del_events;
             s.id_by_all = w.id_by_all, s.id_by_events = w.id_by_events, s.id_by_matches = w.id_by_matches;
+            s.warn_m = (w.flags & RB_ALN_WARN_M) != 0;
         }
     });
     sam_finish(stats, err, f.refusal, qbed, out_text, trailing_panic);
-    size_t printed = 0; // bamstats.rs:145-153: once per such record the reference got to
-    while (printed < n && err[printed].empty()) printed++;
-    for (size_t i = 0; i < printed; i++)
-        if (!std::binary_search(left.begin(), left.end(), i) && (rows[i].flags & RB_ALN_WARN_M))
-            fprintf(stderr, "\r⚠ warning: cigar string contains 'M', assuming mismatch since there is no MD tag.");
     lap("stats lines", tl);
     return true;
 }

@@ -44,6 +44,7 @@ struct Stats {
     char strand = '+';
     uint32_t equal = 0, diff = 0, ins = 0, del = 0, matches = 0, ins_events = 0, del_events = 0;
     float id_by_all = 0, id_by_events = 0, id_by_matches = 0;
+    bool warn_m = false; // an alignment record with M and no MD tag: the reference warns when it gets to it (bamstats.rs:145-153)
 };
 
 class Engine { // one rb_ctx

@@ -5,6 +5,7 @@ A record is dict(name, ref (index into refs, -1: unmapped), pos (0-based), flag,
 nm (int or None)).  refs is [(name, length)].  The models know nothing of the product's code: test_sam_inputs.py holds them to the oracle."""
 import gzip
 import struct
+import zlib
 
 import numpy as np
 
@@ -220,6 +221,21 @@ def bam_bytes(refs, recs):
 def write_bam(path, refs, recs):
     with gzip.open(path, "wb", compresslevel=1) as f:
         f.write(bam_bytes(refs, recs))
+
+
+def bgzf_bytes(data, sizes=(0xFF00,)):
+    """the data as BGZF blocks (SAM spec 4.1: gzip members that carry their own size in a BC subfield) of the given uncompressed sizes in
+    turn, and the empty end-of-file block"""
+    out, at, k = bytearray(), 0, 0
+    while True:
+        chunk = data[at:at + sizes[k % len(sizes)]]
+        co = zlib.compressobj(1, zlib.DEFLATED, -15)
+        body = co.compress(chunk) + co.flush()
+        assert len(body) + 26 <= 0x10000
+        out += struct.pack("<4BI2BH2BHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, len(body) + 25) + body + struct.pack("<II", zlib.crc32(chunk), len(chunk))
+        if not chunk:
+            return bytes(out)
+        at, k = at + len(chunk), k + 1
 
 
 def sam_line(refs, r):
