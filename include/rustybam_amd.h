@@ -26,6 +26,7 @@
  *                            break_paf_on_indels returned (the second command of `rb liftover .. | rb stats --paf`)
  *   rb_dev_parse_md       <- bamstats::parse_md_for_stats                                 bamstats.rs:48-79
  *   rb_dev_aln_stats      <- bamstats::cigar_stats minus the names: query span, strand flip, MD refinement   bamstats.rs:129-142, :190-207
+ *   rb_dev_bam_records    <- what main.rs:60-77 takes from htslib's bam_read1 per record: fields, MD:Z, CIGAR (CG:B,I included)
  *
  * Conventions
  *   - Plain C types only.  Every `rb_dev_*` pointer argument is a DEVICE pointer (HBM) owned by
@@ -849,6 +850,52 @@ int rb_dev_aln_stats(rb_ctx *ctx, const rb_batch_view *batch, const rb_reduce_ro
 int rb_host_aln_stats(rb_ctx *ctx, uint64_t n, const uint32_t *ops, const uint64_t *op_off, const rb_reduce_row *reduce_rows, const int64_t *pos,
                       const uint32_t *flag, const uint32_t *l_seq, const uint32_t *md, const uint8_t *md_status, const uint8_t *has_md,
                       rb_aln_row *rows);
+
+/* ---- the records of a BAM stream (`rb stats in.bam`, main.rs:60-77): columns and packed ops from the inflated bytes ----------- *
+ *
+ * rb_dev_bam_records  <- htslib's bam_read1 bounds, its aux walk for MD:Z and CG:B,I, and its long-CIGAR convention, for n records
+ *                        where they lie in the inflated stream.  BAM's CIGAR words are the packed words of this interface; the call
+ *                        gathers them, from whatever byte the name's length leaves them at, into the aligned ops array.
+ *     data      device bytes of the inflated BAM stream; 16-byte aligned.  SLACK: the call reads whole aligned dwords and 16-byte
+ *               groups that hold at least one byte of a record, so data must be readable up to the next multiple of 16 behind the
+ *               last record's end; no byte outside [rec_off[r], rec_off[r] + rec_len[r]) is looked at, whatever it is.
+ *     rec_off   [n] the first byte behind record r's block_size field;  rec_len [n] u32 that block_size.  n counts ALL records,
+ *               mapped or not.  The hop from record to record (one read each, a serial chain) and the end of the stream are the host's.
+ *     One entry per input record, no compaction -- the columns as rb_dev_scan_records / rb_dev_parse_md / rb_dev_aln_stats take them:
+ *     tid [n] i32, pos [n] i64 (sign-extended), flag [n] u32, l_seq [n] u32, has_md [n] u8,
+ *     md_off / md_end [n] u64 into data (an empty MD: md_end == md_off with has_md = 1),
+ *     op_off [n + 1] u64 exclusive prefix of ops per record, ops u32 (capacity ops_cap, 16-byte aligned), status [n] u8:
+ *       RB_BAM_SHORT_BLOCK  block_size < 32
+ *       RB_BAM_NO_FIT       32 + l_read_name + 4 n_cigar + (l_seq + 1) / 2 + l_seq > block_size (in 64 bits)
+ *       RB_BAM_BAD_NAME     l_read_name == 0, or the name's last byte is not NUL
+ *     checked in this order, for unmapped records too.  A record whose status is not RB_BAM_OK has zero in every other column and 0 ops.
+ *     A record with flag & 4 has 0 ops, has_md = 0 and md_off = md_end = 0; tid, pos, flag and l_seq are reported.
+ *     The aux walk runs while p + 3 <= block_size: A c C take 1 byte, s S 2, i I f 4; Z / H run to the first NUL, or to the record's end
+ *     if there is none (an unterminated MD:Z is then the bytes up to the record's end); B stops the walk if its 5-byte head or its
+ *     array (element size * count, in 64 bits) runs past the record; any other type byte stops it.  What was found before a stop
+ *     counts.  The LAST MD:Z and the last CG:B,I win.  If a CG:B,I was found, n_cigar >= 1 and the first in-record word is S of length
+ *     l_seq, the record's ops are the tag's `count` words (that can be more than 65535); otherwise the in-record words.  Op nibbles
+ *     are copied as they are.
+ *     TRUNCATION, as rb_dev_parse_cigars: the call returns RB_OK whatever ops_cap is, every column and op_off are exact whatever it
+ *     is, nothing is written at or behind ops[ops_cap]: the caller detects a short ops[] by op_off[n] > ops_cap.  (bytes of data) / 4
+ *     is always enough: every word is four bytes of a record.
+ *     scratch   rb_bam_scratch_bytes(n) bytes.
+ *     Enqueues on the context's stream, does not synchronise.  n == 0 is valid (op_off[0] = 0).  Writes its outputs and scratch,
+ *     nothing else.  Two calls on the same input write the same bytes.
+ * rb_bam_shape: the kernels' thresholds, for tests (no device needed): out[0 .. 2] = bytes per step of a row of 16 lanes in the search
+ *     for a Z / H value's NUL, the longest aux area a row walks (longer ones take the whole wavefront), bytes per step of the
+ *     wavefront; out[3 .. 5] = the same of the copy, in ops: per step of a row, the longest CIGAR a row copies, per step of the wavefront.
+ * rb_host_bam_records: the same on HOST arrays (data [data_bytes], no slack or alignment asked of it; every record must lie inside it;
+ *     ops [ops_cap] caller-allocated): uploads, runs, downloads. */
+enum { RB_BAM_OK = 0, RB_BAM_SHORT_BLOCK = 1, RB_BAM_NO_FIT = 2, RB_BAM_BAD_NAME = 3 };
+size_t rb_bam_scratch_bytes(uint64_t n);
+void rb_bam_shape(uint32_t out[6]);
+int rb_dev_bam_records(rb_ctx *ctx, const uint8_t *data, const uint64_t *rec_off, const uint32_t *rec_len, uint64_t n, int32_t *tid, int64_t *pos,
+                       uint32_t *flag, uint32_t *l_seq, uint8_t *has_md, uint64_t *md_off, uint64_t *md_end, uint64_t *op_off, uint32_t *ops,
+                       uint64_t ops_cap, uint8_t *status, void *scratch);
+int rb_host_bam_records(rb_ctx *ctx, const uint8_t *data, uint64_t data_bytes, const uint64_t *rec_off, const uint32_t *rec_len, uint64_t n,
+                        int32_t *tid, int64_t *pos, uint32_t *flag, uint32_t *l_seq, uint8_t *has_md, uint64_t *md_off, uint64_t *md_end,
+                        uint64_t *op_off, uint32_t *ops, uint64_t ops_cap, uint8_t *status);
 
 /* ---- nucfreq: A/C/G/T counts at every covered reference position -----------------
  *

@@ -9,4 +9,5 @@ from .capi import (Engine, RbError, lib, lib_path, HIT_DT, NORM_DT, REDUCE_DT, C
                    BSEARCH_MODERN, BSEARCH_LEGACY, LIFT_EARLY_EXIT, LIFT_DESCRIPTORS, LIFT_FUSED_SCAN, LIFT_OP_STARTS, BREAK_ONE_WALK, TRIM_IN_PLACE, HIT_INSIDE, HIT_GENERIC, HIT_DESCRIPTOR, NF_COVERED, RD_OK, RD_FILTERED, RD_BAD_CIGAR, RD_SEQ_SHORT, exported_symbols, declared_symbols,
                    PAIRS_INFO_DT, PAIRS_ORIENT, PAIRS_FILTER, PAIRS_DECL_PANIC, PAIRS_DECL_KEY, PAIRS_DECL_WRAP, PAIRS_DECL_ZERO_SPAN, pairs_shape, host_pairs_rows,
                    pairs_records_shape, host_pairs_records,
-                   ALN_DT, MD_OK, MD_UNUSUAL, ALN_OK, ALN_PANIC_DEL_FIRST, ALN_PANIC_HARDCLIP, ALN_PANIC_NONE, ALN_PANIC_MD_ASSERT, ALN_MD_STATUS, ALN_WARN_M, md_shape)
+                   ALN_DT, MD_OK, MD_UNUSUAL, ALN_OK, ALN_PANIC_DEL_FIRST, ALN_PANIC_HARDCLIP, ALN_PANIC_NONE, ALN_PANIC_MD_ASSERT, ALN_MD_STATUS, ALN_WARN_M, md_shape,
+                   BAM_OK, BAM_SHORT_BLOCK, BAM_NO_FIT, BAM_BAD_NAME, bam_shape)

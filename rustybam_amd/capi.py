@@ -53,6 +53,7 @@ assert ALN_DT.itemsize == 80
 MD_OK, MD_UNUSUAL = 0, 3  # rb_dev_parse_md: status
 ALN_OK, ALN_PANIC_DEL_FIRST, ALN_PANIC_HARDCLIP, ALN_PANIC_NONE, ALN_PANIC_MD_ASSERT, ALN_MD_STATUS = 0, 32, 33, 34, 35, 64  # rb_aln_row.status
 ALN_WARN_M = 1  # rb_aln_row.flags
+BAM_OK, BAM_SHORT_BLOCK, BAM_NO_FIT, BAM_BAD_NAME = 0, 1, 2, 3  # rb_dev_bam_records: status
 PAIRS_DECL_PANIC, PAIRS_DECL_KEY, PAIRS_DECL_WRAP, PAIRS_DECL_ZERO_SPAN = 1, 2, 4, 8  # rb_pairs_info.declined
 
 
@@ -138,6 +139,17 @@ def md_shape():
     (rb_md_shape: no device needed)"""
     out = (C.c_uint32 * 3)()
     f = lib().rb_md_shape
+    f.restype = None
+    f(out)
+    return tuple(int(x) for x in out)
+
+
+def bam_shape():
+    """rb_dev_bam_records' kernels (rb_bam_shape: no device needed): (bytes per step of a row of 16 lanes in the search for a NUL, longest
+    aux area a row walks, bytes per step of the wavefront; ops per step of a row in the copy, longest CIGAR a row copies, ops per step
+    of the wavefront)"""
+    out = (C.c_uint32 * 6)()
+    f = lib().rb_bam_shape
     f.restype = None
     f(out)
     return tuple(int(x) for x in out)
@@ -521,6 +533,74 @@ class Engine:
         rows = np.zeros(n, ALN_DT)
         self._chk(self.L.rb_host_aln_stats(self.ctx, C.c_uint64(n), _p(ops), _p(op_off), _p(red), *map(_p, cols), _p(rows)), "rb_host_aln_stats")
         return rows
+
+    def bam_scratch_bytes(self, n):
+        f = self.L.rb_bam_scratch_bytes
+        f.restype = C.c_size_t
+        return int(f(C.c_uint64(n)))
+
+    def dev_bam_records(self, data_ptr, rec_off_ptr, rec_len_ptr, n, tid_ptr, pos_ptr, flag_ptr, l_seq_ptr, has_md_ptr, md_off_ptr, md_end_ptr, op_off_ptr,
+                        ops_ptr, ops_cap, status_ptr, scratch_ptr):
+        """rb_dev_bam_records on device addresses; enqueues on the context's stream"""
+        v = C.c_void_p
+        self._chk(self.L.rb_dev_bam_records(self.ctx, v(data_ptr or 0), v(rec_off_ptr or 0), v(rec_len_ptr or 0), C.c_uint64(n), v(tid_ptr or 0),
+                                            v(pos_ptr or 0), v(flag_ptr or 0), v(l_seq_ptr or 0), v(has_md_ptr or 0), v(md_off_ptr or 0), v(md_end_ptr or 0),
+                                            v(op_off_ptr or 0), v(ops_ptr or 0), C.c_uint64(ops_cap), v(status_ptr or 0), v(scratch_ptr or 0)),
+                  "rb_dev_bam_records")
+
+    @staticmethod
+    def _bam_cols(n, guard, fill):
+        mk = (lambda k, dt: np.frombuffer(np.full((k + guard) * np.dtype(dt).itemsize, 0xA5, np.uint8).tobytes(), dt).copy()) if fill else \
+            (lambda k, dt: np.zeros(k, dt))
+        return dict(tid=mk(n, np.int32), pos=mk(n, np.int64), flag=mk(n, np.uint32), l_seq=mk(n, np.uint32), has_md=mk(n, np.uint8), md_off=mk(n, np.uint64),
+                    md_end=mk(n, np.uint64), op_off=mk(n + 1, np.uint64), status=mk(n, np.uint8))
+
+    def bam_records(self, data, rec_off, rec_len, ops_cap=None, guard=0, keep=False):
+        """rb_dev_bam_records on host arrays: data (bytes-like; padded here to the slack the call asks for with 0xA5, which is no NUL), the
+        records' places -> dict(tid, pos, flag, l_seq, has_md, md_off, md_end, status [n + guard], op_off [n + 1 + guard], ops u32
+        [ops_cap + guard]); ops_cap None: (bytes of data) / 4.  The `guard` entries behind every array were filled with 0xA5 before the
+        call, and so was all of ops.  keep: the device buffers stay (dict key "dev": name -> address, "free": call it when done) for
+        calls that go on with the columns where they lie."""
+        data = np.frombuffer(bytes(data), np.uint8)
+        n_bytes = len(data)
+        data = np.concatenate([data, np.full(-len(data) % 16, 0xA5, np.uint8)])
+        rec_off, rec_len = _arr(rec_off, np.uint64), _arr(rec_len, np.uint32)
+        n = len(rec_off)
+        cap = n_bytes // 4 if ops_cap is None else int(ops_cap)
+        out = self._bam_cols(n, guard, True)
+        out["ops"] = np.full(cap + guard, 0xA5A5A5A5, np.uint32)
+        names = ("tid", "pos", "flag", "l_seq", "has_md", "md_off", "md_end", "op_off", "ops", "status")
+        bufs = []
+        try:
+            d = {k: self._up(bufs, a) for k, a in (("data", data), ("rec_off", rec_off), ("rec_len", rec_len))}
+            d.update({k: self._up(bufs, out[k]) for k in names})
+            d["scratch"] = self._up(bufs, np.zeros(self.bam_scratch_bytes(n), np.uint8))
+            self.dev_bam_records(d["data"], d["rec_off"], d["rec_len"], n, *[d[k] for k in names[:9]], cap, d["status"], d["scratch"])
+            for k in names:
+                self._down(out[k], d[k])
+            self.sync()
+            if keep:
+                out["dev"], bufs_kept = d, list(bufs)
+                out["free"] = lambda: [self.dev_free(b) for b in bufs_kept]
+                bufs = []
+            return out
+        finally:
+            self.sync()
+            for b in bufs:
+                self.dev_free(b)
+
+    def host_bam_records(self, data, rec_off, rec_len, ops_cap=None):
+        """rb_host_bam_records -> the same dict without guards (ops [ops_cap], zero behind what the call wrote)"""
+        data = np.frombuffer(bytes(data), np.uint8)
+        rec_off, rec_len = _arr(rec_off, np.uint64), _arr(rec_len, np.uint32)
+        n = len(rec_off)
+        cap = len(data) // 4 if ops_cap is None else int(ops_cap)
+        out = self._bam_cols(n, 0, False)
+        out["ops"] = np.zeros(cap, np.uint32)
+        self._chk(self.L.rb_host_bam_records(self.ctx, _p(data), C.c_uint64(len(data)), _p(rec_off), _p(rec_len), C.c_uint64(n),
+                                             *[_p(out[k]) for k in ("tid", "pos", "flag", "l_seq", "has_md", "md_off", "md_end", "op_off", "ops")],
+                                             C.c_uint64(cap), _p(out["status"])), "rb_host_bam_records")
+        return out
 
     def rows_to_batch_scratch_bytes(self, n_rows):
         f = self.L.rb_rows_to_batch_scratch_bytes

@@ -2630,6 +2630,83 @@ extern "C" int rb_host_aln_stats(rb_ctx *ctx, uint64_t n, const uint32_t *ops, c
     return rc ? rc : rb_ctx_sync(ctx);
 }
 
+// ---- the records of an inflated BAM stream (k_bam.hip) -------------------------------------------------
+// scratch of rb_dev_bam_records: [where each record's words lie (n) u64][block sums of the scan]
+static size_t bam_src_bytes(uint64_t n) { return ((size_t)(n + 1) * 8 + 255) & ~(size_t)255; }
+extern "C" size_t rb_bam_scratch_bytes(uint64_t n) { return bam_src_bytes(n) + (rb_scan_block_sums_count(n) + 4) * 8; }
+extern "C" void rb_bam_shape(uint32_t out[6]) {
+    out[0] = rb_bam_aux_row_step(), out[1] = rb_bam_aux_row_max(), out[2] = rb_bam_aux_wave_step();
+    out[3] = rb_bam_copy_row_step(), out[4] = rb_bam_copy_row_max(), out[5] = rb_bam_copy_wave_step();
+}
+extern "C" int rb_dev_bam_records(rb_ctx *ctx, const uint8_t *data, const uint64_t *rec_off, const uint32_t *rec_len, uint64_t n, int32_t *tid,
+                                  int64_t *pos, uint32_t *flag, uint32_t *l_seq, uint8_t *has_md, uint64_t *md_off, uint64_t *md_end, uint64_t *op_off,
+                                  uint32_t *ops, uint64_t ops_cap, uint8_t *status, void *scratch) {
+    if (!ctx || !op_off) return RB_E_INVALID;
+    if (n && (!data || !rec_off || !rec_len || !tid || !pos || !flag || !l_seq || !has_md || !md_off || !md_end || !status || !scratch)) return RB_E_INVALID;
+    if (ops_cap && !ops) return RB_E_INVALID;
+    if ((((uintptr_t)data | (uintptr_t)ops) & 15u) != 0) return fail(ctx, RB_E_INVALID, "rb_dev_bam_records: data and ops must be 16-byte aligned");
+    if (((uintptr_t)scratch & 7u) != 0) return fail(ctx, RB_E_INVALID, "rb_dev_bam_records: scratch must be 8-byte aligned");
+    rb_bam_params p;
+    p.n = n;
+    p.data = data, p.rec_off = rec_off, p.rec_len = rec_len;
+    p.tid = tid, p.pos = pos, p.flag = flag, p.l_seq = l_seq, p.has_md = has_md, p.md_off = md_off, p.md_end = md_end;
+    p.op_off = op_off, p.ops = ops, p.ops_cap = ops_cap, p.status = status;
+    p.src = (uint64_t *)scratch;
+    HIPCHK(ctx, rb_fill_async(op_off + n, 0, 8, ctx->stream));
+    if (n == 0) return RB_OK;
+    HIPCHK(ctx, rb_launch_bam_peek(&p, ctx->stream));
+    HIPCHK(ctx, rb_launch_exclusive_scan(op_off, n, (uint64_t *)((uint8_t *)scratch + bam_src_bytes(n)), nullptr, ctx->stream));
+    HIPCHK(ctx, rb_launch_bam_copy(&p, ctx->stream));
+    return RB_OK;
+}
+extern "C" int rb_host_bam_records(rb_ctx *ctx, const uint8_t *data, uint64_t data_bytes, const uint64_t *rec_off, const uint32_t *rec_len, uint64_t n,
+                                   int32_t *tid, int64_t *pos, uint32_t *flag, uint32_t *l_seq, uint8_t *has_md, uint64_t *md_off, uint64_t *md_end,
+                                   uint64_t *op_off, uint32_t *ops, uint64_t ops_cap, uint8_t *status) {
+    if (!ctx || !op_off || (data_bytes && !data) || (ops_cap && !ops)) return RB_E_INVALID;
+    if (n && (!rec_off || !rec_len || !tid || !pos || !flag || !l_seq || !has_md || !md_off || !md_end || !status)) return RB_E_INVALID;
+    for (uint64_t r = 0; r < n; r++)
+        if (rec_off[r] > data_bytes || rec_len[r] > data_bytes - rec_off[r]) return fail(ctx, RB_E_INVALID, "record %llu: outside the data", (unsigned long long)r);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBatch b(ctx);
+    uint8_t *d_data = nullptr, *d_has = nullptr, *d_status = nullptr, *d_scr = nullptr;
+    const uint64_t *d_roff = nullptr;
+    const uint32_t *d_rlen = nullptr;
+    int32_t *d_tid = nullptr;
+    int64_t *d_pos = nullptr;
+    uint32_t *d_flag = nullptr, *d_lseq = nullptr, *d_ops = nullptr;
+    uint64_t *d_moff = nullptr, *d_mend = nullptr, *d_opoff = nullptr;
+    int rc = b.alloc((size_t)data_bytes + 32, &d_data); // (the slack the device call asks for)
+    if (!rc && data_bytes) rc = rb_dev_upload(ctx, d_data, data, (size_t)data_bytes);
+    if (!rc) rc = b.up(rec_off, (size_t)n, &d_roff);
+    if (!rc) rc = b.up(rec_len, (size_t)n, &d_rlen);
+    if (!rc) rc = b.alloc((size_t)n + 1, &d_tid);
+    if (!rc) rc = b.alloc((size_t)n + 1, &d_pos);
+    if (!rc) rc = b.alloc((size_t)n + 1, &d_flag);
+    if (!rc) rc = b.alloc((size_t)n + 1, &d_lseq);
+    if (!rc) rc = b.alloc((size_t)n + 1, &d_has);
+    if (!rc) rc = b.alloc((size_t)n + 1, &d_moff);
+    if (!rc) rc = b.alloc((size_t)n + 1, &d_mend);
+    if (!rc) rc = b.alloc((size_t)n + 2, &d_opoff);
+    if (!rc) rc = b.alloc((size_t)ops_cap + 4, &d_ops);
+    if (!rc) rc = b.alloc((size_t)n + 1, &d_status);
+    if (!rc) rc = b.alloc(rb_bam_scratch_bytes(n), &d_scr);
+    if (!rc) rc = rb_dev_bam_records(ctx, d_data, d_roff, d_rlen, n, d_tid, d_pos, d_flag, d_lseq, d_has, d_moff, d_mend, d_opoff, d_ops, ops_cap, d_status, d_scr);
+    if (!rc && n) rc = rb_dev_download(ctx, tid, d_tid, (size_t)n * 4);
+    if (!rc && n) rc = rb_dev_download(ctx, pos, d_pos, (size_t)n * 8);
+    if (!rc && n) rc = rb_dev_download(ctx, flag, d_flag, (size_t)n * 4);
+    if (!rc && n) rc = rb_dev_download(ctx, l_seq, d_lseq, (size_t)n * 4);
+    if (!rc && n) rc = rb_dev_download(ctx, has_md, d_has, (size_t)n);
+    if (!rc && n) rc = rb_dev_download(ctx, md_off, d_moff, (size_t)n * 8);
+    if (!rc && n) rc = rb_dev_download(ctx, md_end, d_mend, (size_t)n * 8);
+    if (!rc && n) rc = rb_dev_download(ctx, status, d_status, (size_t)n);
+    if (!rc) rc = rb_dev_download(ctx, op_off, d_opoff, ((size_t)n + 1) * 8);
+    if (!rc) {
+        const uint64_t got = op_off[n] < ops_cap ? op_off[n] : ops_cap;
+        if (got) rc = rb_dev_download(ctx, ops, d_ops, (size_t)got * 4);
+    }
+    return rc ? rc : rb_ctx_sync(ctx);
+}
+
 // ---- the hit rows of a clip call as a dense batch (k_rows_batch.hip) ----------------------------------
 // scratch of rb_dev_rows_to_batch: [ops per row (n_rows + 1) u64][1 per OK row (n_rows + 1) u64][block sums of the scans]
 static size_t rtb_cnt_bytes(uint64_t n_rows) { return ((size_t)(n_rows + 1) * 8 + 255) & ~(size_t)255; }

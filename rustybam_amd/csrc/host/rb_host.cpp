@@ -2460,10 +2460,8 @@ bool bam_next(BamStream &f, std::vector<uint8_t> &rec) {
     f.exact(rec.data(), bs);
     return true;
 }
-} // namespace
-
-std::vector<Stats> cigar_stats_bam(Engine &eng, const std::string &path, std::string *trailing_panic) {
-    BamStream f(path);
+// the header of the stream: magic, the SAM text (stepped over), the references' names and lengths; f stands at the first record
+void bam_header(BamStream &f, const std::string &path, std::vector<std::string> &ref_nm, std::vector<uint32_t> &ref_len) {
     uint8_t h8[8] = {0}, b4[4] = {0};
     if (!gz_exact(f, h8, 8) || memcmp(h8, "BAM\1", 4) != 0) throw Panic(path + " is not a BAM file");
     if (le32(h8 + 4) > f.n - f.pos) throw Panic("truncated BAM header in " + path); // (sizes are checked before they size anything)
@@ -2471,8 +2469,8 @@ std::vector<Stats> cigar_stats_bam(Engine &eng, const std::string &path, std::st
     bam_need(f, b4, 4, path);
     const uint32_t n_ref = le32(b4);
     if ((uint64_t)n_ref * 8 > f.n - f.pos) throw Panic("truncated BAM header in " + path);
-    std::vector<std::string> ref_nm(n_ref);
-    std::vector<uint32_t> ref_len(n_ref);
+    ref_nm.assign(n_ref, std::string());
+    ref_len.assign(n_ref, 0u);
     for (uint32_t i = 0; i < n_ref; i++) {
         bam_need(f, b4, 4, path);
         if (le32(b4) > f.n - f.pos) throw Panic("truncated BAM header in " + path);
@@ -2482,6 +2480,15 @@ std::vector<Stats> cigar_stats_bam(Engine &eng, const std::string &path, std::st
         bam_need(f, b4, 4, path);
         ref_len[i] = le32(b4);
     }
+}
+} // namespace
+
+std::vector<Stats> cigar_stats_bam(Engine &eng, const std::string &path, std::string *trailing_panic) {
+    BamStream f(path);
+    std::vector<std::string> ref_nm;
+    std::vector<uint32_t> ref_len;
+    bam_header(f, path, ref_nm, ref_len);
+    const uint32_t n_ref = (uint32_t)ref_nm.size();
     // decode every mapped record; cigars go straight into one packed array (BAM's encoding IS the ABI's)
     std::vector<BamRec> recs;
     std::vector<uint32_t> ops;
@@ -2985,6 +2992,181 @@ bool stats_sam_text(Engine &eng, const std::string &path, bool qbed, std::vector
     sam_finish(stats, err, f.refusal, qbed, out_text, trailing_panic);
     lap("stats lines", tl);
     return true;
+}
+
+// ---- BAM input of `rb stats` on the device: the inflated stream uploaded once, the records decoded where they lie (rb_dev_bam_records),
+// then the SAM route's three calls on its columns.  The host keeps the hop from record to record and the names. ----
+void stats_bam_text(Engine &eng, const std::string &path, bool qbed, std::vector<std::string> &out_text, std::string &trailing_panic) {
+    static const bool timing = getenv("RB_TIMING") != nullptr;
+    if (timing) fprintf(stderr, "[rb timing] stats_bam_text: rb_dev_bam_records, rb_dev_scan_records, rb_dev_parse_md, rb_dev_aln_stats\n");
+    double tl = now_s();
+    BamStream f(path);
+    lap("read + inflate", tl);
+    std::vector<std::string> ref_nm;
+    std::vector<uint32_t> ref_len;
+    bam_header(f, path, ref_nm, ref_len);
+    const uint32_t n_ref = (uint32_t)ref_nm.size();
+    // the hop: one read per record.  A file that ends inside a record is the panic of the record that would come next (bam_next)
+    std::vector<uint64_t> rec_off;
+    std::vector<uint32_t> rec_len;
+    std::string pending;
+    while (f.pos < f.n) {
+        if (f.n - f.pos < 4) {
+            pending = "truncated BAM file (inside a block_size field)";
+            break;
+        }
+        const uint32_t bs = le32(f.buf.get() + f.pos);
+        if (bs > f.n - f.pos - 4) {
+            pending = "truncated BAM file (inside a record)";
+            break;
+        }
+        rec_off.push_back(f.pos + 4), rec_len.push_back(bs);
+        f.pos += 4 + (size_t)bs;
+    }
+    const size_t n = rec_off.size();
+    lap("record hop", tl);
+    out_text.clear();
+    trailing_panic = pending;
+    if (n == 0) return;
+    rb_ctx *ctx = eng.ctx();
+    std::vector<uint8_t> status(n);
+    std::vector<int32_t> tid(n);
+    std::vector<int64_t> pos(n);
+    std::vector<uint32_t> flag(n);
+    std::vector<rb_aln_row> rows(n);
+    std::vector<uint64_t> op_off, md_off, md_end; // (downloaded only if a record is left to the host)
+    DevBufs d(ctx);
+    // 1. the stream, once
+    uint8_t *d_data = d.alloc<uint8_t>(eng, f.n + 32);
+    eng.check(rb_dev_upload(ctx, d_data, f.buf.get(), f.n), "rb_dev_upload");
+    const uint64_t *d_roff = d.up(eng, rec_off);
+    const uint32_t *d_rlen = d.up(eng, rec_len);
+    lap("H2D stream + record places", tl);
+    // 2. the records: columns and packed ops
+    const uint64_t ops_cap = f.n / 4 + 8;
+    int32_t *d_tid = d.alloc<int32_t>(eng, n);
+    int64_t *d_pos = d.alloc<int64_t>(eng, n);
+    uint32_t *d_flag = d.alloc<uint32_t>(eng, n), *d_lseq = d.alloc<uint32_t>(eng, n);
+    uint8_t *d_has = d.alloc<uint8_t>(eng, n), *d_st = d.alloc<uint8_t>(eng, n);
+    uint64_t *d_moff = d.alloc<uint64_t>(eng, n), *d_mend = d.alloc<uint64_t>(eng, n), *d_opoff = d.alloc<uint64_t>(eng, n + 2);
+    uint32_t *d_ops = d.alloc<uint32_t>(eng, (size_t)ops_cap + 32);
+    void *d_scr = d.alloc<uint8_t>(eng, rb_bam_scratch_bytes(n));
+    eng.check(rb_dev_bam_records(ctx, d_data, d_roff, d_rlen, n, d_tid, d_pos, d_flag, d_lseq, d_has, d_moff, d_mend, d_opoff, d_ops, ops_cap, d_st, d_scr),
+              "rb_dev_bam_records");
+    uint64_t n_ops = 0;
+    eng.check(rb_dev_download(ctx, &n_ops, d_opoff + n, 8), "rb_dev_download");
+    eng.check(rb_dev_download(ctx, status.data(), d_st, n), "rb_dev_download");
+    eng.check(rb_dev_download(ctx, tid.data(), d_tid, n * 4), "rb_dev_download");
+    eng.check(rb_dev_download(ctx, pos.data(), d_pos, n * 8), "rb_dev_download");
+    eng.check(rb_dev_download(ctx, flag.data(), d_flag, n * 4), "rb_dev_download");
+    lap("bam records + columns D2H", tl);
+    // 3. the record scan, coordinates zero  4. the MD strings where they lie in the stream  5. the spans
+    uint64_t *d_zero = d.alloc<uint64_t>(eng, n);
+    uint8_t *d_strand = d.alloc<uint8_t>(eng, n);
+    eng.check(rb_dev_memset(ctx, d_zero, 0, n * 8), "rb_dev_memset");
+    eng.check(rb_dev_memset(ctx, d_strand, '+', n), "rb_dev_memset");
+    rb_batch_view v{};
+    v.n_rec = n, v.n_ops = n_ops;
+    v.ops = d_ops, v.op_off = d_opoff;
+    v.t_st = v.t_en = v.q_st = v.q_en = d_zero;
+    v.strand = d_strand;
+    rb_reduce_row *d_red = d.alloc<rb_reduce_row>(eng, n);
+    eng.check(rb_dev_scan_records(ctx, &v, d_red, nullptr), "rb_dev_scan_records");
+    uint32_t *d_md = d.alloc<uint32_t>(eng, 4 * n);
+    uint8_t *d_mst = d.alloc<uint8_t>(eng, n + 1);
+    eng.check(rb_dev_parse_md(ctx, d_data, d_moff, d_mend, n, d_md, d_mst), "rb_dev_parse_md");
+    rb_aln_row *d_rows = d.alloc<rb_aln_row>(eng, n);
+    eng.check(rb_dev_aln_stats(ctx, &v, d_red, d_pos, d_flag, d_lseq, d_md, d_mst, d_has, d_rows), "rb_dev_aln_stats");
+    // 6. the rows
+    eng.check(rb_dev_download(ctx, rows.data(), d_rows, n * sizeof(rb_aln_row)), "rb_dev_download");
+    lap("scan, MD, spans + rows D2H", tl);
+    auto mapped = [&](size_t i) { return status[i] == RB_BAM_OK && !(flag[i] & 4u); };
+    auto qname = [&](size_t i) { return std::string((const char *)f.buf.get() + rec_off[i] + 32); }; // (NUL-terminated: the record's status says so)
+    // the records the device leaves to the host: an MD number of ten or more digits.  Their ops, scan row and MD come back one by one.
+    std::vector<size_t> left;
+    for (size_t i = 0; i < n; i++)
+        if (mapped(i) && (rows[i].status & RB_ALN_MD_STATUS)) left.push_back(i);
+    std::vector<Stats> left_stats(left.size());
+    std::vector<std::string> left_err(left.size());
+    if (!left.empty()) {
+        op_off.resize(n + 1), md_off.resize(n), md_end.resize(n);
+        eng.check(rb_dev_download(ctx, op_off.data(), d_opoff, (n + 1) * 8), "rb_dev_download");
+        eng.check(rb_dev_download(ctx, md_off.data(), d_moff, n * 8), "rb_dev_download");
+        eng.check(rb_dev_download(ctx, md_end.data(), d_mend, n * 8), "rb_dev_download");
+        std::vector<uint32_t> cg;
+        for (size_t k = 0; k < left.size(); k++) {
+            const size_t i = left[k];
+            const size_t nc = (size_t)(op_off[i + 1] - op_off[i]);
+            cg.assign(nc + 1, 0u);
+            if (nc) eng.check(rb_dev_download(ctx, cg.data(), d_ops + op_off[i], nc * 4), "rb_dev_download");
+            rb_reduce_row red;
+            eng.check(rb_dev_download(ctx, &red, d_red + i, sizeof red), "rb_dev_download");
+            uint32_t l_seq = 0;
+            eng.check(rb_dev_download(ctx, &l_seq, d_lseq + i, 4), "rb_dev_download");
+            try {
+                aln_stats_record(cg.data(), nc, red, pos[i], flag[i], l_seq, true, std::string((const char *)f.buf.get() + md_off[i], (size_t)(md_end[i] - md_off[i])),
+                                 qname(i), left_stats[k]);
+            } catch (const Panic &e) {
+                left_err[k] = e.what();
+            }
+        }
+    }
+    if (timing) fprintf(stderr, "[rb timing]   stats_bam_text: records left to the host %zu of %zu\n", left.size(), n);
+    // 7. the lines: every chunk up to its first record the reference dies on
+    const unsigned T = parallel_chunk_count(n);
+    std::vector<std::string> text(T), err(T);
+    std::vector<size_t> warns(T, 0);
+    parallel_chunks(n, [&](unsigned t, size_t lo, size_t hi) {
+        size_t li = (size_t)(std::lower_bound(left.begin(), left.end(), lo) - left.begin());
+        for (size_t i = lo; i < hi && err[t].empty(); i++) {
+            switch (status[i]) {
+            case RB_BAM_OK: break;
+            case RB_BAM_SHORT_BLOCK: err[t] = "invalid BAM record: block_size < 32"; break;
+            case RB_BAM_NO_FIT: err[t] = "invalid BAM record: name, cigar and sequence do not fit the block"; break;
+            default: err[t] = "invalid BAM record: read name is not NUL-terminated"; break;
+            }
+            if (!mapped(i)) continue; // main.rs:73 is_unmapped (a broken record ends the chunk through err[t])
+            Stats s;
+            const bool known = tid[i] >= 0 && (uint32_t)tid[i] < n_ref;
+            s.r_nm = known ? ref_nm[tid[i]] : "*";
+            s.r_len = known ? ref_len[tid[i]] : 0;
+            s.q_nm = qname(i);
+            if (li < left.size() && left[li] == i) {
+                const std::string nm = std::move(s.q_nm), rn = std::move(s.r_nm);
+                const int64_t rl = s.r_len;
+                s = std::move(left_stats[li]), err[t] = std::move(left_err[li]);
+                s.q_nm = nm, s.r_nm = rn, s.r_len = rl;
+                li++;
+            } else {
+                const rb_aln_row &w = rows[i];
+                switch (w.status) {
+                case RB_ALN_OK: break;
+                case RB_ALN_PANIC_DEL_FIRST: err[t] = "read_pos: 'deletion' found before any operation describing read sequence (" + s.q_nm + ")"; break;
+                case RB_ALN_PANIC_HARDCLIP: err[t] = "read_pos: hard clip between operations (" + s.q_nm + ")"; break;
+                case RB_ALN_PANIC_MD_ASSERT: err[t] = "assertion failed: m_count + mm_count == stats.diff"; break;
+                default: err[t] = "called `Option::unwrap()` on a `None` value (read_pos) for " + s.q_nm; break;
+                }
+                s.r_st = pos[i], s.r_en = w.r_en, s.q_st = w.q_st, s.q_en = w.q_en, s.q_len = w.q_len;
+                s.strand = (flag[i] & 16) ? '-' : '+';
+                s.equal = w.equal, s.diff = w.diff, s.ins = w.ins, s.del = w.del, s.matches = w.matches;
+                s.ins_events = w.ins_events, s.del_events = w.del_events;
+                s.id_by_all = w.id_by_all, s.id_by_events = w.id_by_events, s.id_by_matches = w.id_by_matches;
+                s.warn_m = (w.flags & RB_ALN_WARN_M) != 0;
+            }
+            if (!err[t].empty()) break;
+            text[t] += cigar_stats_line(s, qbed);
+            if (s.warn_m) warns[t]++;
+        }
+    });
+    for (unsigned t = 0; t < T; t++) { // the first chunk's panic = the first such record in file order; the warning once per M-without-MD record in front of it
+        out_text.push_back(std::move(text[t]));
+        for (size_t k = 0; k < warns[t]; k++) warn_m_without_md();
+        if (!err[t].empty()) {
+            trailing_panic = err[t];
+            break;
+        }
+    }
+    lap("stats lines", tl);
 }
 
 std::string cigar_stats_header(bool qbed) {

@@ -195,6 +195,14 @@ enum { STATS_INPUT_BAM = 0, STATS_INPUT_TEXT = 1, STATS_INPUT_CRAM = 2 };
 int stats_input_kind(const std::string &path);
 bool stats_sam_text(Engine &eng, const std::string &path, bool qbed, std::vector<std::string> &out_text, std::string &trailing_panic);
 bool stats_sam_records(Engine &eng, const std::string &path, bool qbed, std::vector<std::string> &out_text, std::string &trailing_panic);
+// stats_bam_text: BAM in (a file or stdin, BGZF or plain gzip), stats lines out on the device: the stream inflated as cigar_stats_bam
+// does, the records hopped through on the host (one read each, and the two truncation panics), the stream uploaded once,
+// rb_dev_bam_records (fields, MD:Z and CG:B,I of the aux area, the CIGAR words gathered into aligned ops), rb_dev_scan_records,
+// rb_dev_parse_md on the MD values where they lie in the stream, rb_dev_aln_stats, the rows back, the lines assembled on all host cores
+// (query names from the host's copy, reference names from the header).  The lines of the mapped records in front of the first record the
+// reference dies on come back, its panic in trailing_panic.  A header that is broken throws, as cigar_stats_bam does.  RB_TIMING=1:
+// names itself, its laps and how many records it left to the host (an MD number of ten or more digits).
+void stats_bam_text(Engine &eng, const std::string &path, bool qbed, std::vector<std::string> &out_text, std::string &trailing_panic);
 std::string cigar_stats_header(bool qbed);              // bamstats.rs:225-236
 // bed::parse_region (bed.rs:88-131): "name:st-en", 1-based inclusive start -> 0-based half-open; id = the same text
 Region parse_region(const std::string &region);

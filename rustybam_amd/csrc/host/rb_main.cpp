@@ -1011,7 +1011,11 @@ int main(int argc, char **argv) {
                 if (kind == rb::STATS_INPUT_TEXT && (text_path ? rb::stats_sam_text(eng, paf_path, qbed, text, panic) : rb::stats_sam_records(eng, paf_path, qbed, text, panic))) {
                     emit(text);
                     lap("stats (SAM)", tl);
-                } else { // (text that is not SAM ends where it always did: "... is not a BAM file")
+                } else if (kind == rb::STATS_INPUT_BAM && text_path) { // BAM: the records are decoded on the device where they lie in the inflated stream
+                    rb::stats_bam_text(eng, paf_path, qbed, text, panic);
+                    emit(text);
+                    lap("stats (BAM)", tl);
+                } else { // RB_GENERAL_PATH=1: record by record on the host (text that is not SAM ends where it always did: "... is not a BAM file")
                     for (const rb::Stats &s : rb::cigar_stats_bam(eng, paf_path, &panic)) put(rb::cigar_stats_line(s, qbed));
                 }
                 if (!panic.empty()) throw rb::Panic(panic);

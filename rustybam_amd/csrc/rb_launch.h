@@ -266,6 +266,32 @@ extern "C" uint32_t rb_md_row_step(void);
 extern "C" uint32_t rb_md_wave_step(void);
 extern "C" uint32_t rb_md_row_max(void);
 
+// ---- k_bam.hip: the records of an inflated BAM stream as columns and packed ops ----
+struct rb_bam_params {
+    uint64_t n;
+    const uint8_t *data;     // 16-byte aligned, readable to the next multiple of 16 behind the last record
+    const uint64_t *rec_off; // [n] the first byte behind the record's block_size field
+    const uint32_t *rec_len; // [n] its block_size
+    int32_t *tid;            // [n] OUT
+    int64_t *pos;            // [n] OUT
+    uint32_t *flag, *l_seq;  // [n] OUT
+    uint8_t *has_md;         // [n] OUT
+    uint64_t *md_off, *md_end; // [n] OUT places in data
+    uint64_t *op_off;        // [n + 1] OUT ops per record (peek), then their exclusive prefix
+    uint32_t *ops;           // OUT (16-byte aligned)
+    uint64_t ops_cap;
+    uint8_t *status;         // [n] OUT RB_BAM_*
+    uint64_t *src;           // [n] scratch: where in data the record's words lie (in the record, or in its CG:B,I tag)
+};
+extern "C" hipError_t rb_launch_bam_peek(const rb_bam_params *p, hipStream_t stream);
+extern "C" hipError_t rb_launch_bam_copy(const rb_bam_params *p, hipStream_t stream);
+extern "C" uint32_t rb_bam_aux_row_step(void);
+extern "C" uint32_t rb_bam_aux_row_max(void);
+extern "C" uint32_t rb_bam_aux_wave_step(void);
+extern "C" uint32_t rb_bam_copy_row_step(void);
+extern "C" uint32_t rb_bam_copy_row_max(void);
+extern "C" uint32_t rb_bam_copy_wave_step(void);
+
 // ---- k_rows_batch.hip: the hit rows of a clip call as a dense batch ----
 struct rb_rows_batch_params {
     const uint32_t *ops;      // the source batch's packed ops (descriptor rows point into them)
