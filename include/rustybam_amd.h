@@ -952,6 +952,62 @@ int rb_dev_nucfreq(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, 
 int rb_host_nucfreq(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
                     const uint64_t *rg_en, uint32_t *counts, uint32_t *read_status, rb_nucfreq_counters *counters);
 
+/* ---- nucfreq: the lines printed on the device (k_nftext.hip) ----------------------------------------------------------
+ *
+ * rb_dev_nucfreq_text  <- impl Display for Nucfreq (nucfreq.rs:17-33) and the --small lines (nucfreq.rs:148-150), one line per
+ *                         covered position, from the counts where rb_dev_nucfreq left them.
+ *   counts    DEVICE, 16-byte aligned: the output of rb_dev_nucfreq, four u32 per position, RB_NF_COVERED in bit 31 of the A word
+ *   segments  n_seg of them (below 2^32), described by seven HOST arrays of n_seg entries that are consumed before the call returns:
+ *             segment s covers the positions seg_pos[s] + k, k < seg_n[s], whose counts start at counts[4 * (seg_cnt[s] + k)].
+ *             Segments are independent: they may overlap in counts, and seg_cnt need not ascend.  A segment's prefix is
+ *             strings[pre_off[s] .. + pre_len[s]), its suffix strings[suf_off[s] .. + suf_len[s]); strings is DEVICE memory.
+ *             (The segment tables are a few words per print piece and the call has to look at them -- the refusals below, the launch
+ *             size --: as host arrays it does so without waiting for the device.)
+ *   text      Only positions whose A word has RB_NF_COVERED set make a line, in position order.
+ *             RB_NFT_FULL:  prefix dec(p) TAB dec((uint32_t)(p + 1)) TAB dec(A & 0x7fffffff) TAB dec(C) TAB dec(G) TAB dec(T) suffix
+ *             RB_NFT_SMALL: dec(largest of the four) TAB dec(second largest) LF; prefix and suffix are not looked at, strings and
+ *                           their four arrays may be NULL
+ *             The header lines (`#chr\tstart...`, `#name\tpos\tid`) are the caller's: seg_first says where the second kind goes.
+ *   outputs   DEVICE: seg_text_off [n_seg + 1] exclusive prefix of the segments' bytes; seg_first [n_seg] the first covered position
+ *             of the segment, ~0 if it has none; seg_lines [n_seg] its lines; text (16-byte aligned; NULL: a sizes-only call) the
+ *             segments' lines back to back with no padding: a segment starts at the byte the one in front ended on.
+ *   scratch   DEVICE, rb_nucfreq_text_scratch_bytes(n_seg, sum of seg_n) bytes, 256-byte aligned
+ *   CONTRACT  The call enqueues on the context's stream and does not wait for it (the upload of the segment tables goes through the
+ *             context's page-locked chunks, as every rb_dev_upload does, and can wait for an earlier upload's copy to leave its chunk:
+ *             never for a kernel).  It writes its outputs and its scratch and nothing
+ *             else; two calls on the same input write the same bytes, whatever outputs and scratch held before.
+ *             TRUNCATION: the call returns RB_OK whatever text_cap is, and the three segment arrays are exact whatever it is: the caller
+ *             detects a short text[] by seg_text_off[n_seg] > text_cap.  Nothing is written at or behind text[text_cap].  Below it
+ *             every segment that ends at or in front of the last 16-byte boundary <= text_cap is printed whole; of the others any
+ *             byte may be missing (a 16-byte group that would reach behind text_cap is left out whole), and a byte that is there is
+ *             the right one.
+ *             RB_E_INVALID, before anything is enqueued: seg_pos[s] + seg_n[s] > 2^32; a prefix or suffix longer than 255 bytes
+ *             (RB_NFT_FULL); a mode that is neither; a NULL pointer that is needed; counts, text or scratch misaligned.
+ *             n_seg == 0 and seg_n[s] == 0 are valid.
+ * rb_nucfreq_text_shape: {positions per wavefront step, positions per workgroup, longest prefix, longest suffix} (no device needed).
+ * rb_host_nucfreq_text: rb_host_nucfreq with the lines instead of the counts.  Reads and regions as there; the segments as above with
+ *             seg_cnt relative to the layout rb_host_nucfreq gives counts (region r at the sum of en - st of the regions in front),
+ *             and strings a HOST array of strings_bytes bytes.  The counts never leave the device.  The refusals are those of
+ *             rb_host_nucfreq (unsorted, cap_overflow, depth > 65535: RB_E_INVALID, nothing is handed to sink); read_status [n_reads]
+ *             and counters come back as there.  The text is printed in runs of whole segments of at most 1 GiB and handed to sink in
+ *             segment order: segments [first_seg, first_seg + n_seg), seg_text_off [n_seg + 1] relative to text, seg_first [n_seg]; the
+ *             three pointers are valid until sink returns.  A single segment of more than 1 GiB of text gets a slab of its own size.
+ *             (RB_DEBUG_NFT_SLAB=<bytes> in the environment lowers the 1 GiB: the tests' way to several slabs at a small size.) */
+enum { RB_NFT_FULL = 0, RB_NFT_SMALL = 1 };
+size_t rb_nucfreq_text_scratch_bytes(uint64_t n_seg, uint64_t n_positions);
+void rb_nucfreq_text_shape(uint32_t out[4]);
+int rb_dev_nucfreq_text(rb_ctx *ctx, const uint32_t *counts, uint64_t n_seg, const uint64_t *seg_cnt, const uint64_t *seg_pos,
+                        const uint32_t *seg_n, const uint8_t *strings, const uint32_t *pre_off, const uint32_t *pre_len,
+                        const uint32_t *suf_off, const uint32_t *suf_len, int mode, uint64_t *seg_text_off, uint64_t *seg_first,
+                        uint64_t *seg_lines, uint8_t *text, uint64_t text_cap, void *scratch);
+int rb_host_nucfreq_text(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
+                         const uint64_t *rg_en, uint64_t n_seg, const uint64_t *seg_cnt, const uint64_t *seg_pos, const uint32_t *seg_n,
+                         const uint8_t *strings, uint64_t strings_bytes, const uint32_t *pre_off, const uint32_t *pre_len,
+                         const uint32_t *suf_off, const uint32_t *suf_len, int mode, uint32_t *read_status, rb_nucfreq_counters *counters,
+                         void (*sink)(void *user, uint64_t first_seg, uint64_t n_seg, const uint64_t *seg_text_off,
+                                      const uint64_t *seg_first, const uint8_t *text),
+                         void *user);
+
 /* ---- verification aid (tests, bench; not a reference function): digest of hit rows and their clipped CIGARs ---------------
  * *digest += sum over i < n_rows of mix(row i) * (2 * (row_base + i) + 1), wrapping u64 (the caller zeroes *digest).  mix covers
  * rec + rec_base, win, status and -- for RB_ST_OK rows -- the INSIDE flag, out_n, the coordinates, nmatch, aln_len and every op of

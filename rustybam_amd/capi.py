@@ -17,6 +17,7 @@ BREAK_ONE_WALK = 128  # rb_dev_break: the clip kernel finds the long indels itse
 HIT_INSIDE, HIT_GENERIC, HIT_DESCRIPTOR = 1, 2, 4
 NF_COVERED = 0x80000000
 RD_OK, RD_FILTERED, RD_BAD_CIGAR, RD_SEQ_SHORT = 0, 1, 2, 3
+NFT_FULL, NFT_SMALL = 0, 1  # rb_dev_nucfreq_text modes
 
 REDUCE_DT = np.dtype(
     [("t_bases", "<u8"), ("q_bases", "<u8"), ("nmatch", "<u4"), ("aln_len", "<u4"), ("equal", "<u4"),
@@ -129,6 +130,16 @@ def rows_to_batch_shape():
     (rb_rows_to_batch_shape: no device needed)"""
     out = (C.c_uint32 * 3)()
     f = lib().rb_rows_to_batch_shape
+    f.restype = None
+    f(out)
+    return tuple(int(x) for x in out)
+
+
+def nucfreq_text_shape():
+    """(positions per wavefront step, positions per workgroup, longest prefix, longest suffix) of rb_dev_nucfreq_text's kernel
+    (rb_nucfreq_text_shape: no device needed)"""
+    out = (C.c_uint32 * 4)()
+    f = lib().rb_nucfreq_text_shape
     f.restype = None
     f(out)
     return tuple(int(x) for x in out)
@@ -1012,6 +1023,62 @@ class Engine:
                                          _p(ctr)), "rb_host_nucfreq")
         return counts[:n_pos], status[:n], dict(max_depth=int(ctr[0]), n_covered=int(ctr[1]), n_bad=int(ctr[2]), unsorted=int(ctr[3]),
                                                     n_dropped=int(ctr[4]), cap_overflow=int(ctr[5]))
+
+    # ---- nucfreq: the lines (k_nftext.hip) ----
+    def nucfreq_text_scratch_bytes(self, n_seg, n_pos):
+        f = self.L.rb_nucfreq_text_scratch_bytes
+        f.restype = C.c_size_t
+        return int(f(C.c_uint64(n_seg), C.c_uint64(n_pos)))
+
+    def dev_nucfreq_text(self, counts, seg_cnt, seg_pos, seg_n, strings, pre_off, pre_len, suf_off, suf_len, mode, seg_text_off, seg_first,
+                         seg_lines, text, text_cap, scratch, check=True):
+        """counts, strings, the three segment outputs, text and scratch are device addresses (int); the seven segment arrays are host
+        arrays (or None).  Enqueues on the context's stream.  Returns the call's return value (check=False: without raising)."""
+        n_seg = len(seg_n) if seg_n is not None else 0
+        h = [None if a is None else _arr(a, dt) for a, dt in ((seg_cnt, np.uint64), (seg_pos, np.uint64), (seg_n, np.uint32), (pre_off, np.uint32),
+                                                              (pre_len, np.uint32), (suf_off, np.uint32), (suf_len, np.uint32))]
+        q = [None if a is None else _p(a) for a in h]
+        rc = self.L.rb_dev_nucfreq_text(self.ctx, C.c_void_p(counts), C.c_uint64(n_seg), q[0], q[1], q[2], C.c_void_p(strings), q[3], q[4], q[5], q[6],
+                                        C.c_int(mode), C.c_void_p(seg_text_off), C.c_void_p(seg_first), C.c_void_p(seg_lines), C.c_void_p(text),
+                                        C.c_uint64(text_cap), C.c_void_p(scratch))
+        if check:
+            self._chk(rc, "rb_dev_nucfreq_text")
+        return int(rc)
+
+    def nucfreq_text(self, tid, pos, flag, op_off, ops, l_seq, seq_off, seq, rg_tid, rg_st, rg_en, seg_cnt, seg_pos, seg_n, strings=b"",
+                     pre_off=None, pre_len=None, suf_off=None, suf_len=None, mode=NFT_FULL):
+        """Reads x regions as nucfreq(), the lines of the segments instead of the counts (rb_host_nucfreq_text).  Returns (slabs,
+        read_status, counters): slabs = [(first_seg, seg_text_off [n + 1], seg_first [n], text bytes)] in segment order."""
+        tid, pos, flag = _arr(tid, np.int32), _arr(pos, np.int64), _arr(flag, np.uint32)
+        op_off, ops = _arr(op_off, np.uint64), np.concatenate([_arr(ops, np.uint32), np.zeros(4, np.uint32)])
+        l_seq, seq_off = _arr(l_seq, np.uint32), _arr(seq_off, np.uint64)
+        seq = np.concatenate([_arr(seq, np.uint8), np.zeros(32, np.uint8)])
+        rg_tid, rg_st, rg_en = _arr(rg_tid, np.int32), _arr(rg_st, np.uint64), _arr(rg_en, np.uint64)
+        seg_cnt, seg_pos, seg_n = _arr(seg_cnt, np.uint64), _arr(seg_pos, np.uint64), _arr(seg_n, np.uint32)
+        fix = [None if a is None else _arr(a, np.uint32) for a in (pre_off, pre_len, suf_off, suf_len)]
+        sb = np.frombuffer(bytes(strings) + b"\0", np.uint8).copy()
+        n, nr = len(tid), len(rg_tid)
+
+        class View(C.Structure):
+            _fields_ = [("n_reads", C.c_uint64), ("ops", C.c_void_p), ("op_off", C.c_void_p), ("seq", C.c_void_p), ("seq_off", C.c_void_p),
+                        ("l_seq", C.c_void_p), ("tid", C.c_void_p), ("pos", C.c_void_p), ("flag", C.c_void_p)]
+        v = View(n, ops.ctypes.data, op_off.ctypes.data, seq.ctypes.data, seq_off.ctypes.data, l_seq.ctypes.data, tid.ctypes.data,
+                 pos.ctypes.data, flag.ctypes.data)
+        status = np.zeros(max(n, 1), np.uint32)
+        ctr = np.zeros(6, np.uint64)
+        slabs = []
+        SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8))
+
+        def sink(_user, first_seg, k, off, first, text):
+            o = np.ctypeslib.as_array(off, (k + 1,)).copy()
+            slabs.append((int(first_seg), o, np.ctypeslib.as_array(first, (k,)).copy(), C.string_at(text, int(o[k])) if int(o[k]) else b""))
+        cb = SINK(sink)
+        self._chk(self.L.rb_host_nucfreq_text(self.ctx, C.byref(v), C.c_uint64(nr), _p(rg_tid), _p(rg_st), _p(rg_en), C.c_uint64(len(seg_n)),
+                                              _p(seg_cnt), _p(seg_pos), _p(seg_n), _p(sb), C.c_uint64(len(strings)),
+                                              *[None if a is None else _p(a) for a in fix], C.c_int(mode), _p(status), _p(ctr), cb, None),
+                  "rb_host_nucfreq_text")
+        return slabs, status[:n], dict(max_depth=int(ctr[0]), n_covered=int(ctr[1]), n_bad=int(ctr[2]), unsorted=int(ctr[3]),
+                                       n_dropped=int(ctr[4]), cap_overflow=int(ctr[5]))
 
 
 def synth_n_ops(seed, first_record, n_rec, lo, hi):

@@ -3131,70 +3131,253 @@ extern "C" int rb_dev_nucfreq(rb_ctx *ctx, const rb_reads_view *reads, uint64_t 
     return RB_OK;
 }
 
-extern "C" int rb_host_nucfreq(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
-                               const uint64_t *rg_en, uint32_t *counts, uint32_t *read_status, rb_nucfreq_counters *counters) {
-    if (!ctx || !reads || !counters || (n_regions && (!rg_tid || !rg_st || !rg_en))) return RB_E_INVALID;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const uint64_t n = reads->n_reads;
-    std::vector<uint64_t> out_off(n_regions + 1, 0);
-    for (uint64_t r = 0; r < n_regions; r++) {
-        if (rg_en[r] < rg_st[r]) return fail(ctx, RB_E_INVALID, "region %llu ends before it starts", (unsigned long long)r);
-        out_off[r + 1] = out_off[r] + (rg_en[r] - rg_st[r]);
-    }
-    const uint64_t n_pos = out_off[n_regions];
-    if (n_pos && !counts) return RB_E_INVALID;
-    DevBatch b(ctx);
-    rb_reads_view d{};
-    d.n_reads = n;
-    int rc;
-    std::vector<uint64_t> opo, sqo; // (function scope: the asynchronous uploads below read them until the stream is synchronised)
-    if (n) {
-        // only the part of ops / seq these reads use goes up, offsets rebased
-        const uint64_t op0 = reads->op_off[0], op1 = reads->op_off[n];
-        uint64_t s0 = ~0ull, s1 = 0;
-        for (uint64_t i = 0; i < n; i++) {
-            const uint64_t a = reads->seq_off[i], e = a + ((uint64_t)reads->l_seq[i] + 1) / 2;
-            s0 = std::min(s0, a), s1 = std::max(s1, e);
+namespace {
+// the reads, the regions and the outputs of one rb_dev_nucfreq call made from host arrays, resident until this goes out of scope
+struct NfDev {
+    DevBatch b;
+    std::vector<uint64_t> out_off, opo, sqo; // (the asynchronous uploads read them until the stream is synchronised)
+    uint64_t n_pos = 0;
+    uint32_t *d_counts = nullptr;
+    explicit NfDev(rb_ctx *c) : b(c) {}
+    // where the regions' counts go: region r at the sum of en - st of the regions in front
+    int layout(rb_ctx *ctx, uint64_t n_regions, const uint64_t *rg_st, const uint64_t *rg_en) {
+        out_off.assign(n_regions + 1, 0);
+        for (uint64_t r = 0; r < n_regions; r++) {
+            if (rg_en[r] < rg_st[r]) return fail(ctx, RB_E_INVALID, "region %llu ends before it starts", (unsigned long long)r);
+            out_off[r + 1] = out_off[r] + (rg_en[r] - rg_st[r]);
         }
-        opo.resize(n + 1), sqo.resize(n);
-        for (uint64_t i = 0; i <= n; i++) opo[i] = reads->op_off[i] - op0;
-        for (uint64_t i = 0; i < n; i++) sqo[i] = reads->seq_off[i] - s0;
-        if ((rc = b.up(reads->ops + op0, (size_t)(op1 - op0), &d.ops))) return rc;
-        if ((rc = b.up(opo.data(), (size_t)n + 1, &d.op_off))) return rc;
-        {   // (32 readable bytes behind the last read, as the kernel asks)
-            uint8_t *dsq = nullptr;
-            if ((rc = b.alloc((size_t)(s1 - s0) + 32, &dsq))) return rc;
-            if (s1 > s0 && (rc = rb_dev_upload(ctx, dsq, reads->seq + s0, (size_t)(s1 - s0)))) return rc;
-            d.seq = dsq;
-        }
-        if ((rc = b.up(sqo.data(), (size_t)n, &d.seq_off))) return rc;
-        if ((rc = b.up(reads->l_seq, (size_t)n, &d.l_seq))) return rc;
-        if ((rc = b.up(reads->tid, (size_t)n, &d.tid))) return rc;
-        if ((rc = b.up(reads->pos, (size_t)n, &d.pos))) return rc;
-        if ((rc = b.up(reads->flag, (size_t)n, &d.flag))) return rc;
+        n_pos = out_off[n_regions];
+        return RB_OK;
     }
-    const int32_t *d_tid = nullptr;
-    const uint64_t *d_st = nullptr, *d_en = nullptr, *d_off = nullptr;
-    if ((rc = b.up(rg_tid, (size_t)n_regions, &d_tid))) return rc;
-    if ((rc = b.up(rg_st, (size_t)n_regions, &d_st))) return rc;
-    if ((rc = b.up(rg_en, (size_t)n_regions, &d_en))) return rc;
-    if ((rc = b.up(out_off.data(), (size_t)n_regions + 1, &d_off))) return rc;
-    uint32_t *d_counts = nullptr, *d_status = nullptr;
-    rb_nucfreq_counters *d_ctr = nullptr;
-    uint8_t *d_ws = nullptr;
-    if ((rc = b.alloc((size_t)n_pos * 4 + 4, &d_counts))) return rc;
-    if ((rc = b.alloc((size_t)n + 1, &d_status))) return rc;
-    if ((rc = b.alloc(1, &d_ctr))) return rc;
-    const size_t wsb = rb_nucfreq_workspace_bytes(n, n_regions, n_pos);
-    if ((rc = b.alloc(wsb, &d_ws))) return rc;
-    if ((rc = rb_dev_nucfreq(ctx, &d, n_regions, d_tid, d_st, d_en, d_off, n_pos, d_counts, d_status, d_ctr, d_ws, wsb))) return rc;
-    if ((rc = rb_dev_download(ctx, counters, d_ctr, sizeof(*counters)))) return rc;
-    if (read_status && n && (rc = rb_dev_download(ctx, read_status, d_status, (size_t)n * 4))) return rc;
-    if (n_pos && (rc = rb_dev_download(ctx, counts, d_counts, (size_t)n_pos * 16))) return rc;
+    // upload, rb_dev_nucfreq into d_counts, counters and read_status back (layout() first)
+    int run(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st, const uint64_t *rg_en,
+            uint32_t *read_status, rb_nucfreq_counters *counters) {
+        const uint64_t n = reads->n_reads;
+        rb_reads_view d{};
+        d.n_reads = n;
+        int rc;
+        if (n) {
+            // only the part of ops / seq these reads use goes up, offsets rebased
+            const uint64_t op0 = reads->op_off[0], op1 = reads->op_off[n];
+            uint64_t s0 = ~0ull, s1 = 0;
+            for (uint64_t i = 0; i < n; i++) {
+                const uint64_t a = reads->seq_off[i], e = a + ((uint64_t)reads->l_seq[i] + 1) / 2;
+                s0 = std::min(s0, a), s1 = std::max(s1, e);
+            }
+            opo.resize(n + 1), sqo.resize(n);
+            for (uint64_t i = 0; i <= n; i++) opo[i] = reads->op_off[i] - op0;
+            for (uint64_t i = 0; i < n; i++) sqo[i] = reads->seq_off[i] - s0;
+            if ((rc = b.up(reads->ops + op0, (size_t)(op1 - op0), &d.ops))) return rc;
+            if ((rc = b.up(opo.data(), (size_t)n + 1, &d.op_off))) return rc;
+            {   // (32 readable bytes behind the last read, as the kernel asks)
+                uint8_t *dsq = nullptr;
+                if ((rc = b.alloc((size_t)(s1 - s0) + 32, &dsq))) return rc;
+                if (s1 > s0 && (rc = rb_dev_upload(ctx, dsq, reads->seq + s0, (size_t)(s1 - s0)))) return rc;
+                d.seq = dsq;
+            }
+            if ((rc = b.up(sqo.data(), (size_t)n, &d.seq_off))) return rc;
+            if ((rc = b.up(reads->l_seq, (size_t)n, &d.l_seq))) return rc;
+            if ((rc = b.up(reads->tid, (size_t)n, &d.tid))) return rc;
+            if ((rc = b.up(reads->pos, (size_t)n, &d.pos))) return rc;
+            if ((rc = b.up(reads->flag, (size_t)n, &d.flag))) return rc;
+        }
+        const int32_t *d_tid = nullptr;
+        const uint64_t *d_st = nullptr, *d_en = nullptr, *d_off = nullptr;
+        if ((rc = b.up(rg_tid, (size_t)n_regions, &d_tid))) return rc;
+        if ((rc = b.up(rg_st, (size_t)n_regions, &d_st))) return rc;
+        if ((rc = b.up(rg_en, (size_t)n_regions, &d_en))) return rc;
+        if ((rc = b.up(out_off.data(), (size_t)n_regions + 1, &d_off))) return rc;
+        uint32_t *d_status = nullptr;
+        rb_nucfreq_counters *d_ctr = nullptr;
+        uint8_t *d_ws = nullptr;
+        if ((rc = b.alloc((size_t)n_pos * 4 + 4, &d_counts))) return rc;
+        if ((rc = b.alloc((size_t)n + 1, &d_status))) return rc;
+        if ((rc = b.alloc(1, &d_ctr))) return rc;
+        const size_t wsb = rb_nucfreq_workspace_bytes(n, n_regions, n_pos);
+        if ((rc = b.alloc(wsb, &d_ws))) return rc;
+        if ((rc = rb_dev_nucfreq(ctx, &d, n_regions, d_tid, d_st, d_en, d_off, n_pos, d_counts, d_status, d_ctr, d_ws, wsb))) return rc;
+        if ((rc = rb_dev_download(ctx, counters, d_ctr, sizeof(*counters)))) return rc;
+        if (read_status && n && (rc = rb_dev_download(ctx, read_status, d_status, (size_t)n * 4))) return rc;
+        return RB_OK;
+    }
+};
+// counts that are not the reference's
+int nf_refuse(rb_ctx *ctx, const rb_nucfreq_counters *counters) {
     if (counters->unsorted) return fail(ctx, RB_E_INVALID, "nucfreq: the reads are not sorted by (tid, pos)");
     if (counters->cap_overflow)
         return fail(ctx, RB_E_INVALID, "nucfreq: the bookkeeping of htslib's cap of %u buffered reads does not fit (depth %llu)", RB_NF_DEPTH_CAP,
                     (unsigned long long)counters->max_depth);
     if (counters->max_depth > 65535) return fail(ctx, RB_E_INVALID, "nucfreq: depth %llu does not fit the 16-bit counters", (unsigned long long)counters->max_depth);
+    return RB_OK;
+}
+} // namespace
+
+extern "C" int rb_host_nucfreq(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
+                               const uint64_t *rg_en, uint32_t *counts, uint32_t *read_status, rb_nucfreq_counters *counters) {
+    if (!ctx || !reads || !counters || (n_regions && (!rg_tid || !rg_st || !rg_en))) return RB_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    NfDev D(ctx);
+    int rc;
+    if ((rc = D.layout(ctx, n_regions, rg_st, rg_en))) return rc;
+    if (D.n_pos && !counts) return RB_E_INVALID;
+    if ((rc = D.run(ctx, reads, n_regions, rg_tid, rg_st, rg_en, read_status, counters))) return rc;
+    if (D.n_pos && (rc = rb_dev_download(ctx, counts, D.d_counts, (size_t)D.n_pos * 16))) return rc;
+    return nf_refuse(ctx, counters);
+}
+
+// ---- nucfreq: the lines (k_nftext.hip) ------------------------------------------------------------------------------------
+namespace {
+struct nft_layout {
+    size_t seg, unit0, unit_off, blk, total;
+    uint64_t max_units;
+};
+nft_layout nft_scratch_layout(uint64_t n_seg, uint64_t n_positions) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    nft_layout L;
+    L.max_units = n_positions / rb_nft_run() + n_seg; // a segment of n positions is ceil(n / run) runs
+    size_t o = 0;
+    L.seg = o, o = up(o + (size_t)n_seg * sizeof(rb_nft_seg));
+    L.unit0 = o, o = up(o + ((size_t)n_seg + 1) * 4);
+    L.unit_off = o, o = up(o + ((size_t)L.max_units + 2) * 8);
+    L.blk = o, o = up(o + (rb_scan_block_sums_count(L.max_units) + 4) * 8);
+    L.total = o;
+    return L;
+}
+} // namespace
+
+extern "C" size_t rb_nucfreq_text_scratch_bytes(uint64_t n_seg, uint64_t n_positions) { return nft_scratch_layout(n_seg, n_positions).total; }
+extern "C" void rb_nucfreq_text_shape(uint32_t out[4]) {
+    out[0] = rb_nft_step(), out[1] = rb_nft_block(), out[2] = rb_nft_fix(), out[3] = rb_nft_fix();
+}
+
+extern "C" int rb_dev_nucfreq_text(rb_ctx *ctx, const uint32_t *counts, uint64_t n_seg, const uint64_t *seg_cnt, const uint64_t *seg_pos,
+                                   const uint32_t *seg_n, const uint8_t *strings, const uint32_t *pre_off, const uint32_t *pre_len,
+                                   const uint32_t *suf_off, const uint32_t *suf_len, int mode, uint64_t *seg_text_off, uint64_t *seg_first,
+                                   uint64_t *seg_lines, uint8_t *text, uint64_t text_cap, void *scratch) {
+    if (!ctx) return RB_E_INVALID;
+    if (mode != RB_NFT_FULL && mode != RB_NFT_SMALL) return fail(ctx, RB_E_INVALID, "nucfreq text: mode %d is neither RB_NFT_FULL nor RB_NFT_SMALL", mode);
+    if (!seg_text_off || !scratch || (n_seg && (!seg_cnt || !seg_pos || !seg_n || !seg_first || !seg_lines)))
+        return fail(ctx, RB_E_INVALID, "nucfreq text: a pointer that is needed is NULL");
+    if (mode == RB_NFT_FULL && n_seg && (!strings || !pre_off || !pre_len || !suf_off || !suf_len))
+        return fail(ctx, RB_E_INVALID, "nucfreq text: RB_NFT_FULL needs strings and the prefix and suffix arrays");
+    if (n_seg >= 0xFFFFFFFFull) return fail(ctx, RB_E_INVALID, "nucfreq text: too many segments for one call");
+    if (((uintptr_t)counts & 15u) || ((uintptr_t)text & 15u) || ((uintptr_t)scratch & 255u))
+        return fail(ctx, RB_E_INVALID, "nucfreq text: counts and text must be 16-byte aligned, the scratch 256-byte aligned");
+    // the segments as the kernel reads them, and the runs numbered through
+    std::vector<rb_nft_seg> seg((size_t)n_seg);
+    std::vector<uint32_t> unit0((size_t)n_seg + 1);
+    uint64_t n_units = 0, n_positions = 0;
+    for (uint64_t s = 0; s < n_seg; s++) {
+        if (seg_pos[s] > (1ull << 32) || seg_pos[s] + seg_n[s] > (1ull << 32))
+            return fail(ctx, RB_E_INVALID, "nucfreq text: segment %llu reaches behind position 2^32", (unsigned long long)s);
+        rb_nft_seg &g = seg[(size_t)s];
+        g.cnt = seg_cnt[s], g.pos = (uint32_t)seg_pos[s], g.n = seg_n[s];
+        g.pre_off = g.suf_off = g.pre_len = g.suf_len = 0;
+        if (mode == RB_NFT_FULL) {
+            if (pre_len[s] > rb_nft_fix() || suf_len[s] > rb_nft_fix())
+                return fail(ctx, RB_E_INVALID, "nucfreq text: the prefix or suffix of segment %llu is longer than %u bytes", (unsigned long long)s, rb_nft_fix());
+            g.pre_off = pre_off[s], g.suf_off = suf_off[s], g.pre_len = pre_len[s], g.suf_len = suf_len[s];
+        }
+        unit0[(size_t)s] = (uint32_t)n_units;
+        n_units += ((uint64_t)seg_n[s] + rb_nft_run() - 1) / rb_nft_run();
+        n_positions += seg_n[s];
+        if (n_units >= 0xFFFFFFFFull) return fail(ctx, RB_E_INVALID, "nucfreq text: too many positions for one call");
+    }
+    unit0[(size_t)n_seg] = (uint32_t)n_units;
+    if (n_units && !counts) return fail(ctx, RB_E_INVALID, "nucfreq text: counts is NULL");
+    const nft_layout L = nft_scratch_layout(n_seg, n_positions);
+    uint8_t *w = (uint8_t *)scratch;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if (n_seg && (rc = rb_dev_upload(ctx, w + L.seg, seg.data(), seg.size() * sizeof(rb_nft_seg)))) return rc; // (consumed when it returns)
+    if ((rc = rb_dev_upload(ctx, w + L.unit0, unit0.data(), unit0.size() * 4))) return rc;
+    rb_nft_params p{};
+    p.counts = counts, p.n_seg = n_seg, p.seg = (const rb_nft_seg *)(w + L.seg), p.unit0 = (const uint32_t *)(w + L.unit0), p.n_units = n_units;
+    p.strings = strings, p.mode = mode;
+    p.unit_off = (uint64_t *)(w + L.unit_off);
+    p.seg_text_off = seg_text_off, p.seg_first = seg_first, p.seg_lines = seg_lines;
+    p.text = text, p.text_cap = text_cap;
+    if (n_seg) {
+        HIPCHK(ctx, rb_fill_async(seg_first, 0xFF, (size_t)n_seg * 8, ctx->stream));
+        HIPCHK(ctx, rb_fill_async(seg_lines, 0, (size_t)n_seg * 8, ctx->stream));
+    }
+    HIPCHK(ctx, rb_fill_async(p.unit_off + n_units, 0, 8, ctx->stream));
+    HIPCHK(ctx, rb_launch_nft(&p, false, ctx->stream));
+    HIPCHK(ctx, rb_launch_exclusive_scan(p.unit_off, n_units, (uint64_t *)(w + L.blk), nullptr, ctx->stream));
+    HIPCHK(ctx, rb_launch_nft_seg_off(&p, ctx->stream));
+    if (text) HIPCHK(ctx, rb_launch_nft(&p, true, ctx->stream));
+    return RB_OK;
+}
+
+extern "C" int rb_host_nucfreq_text(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
+                                    const uint64_t *rg_en, uint64_t n_seg, const uint64_t *seg_cnt, const uint64_t *seg_pos, const uint32_t *seg_n,
+                                    const uint8_t *strings, uint64_t strings_bytes, const uint32_t *pre_off, const uint32_t *pre_len,
+                                    const uint32_t *suf_off, const uint32_t *suf_len, int mode, uint32_t *read_status, rb_nucfreq_counters *counters,
+                                    void (*sink)(void *user, uint64_t first_seg, uint64_t n_seg, const uint64_t *seg_text_off,
+                                                 const uint64_t *seg_first, const uint8_t *text),
+                                    void *user) {
+    if (!ctx || !reads || !counters || !sink || (n_regions && (!rg_tid || !rg_st || !rg_en))) return RB_E_INVALID;
+    if (n_seg && (!seg_cnt || !seg_pos || !seg_n)) return RB_E_INVALID;
+    if (mode == RB_NFT_FULL && n_seg && (!pre_off || !pre_len || !suf_off || !suf_len || (strings_bytes && !strings))) return RB_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    NfDev D(ctx);
+    int rc;
+    if ((rc = D.layout(ctx, n_regions, rg_st, rg_en))) return rc;
+    uint64_t seg_positions = 0;
+    for (uint64_t s = 0; s < n_seg; s++) {
+        if (seg_cnt[s] > D.n_pos || seg_n[s] > D.n_pos - seg_cnt[s])
+            return fail(ctx, RB_E_INVALID, "nucfreq text: segment %llu lies outside the %llu positions of the regions", (unsigned long long)s, (unsigned long long)D.n_pos);
+        seg_positions += seg_n[s];
+        if (mode == RB_NFT_FULL && ((uint64_t)pre_off[s] + pre_len[s] > strings_bytes || (uint64_t)suf_off[s] + suf_len[s] > strings_bytes))
+            return fail(ctx, RB_E_INVALID, "nucfreq text: a string of segment %llu lies outside strings", (unsigned long long)s);
+    }
+    if ((rc = D.run(ctx, reads, n_regions, rg_tid, rg_st, rg_en, read_status, counters))) return rc;
+    if ((rc = nf_refuse(ctx, counters))) return rc;
+    if (n_seg == 0) return RB_OK;
+    // sizes first, then runs of whole segments into a bounded buffer
+    const uint8_t *d_strings = nullptr;
+    if ((rc = D.b.up(strings, (size_t)strings_bytes, &d_strings))) return rc;
+    uint64_t *d_off = nullptr, *d_first = nullptr, *d_lines = nullptr;
+    uint8_t *d_scr = nullptr, *d_text = nullptr;
+    if ((rc = D.b.alloc((size_t)n_seg + 1, &d_off)) || (rc = D.b.alloc((size_t)n_seg, &d_first)) || (rc = D.b.alloc((size_t)n_seg, &d_lines))) return rc;
+    if ((rc = D.b.alloc(rb_nucfreq_text_scratch_bytes(n_seg, seg_positions) + 256, &d_scr))) return rc;
+    d_scr = (uint8_t *)(((uintptr_t)d_scr + 255) & ~(uintptr_t)255);
+    if ((rc = rb_dev_nucfreq_text(ctx, D.d_counts, n_seg, seg_cnt, seg_pos, seg_n, d_strings, pre_off, pre_len, suf_off, suf_len, mode, d_off, d_first,
+                                  d_lines, nullptr, 0, d_scr)))
+        return rc;
+    std::vector<uint64_t> off((size_t)n_seg + 1), first((size_t)n_seg), rel;
+    if ((rc = rb_dev_download(ctx, off.data(), d_off, off.size() * 8)) || (rc = rb_dev_download(ctx, first.data(), d_first, first.size() * 8))) return rc;
+    uint64_t SLAB = 1ull << 30;
+    if (const char *e = getenv("RB_DEBUG_NFT_SLAB")) SLAB = std::max<uint64_t>(strtoull(e, nullptr, 10), 1); // tests: several slabs, and a segment longer than one, at a small size
+    uint64_t cap = 0; // the largest slab: whole segments up to SLAB bytes, a longer segment alone
+    for (uint64_t s0 = 0, s1; s0 < n_seg; s0 = s1) {
+        for (s1 = s0 + 1; s1 < n_seg && off[(size_t)s1 + 1] - off[(size_t)s0] <= SLAB; s1++) {}
+        cap = std::max(cap, off[(size_t)s1] - off[(size_t)s0]);
+    }
+    uint8_t *h_text = nullptr;
+    if (cap) {
+        if ((rc = D.b.alloc((size_t)cap + 16, &d_text))) return rc;
+        h_text = (uint8_t *)malloc((size_t)cap);
+        if (!h_text) return fail(ctx, RB_E_NOMEM, "nucfreq text: %llu bytes of host memory", (unsigned long long)cap);
+        rb_advise_huge(h_text, (size_t)cap);
+    }
+    for (uint64_t s0 = 0, s1; s0 < n_seg; s0 = s1) {
+        for (s1 = s0 + 1; s1 < n_seg && off[(size_t)s1 + 1] - off[(size_t)s0] <= SLAB; s1++) {}
+        const uint64_t bytes = off[(size_t)s1] - off[(size_t)s0];
+        if (bytes) {
+            rc = rb_dev_nucfreq_text(ctx, D.d_counts, s1 - s0, seg_cnt + s0, seg_pos + s0, seg_n + s0, d_strings, pre_off ? pre_off + s0 : nullptr,
+                                     pre_len ? pre_len + s0 : nullptr, suf_off ? suf_off + s0 : nullptr, suf_len ? suf_len + s0 : nullptr, mode, d_off,
+                                     d_first, d_lines, d_text, bytes, d_scr);
+            if (!rc) rc = rb_dev_download(ctx, h_text, d_text, (size_t)bytes);
+            if (rc) {
+                free(h_text);
+                return rc;
+            }
+        }
+        rel.resize((size_t)(s1 - s0) + 1);
+        for (uint64_t s = s0; s <= s1; s++) rel[(size_t)(s - s0)] = off[(size_t)s] - off[(size_t)s0];
+        sink(user, s0, s1 - s0, rel.data(), first.data() + s0, h_text);
+    }
+    free(h_text);
     return RB_OK;
 }

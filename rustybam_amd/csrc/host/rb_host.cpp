@@ -3596,6 +3596,42 @@ static bool load_bam_reads_indexed(const std::string &path, const std::vector<Re
     return true;
 }
 
+// the print pieces of a batch of chunks as the segments of rb_host_nucfreq_text: one per [m0, me) of nucfreq_bam, with the region's
+// name + TAB and TAB + id + LF as prefix and suffix.  build() returns false when a region's strings do not fit the kernel's 255 bytes.
+struct NfSegs {
+    std::vector<uint64_t> cnt, pos;
+    std::vector<uint32_t> n, pre_off, pre_len, suf_off, suf_len;
+    std::vector<const Region *> region;
+    std::string strings;
+    template <typename F>
+    bool build(size_t n_chunks, const uint64_t *off, F chunk, uint64_t piece) {
+        uint32_t fix[4];
+        rb_nucfreq_text_shape(fix);
+        const Region *last = nullptr;
+        uint32_t po = 0, pl = 0, so = 0, sl = 0;
+        for (size_t k = 0; k < n_chunks; k++) {
+            uint64_t b0, b1, c1;
+            const Region *R = chunk(k, &b0, &b1, &c1);
+            if (R != last) {
+                if (R->name.size() + 1 > fix[2] || R->id.size() + 2 > fix[3]) return false;
+                po = (uint32_t)strings.size(), pl = (uint32_t)R->name.size() + 1;
+                strings += R->name, strings += '\t';
+                so = (uint32_t)strings.size(), sl = (uint32_t)R->id.size() + 2;
+                strings += '\t', strings += R->id, strings += '\n';
+                last = R;
+            }
+            for (uint64_t m0 = b0; m0 < b1; m0 += piece) {
+                const uint64_t me = std::min(std::min(m0 + piece, b1), c1);
+                const uint32_t np = me > m0 ? (uint32_t)(me - m0) : 0u; // (a piece behind the contig's end: a header and no lines)
+                cnt.push_back(np ? off[k] + (m0 - b0) : off[k]), pos.push_back(np ? m0 : 0), n.push_back(np);
+                pre_off.push_back(po), pre_len.push_back(pl), suf_off.push_back(so), suf_len.push_back(sl);
+                region.push_back(R);
+            }
+        }
+        return true;
+    }
+};
+
 void put_u64(std::string &o, uint64_t v) {
     char b[24];
     auto [p, e] = std::to_chars(b, b + sizeof b, v);
@@ -3605,8 +3641,14 @@ void put_u64(std::string &o, uint64_t v) {
 } // namespace
 
 void nucfreq_bam(Engine &eng, const std::string &bam_path, const std::vector<Region> &rgns, bool small,
-                 const std::function<void(const std::string &)> &put) {
+                 const std::function<void(const std::string &)> &put, const std::function<void(const char *, size_t)> &put_bytes) {
     double tl = now_s();
+    // the text route: the lines are printed on the device (rb_host_nucfreq_text) and only text comes back; RB_GENERAL_PATH=1 keeps the
+    // counts coming back and the lines formatted on the host.  --small takes it by default; the full format does with RB_NUCFREQ_TEXT=1
+    // only: end to end it did not beat the host formatter by more than that one's own run-to-run spread (profiles/nucfreq_text_summary.md)
+    const bool text_route = !getenv("RB_GENERAL_PATH") && (small || getenv("RB_NUCFREQ_TEXT"));
+    static const bool timing = getenv("RB_TIMING") != nullptr;
+    bool route_named = false;
     BamReads B;
     if (!load_bam_reads_indexed(bam_path, rgns, B)) {
         B = BamReads();
@@ -3637,7 +3679,7 @@ void nucfreq_bam(Engine &eng, const std::string &bam_path, const std::vector<Reg
             off[k + 1] = off[k] + (en[k] - st[k]);
             if (en[k] > st[k]) lo_pos = std::min(lo_pos, st[k]), hi_pos = std::max(hi_pos, en[k]);
         }
-        counts.assign((size_t)off[batch.size()] * 4 + 4, 0);
+        bool counts_zeroed = false; // (the text route never looks at counts: 16 bytes a position stay untouched)
         if (hi_pos > lo_pos) { // the slice of reads that can reach any chunk of the batch
             const uint64_t k_st = nf_key(tid, lo_pos), k_en = nf_key(tid, hi_pos);
             const uint64_t i0 = (uint64_t)(std::upper_bound(B.end_key_pmax.begin(), B.end_key_pmax.end(), k_st) - B.end_key_pmax.begin());
@@ -3654,17 +3696,75 @@ void nucfreq_bam(Engine &eng, const std::string &bam_path, const std::vector<Reg
                 v.ops = B.ops.data(), v.op_off = B.op_off.data() + i0, v.seq = B.seq.data(), v.seq_off = B.seq_off.data() + i0;
                 v.l_seq = B.l_seq.data() + i0, v.tid = B.tid.data() + i0, v.pos = B.pos.data() + i0, v.flag = B.flag.data() + i0;
                 status.assign((size_t)v.n_reads, 0);
-                eng.check(rb_host_nucfreq(eng.ctx(), &v, batch.size(), rt.data(), st.data(), en.data(), counts.data(), status.data(), &ctr), "rb_host_nucfreq");
-                for (uint64_t i = 0; i < v.n_reads; i++) {
-                    if (status[i] == RB_RD_SEQ_SHORT) throw Panic("index out of bounds: a base of read " + std::to_string(i0 + i) + " lies past its sequence");
-                    if (status[i] == RB_RD_BAD_CIGAR) { // htslib's cursor asserts on it -- if a fetch of one of these chunks returns the read
-                        const int64_t p0 = B.pos[i0 + i];
-                        for (const Chunk &c : batch)
-                            if (p0 < (int64_t)c.c1 && p0 + 1 > (int64_t)c.b0) throw Panic("nucfreq: read " + std::to_string(i0 + i) + " has a cigar htslib's pileup cannot walk");
+                // the reads the reference dies on: looked for before anything of the batch is printed
+                auto check_reads = [&]() {
+                    for (uint64_t i = 0; i < v.n_reads; i++) {
+                        if (status[i] == RB_RD_SEQ_SHORT) throw Panic("index out of bounds: a base of read " + std::to_string(i0 + i) + " lies past its sequence");
+                        if (status[i] == RB_RD_BAD_CIGAR) { // htslib's cursor asserts on it -- if a fetch of one of these chunks returns the read
+                            const int64_t p0 = B.pos[i0 + i];
+                            for (const Chunk &c : batch)
+                                if (p0 < (int64_t)c.c1 && p0 + 1 > (int64_t)c.b0) throw Panic("nucfreq: read " + std::to_string(i0 + i) + " has a cigar htslib's pileup cannot walk");
+                        }
                     }
+                };
+                // one segment per print piece; a region's prefix is its name + TAB, its suffix TAB + id + LF
+                NfSegs S;
+                if (text_route && S.build(batch.size(), off.data(), [&](size_t k, uint64_t *b0, uint64_t *b1, uint64_t *c1) {
+                        *b0 = batch[k].b0, *b1 = batch[k].b1, *c1 = batch[k].c1;
+                        return &rgns[batch[k].rg];
+                    }, MED)) {
+                    if (timing && !route_named) fprintf(stderr, "[rb timing] nucfreq_text: rb_dev_nucfreq, rb_dev_nucfreq_text\n");
+                    route_named = true;
+                    struct Sink {
+                        NfSegs *S;
+                        bool small;
+                        const std::function<void(const std::string &)> *put;
+                        const std::function<void(const char *, size_t)> *put_bytes;
+                        const std::function<void()> *check_reads;
+                        bool checked = false;
+                        std::exception_ptr err;
+                        std::string line;
+                    } sk{&S, small, &put, &put_bytes, nullptr};
+                    const std::function<void()> chk = check_reads;
+                    sk.check_reads = &chk;
+                    auto sink = [](void *user, uint64_t first_seg, uint64_t n_seg, const uint64_t *seg_text_off, const uint64_t *seg_first, const uint8_t *text) {
+                        Sink &K = *(Sink *)user;
+                        if (K.err) return;
+                        try { // (nothing is thrown across the C ABI: the panic waits until the call is back)
+                            if (!K.checked) (*K.check_reads)();
+                            K.checked = true;
+                            for (uint64_t j = 0; j < n_seg; j++) {
+                                const Region &R = *K.S->region[(size_t)(first_seg + j)];
+                                K.line.clear();
+                                if (!K.small) {
+                                    K.line = "#chr\tstart\tend\tA\tC\tG\tT\tregion_id\n"; // nucfreq.rs:127-131, once per piece
+                                } else if (seg_first[j] != ~0ull) { // the "#name pos id" line in front of the piece's first reported position
+                                    K.line += '#', K.line += R.name, K.line += '\t';
+                                    put_u64(K.line, seg_first[j]);
+                                    K.line += '\t', K.line += R.id, K.line += '\n';
+                                }
+                                (*K.put)(K.line);
+                                if (seg_text_off[j + 1] > seg_text_off[j]) (*K.put_bytes)((const char *)text + seg_text_off[j], (size_t)(seg_text_off[j + 1] - seg_text_off[j]));
+                            }
+                        } catch (...) {
+                            K.err = std::current_exception();
+                        }
+                    };
+                    const int rc = rb_host_nucfreq_text(eng.ctx(), &v, batch.size(), rt.data(), st.data(), en.data(), S.cnt.size(), S.cnt.data(), S.pos.data(),
+                                                        S.n.data(), (const uint8_t *)S.strings.data(), S.strings.size(), S.pre_off.data(), S.pre_len.data(),
+                                                        S.suf_off.data(), S.suf_len.data(), small ? RB_NFT_SMALL : RB_NFT_FULL, status.data(), &ctr, sink, &sk);
+                    if (sk.err) std::rethrow_exception(sk.err);
+                    eng.check(rc, "rb_host_nucfreq_text");
+                    if (!sk.checked) check_reads();
+                    lap("nucfreq: device + lines + write", tl);
+                    return;
                 }
+                counts.assign((size_t)off[batch.size()] * 4 + 4, 0), counts_zeroed = true;
+                eng.check(rb_host_nucfreq(eng.ctx(), &v, batch.size(), rt.data(), st.data(), en.data(), counts.data(), status.data(), &ctr), "rb_host_nucfreq");
+                check_reads();
             }
         }
+        if (!counts_zeroed) counts.assign((size_t)off[batch.size()] * 4 + 4, 0); // (no read reaches the batch)
         lap("nucfreq: device", tl);
         for (size_t k = 0; k < batch.size(); k++) {
             const Chunk &C = batch[k];

@@ -207,9 +207,15 @@ std::string cigar_stats_header(bool qbed);              // bamstats.rs:225-236
 // bed::parse_region (bed.rs:88-131): "name:st-en", 1-based inclusive start -> 0-based half-open; id = the same text
 Region parse_region(const std::string &region);
 // main.rs:82-121 + nucfreq.rs: A/C/G/T counts at every covered position of every region, printed piece by piece (1 Mbp) through
-// `put`; BGZF/BAM decode on the host, the pileup on the device (rb_host_nucfreq)
+// `put`; BGZF/BAM decode on the host, the pileup and the lines on the device (rb_host_nucfreq_text: the counts stay there, the text of
+// a piece comes back and goes out through `put_bytes` behind the header line the host writes through `put`) -- by default for --small,
+// with RB_NUCFREQ_TEXT=1 for the full format too (profiles/nucfreq_text_summary.md says why not by default).  RB_GENERAL_PATH=1, and a
+// region whose name + TAB or TAB + id + LF is longer than the kernel's 255 bytes: rb_host_nucfreq, the counts back, the lines formatted on
+// all host cores.  So does, on either route, a batch of regions that no read reaches: nothing is sent to the device for it, and it prints
+// header lines only.  RB_TIMING=1: the text route names itself ("[rb timing] nucfreq_text: ...") the first time a batch takes it, and a
+// batch on it has one lap ("nucfreq: device + lines + write") where the host formatter has two ("nucfreq: device", "nucfreq: format + write").
 void nucfreq_bam(Engine &eng, const std::string &bam_path, const std::vector<Region> &rgns, bool small,
-                 const std::function<void(const std::string &)> &put);
+                 const std::function<void(const std::string &)> &put, const std::function<void(const char *, size_t)> &put_bytes);
 std::string cigar_stats_line(const Stats &s, bool qbed); // bamstats.rs:239-270
 
 } // namespace rb

@@ -999,7 +999,7 @@ int main(int argc, char **argv) {
             if (!region.empty()) rgns.push_back(rb::parse_region(region));
             if (!bed_path.empty())
                 for (rb::Region &r : rb::parse_bed(bed_path)) rgns.push_back(std::move(r));
-            rb::nucfreq_bam(eng, paf_path, rgns, small, [&](const std::string &t) { put(t); });
+            rb::nucfreq_bam(eng, paf_path, rgns, small, [&](const std::string &t) { put(t); }, [&](const char *p, size_t n) { fwrite(p, 1, n, stdout); });
         } else if (cmd == "stats") {
             if (!g_worker.on) put(rb::cigar_stats_header(qbed)); // (`--gpus`: the parent has printed it)
             if (!is_paf) { // BAM or SAM input (main.rs:60-77: htslib reads "sam/bam/cram", cli.rs:49-60)

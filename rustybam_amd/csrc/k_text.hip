@@ -195,20 +195,7 @@ __global__ __launch_bounds__(256) void rb_k_parse_cigars(rb_parse_params p) {
     }
 }
 
-// decimal digits of v, at most 9 (an op with a continuation word may have ten: its caller adds the tenth)
-__device__ __forceinline__ uint32_t rb_ndigits(uint32_t v) {
-    return 1u + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u) + (v >= 100000000u);
-}
-
 #define RB_FMT_STAGE (256 * 10 + 48) // bytes of text one step of 256 words can make (9 digits + the op character each; an op with a continuation word: 11 bytes for its two words) + the 16-byte phase + 16 bytes of slack in front
-// the four low decimal digits of x < 10000, least significant first, as one byte each of a dword: multiplications by constants that
-// fit 24 bits (v_mul_u32_u24: full rate; the per-digit x / 10 of round 2 was a v_mul_hi_u32 -- quarter rate -- per digit)
-__device__ __forceinline__ uint32_t rb_digits4(uint32_t x) {
-    const uint32_t hi = (x * 5243u) >> 19, lo = x - hi * 100u; // x / 100, x % 100 (exact below 43699)
-    const uint32_t a = (hi * 103u) >> 10, b = hi - a * 10u;     // y / 10, y % 10 (exact below 179)
-    const uint32_t c = (lo * 103u) >> 10, d = lo - c * 10u;
-    return d | (c << 8) | (b << 16) | (a << 24);
-}
 template <bool FILL>
 __global__ __launch_bounds__(256) void rb_k_format_cigars(rb_format_params p) {
     // fill pass: the text of a step is put together in LDS (one byte per digit, at the 16-byte phase it has in memory) and leaves with

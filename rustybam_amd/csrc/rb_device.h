@@ -207,3 +207,18 @@ __device__ __forceinline__ uint4 rb_load4_unaligned(const uint32_t *p) {
     rb_u4_unaligned t = *reinterpret_cast<const rb_u4_unaligned *>(p);
     return make_uint4(t.x, t.y, t.z, t.w);
 }
+
+// ---- decimal text (k_text.hip, k_nftext.hip) ----
+// decimal digits of v, at most 9 (an op with a continuation word may have ten: its caller adds the tenth)
+__device__ __forceinline__ uint32_t rb_ndigits(uint32_t v) {
+    return 1u + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u) + (v >= 100000000u);
+}
+
+// the four low decimal digits of x < 10000, least significant first, as one byte each of a dword: multiplications by constants that
+// fit 24 bits (v_mul_u32_u24: full rate; the per-digit x / 10 of round 2 was a v_mul_hi_u32 -- quarter rate -- per digit)
+__device__ __forceinline__ uint32_t rb_digits4(uint32_t x) {
+    const uint32_t hi = (x * 5243u) >> 19, lo = x - hi * 100u; // x / 100, x % 100 (exact below 43699)
+    const uint32_t a = (hi * 103u) >> 10, b = hi - a * 10u;     // y / 10, y % 10 (exact below 179)
+    const uint32_t c = (lo * 103u) >> 10, d = lo - c * 10u;
+    return d | (c << 8) | (b << 16) | (a << 24);
+}

@@ -355,5 +355,33 @@ extern "C" hipError_t rb_launch_nucfreq(const rb_nf_params *p, hipStream_t strea
 extern "C" size_t rb_nf_tile_positions(void);
 extern "C" size_t rb_nf_scan_blocks(uint64_t n);
 
+// ---- k_nftext.hip: the lines of nucfreq ----
+struct rb_nft_seg { // one segment as the kernel reads it (capi.hip packs the caller's seven arrays into these)
+    uint64_t cnt;   // counts[4 * (cnt + k)] belongs to position pos + k
+    uint32_t pos, n;
+    uint32_t pre_off, suf_off, pre_len, suf_len;
+};
+struct rb_nft_params {
+    const uint32_t *counts;   // 16-byte aligned
+    uint64_t n_seg;
+    const rb_nft_seg *seg;    // [n_seg]
+    const uint32_t *unit0;    // [n_seg + 1] the first run of every segment; [n_seg] = n_units
+    uint64_t n_units;         // runs of rb_nft_run() positions, all segments together
+    const uint8_t *strings;
+    int mode;                 // RB_NFT_FULL / RB_NFT_SMALL
+    uint64_t *unit_off;       // [n_units + 1] bytes per run (sizes pass), then their exclusive prefix
+    uint64_t *seg_text_off;   // [n_seg + 1] OUT
+    uint64_t *seg_first;      // [n_seg] OUT, set to ~0 before the sizes pass
+    uint64_t *seg_lines;      // [n_seg] OUT, zeroed before the sizes pass
+    uint8_t *text;            // 16-byte aligned
+    uint64_t text_cap;
+};
+extern "C" hipError_t rb_launch_nft(const rb_nft_params *p, bool fill, hipStream_t stream);
+extern "C" hipError_t rb_launch_nft_seg_off(const rb_nft_params *p, hipStream_t stream);
+extern "C" uint32_t rb_nft_step(void);
+extern "C" uint32_t rb_nft_run(void);
+extern "C" uint32_t rb_nft_block(void);
+extern "C" uint32_t rb_nft_fix(void);
+
 // ---- capi.hip: the library's own fill kernel (capi.hip says why) ----
 extern "C" hipError_t rb_fill_async(void *dst, int value, size_t bytes, hipStream_t stream);
