@@ -897,6 +897,43 @@ int rb_host_bam_records(rb_ctx *ctx, const uint8_t *data, uint64_t data_bytes, c
                         int32_t *tid, int64_t *pos, uint32_t *flag, uint32_t *l_seq, uint8_t *has_md, uint64_t *md_off, uint64_t *md_end,
                         uint64_t *op_off, uint32_t *ops, uint64_t ops_cap, uint8_t *status);
 
+/* ---- the per-read index of `rb nucfreq in.bam` (k_bamreads.hip): what bam_read_records keeps per record besides the columns ------ *
+ *
+ * rb_dev_bam_reads  <- the SEQ place, the (tid, pos) key, the running maximum of (tid, bam_endpos) over the reads the pileup admits
+ *                      and the sortedness test of the pileup iterator, for the n records rb_dev_bam_records decoded.
+ *     data, rec_off, rec_len, n   as given to rb_dev_bam_records (rec_len is not read).  data 16-byte aligned, slack as there.
+ *     tid, pos, flag, op_off, ops, status   what rb_dev_bam_records wrote.  ops holds all op_off[n] words (a call that was cut short
+ *               by its ops_cap is not an input), is 16-byte aligned and readable to the next multiple of 4 words behind the last op:
+ *               the call reads whole aligned 16-byte groups that hold a word of a record.
+ *     One entry per record, no compaction:
+ *     seq_off [n] u64       the byte of data where the record's SEQ starts: rec_off + 32 + l_read_name + 4 * n_cigar_op with the
+ *                           IN-RECORD n_cigar_op (behind the two in-record words of a CG:B,I record); 0 where status != RB_BAM_OK.
+ *     start_key [n] u64     (uint64_t)(uint32_t)tid << 32 | min((uint64_t)pos, 0xFFFFFFFF): a negative pos saturates.
+ *     end_key_pmax [n] u64  the INCLUSIVE prefix maximum over records 0 .. i of the same key of (tid, endpos) of the reads that enter
+ *                           the pileup: tid >= 0, no flag of 0x4 | 0x100 | 0x200 | 0x400, status == RB_BAM_OK.
+ *                           endpos = max(pos, 0) + ((flag & 4) || ref == 0 ? 1 : ref), ref = the 64-bit sum of the lengths of the
+ *                           record's ops whose nibble is M, D, N, = or X.  A read that does not enter carries the value in front of
+ *                           it; the value in front of record 0 is 0.
+ *     first_unsorted  one u64: the smallest i >= 1 with start_key[i] < start_key[i - 1] && tid[i] >= 0 && pos[i] >= 0; ~0 if none.
+ *     scratch   rb_bam_reads_scratch_bytes(n) bytes, 256-byte aligned.
+ *     Enqueues on the context's stream, does not synchronise.  n == 0 is valid (first_unsorted = ~0).  Writes its outputs and scratch,
+ *     nothing else.  Two calls on the same input write the same bytes, whatever the buffers held.  RB_E_INVALID, before anything is
+ *     enqueued: a NULL pointer that is needed, data or ops misaligned, scratch misaligned.
+ * rb_bam_reads_shape: {ops per step of a row of 16 lanes, the longest CIGAR a row sums (longer ones take the whole wavefront), ops per
+ *     step of the wavefront, records per workgroup of the scan} (no device needed).  A workgroup of the scan's second level takes as
+ *     many maxima as the first takes records: above out[3] * out[3] records a serial top level joins in.
+ * rb_host_bam_reads: rb_host_bam_records and this call on HOST arrays: uploads, runs both, downloads every column of both.
+ *     RB_E_INVALID if ops_cap is smaller than the records' ops. */
+size_t rb_bam_reads_scratch_bytes(uint64_t n);
+void rb_bam_reads_shape(uint32_t out[4]);
+int rb_dev_bam_reads(rb_ctx *ctx, const uint8_t *data, const uint64_t *rec_off, const uint32_t *rec_len, uint64_t n, const int32_t *tid,
+                     const int64_t *pos, const uint32_t *flag, const uint64_t *op_off, const uint32_t *ops, const uint8_t *status,
+                     uint64_t *seq_off, uint64_t *start_key, uint64_t *end_key_pmax, uint64_t *first_unsorted, void *scratch);
+int rb_host_bam_reads(rb_ctx *ctx, const uint8_t *data, uint64_t data_bytes, const uint64_t *rec_off, const uint32_t *rec_len, uint64_t n,
+                      int32_t *tid, int64_t *pos, uint32_t *flag, uint32_t *l_seq, uint8_t *has_md, uint64_t *md_off, uint64_t *md_end,
+                      uint64_t *op_off, uint32_t *ops, uint64_t ops_cap, uint8_t *status, uint64_t *seq_off, uint64_t *start_key,
+                      uint64_t *end_key_pmax, uint64_t *first_unsorted);
+
 /* ---- nucfreq: A/C/G/T counts at every covered reference position -----------------
  *
  * rb_dev_nucfreq  <- nucfreq::nucfreq (nucfreq.rs:61-95) over the reads nucfreq::region_nucfreq fetches (:111-125),
@@ -951,6 +988,13 @@ int rb_dev_nucfreq(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, 
  * counts [4 * sum(en - st)] and read_status [n_reads] are caller-allocated; read_status may be NULL */
 int rb_host_nucfreq(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
                     const uint64_t *rg_en, uint32_t *counts, uint32_t *read_status, rb_nucfreq_counters *counters);
+/* resident-reads form: rb_host_nucfreq, except that every pointer of reads is DEVICE memory and nothing of the reads is uploaded.
+ * ops and seq are the caller's bases, indexed by ABSOLUTE op_off / seq_off (the columns of rb_dev_bam_records / rb_dev_bam_reads, seq =
+ * the stream itself); the other arrays may be interior pointers (column base + i0) for the slice [i0, i0 + n_reads), op_off with
+ * n_reads + 1 entries.  MEMORY: seq is 4-byte aligned, and 32 readable bytes lie behind the last read's SEQ (a stream buffer is
+ * allocated with that slack).  Regions, counts, read_status and counters are HOST memory as there; the refusals are the same. */
+int rb_devreads_nucfreq(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
+                        const uint64_t *rg_en, uint32_t *counts, uint32_t *read_status, rb_nucfreq_counters *counters);
 
 /* ---- nucfreq: the lines printed on the device (k_nftext.hip) ----------------------------------------------------------
  *
@@ -1007,6 +1051,15 @@ int rb_host_nucfreq_text(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_reg
                          void (*sink)(void *user, uint64_t first_seg, uint64_t n_seg, const uint64_t *seg_text_off,
                                       const uint64_t *seg_first, const uint8_t *text),
                          void *user);
+/* resident-reads form: rb_host_nucfreq_text with reads a DEVICE view under the memory contract of rb_devreads_nucfreq; segments, strings,
+ * read_status, counters and sink stay HOST-side; refusals, slabs and RB_DEBUG_NFT_SLAB as there. */
+int rb_devreads_nucfreq_text(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
+                             const uint64_t *rg_en, uint64_t n_seg, const uint64_t *seg_cnt, const uint64_t *seg_pos, const uint32_t *seg_n,
+                             const uint8_t *strings, uint64_t strings_bytes, const uint32_t *pre_off, const uint32_t *pre_len,
+                             const uint32_t *suf_off, const uint32_t *suf_len, int mode, uint32_t *read_status, rb_nucfreq_counters *counters,
+                             void (*sink)(void *user, uint64_t first_seg, uint64_t n_seg, const uint64_t *seg_text_off,
+                                          const uint64_t *seg_first, const uint8_t *text),
+                             void *user);
 
 /* ---- verification aid (tests, bench; not a reference function): digest of hit rows and their clipped CIGARs ---------------
  * *digest += sum over i < n_rows of mix(row i) * (2 * (row_base + i) + 1), wrapping u64 (the caller zeroes *digest).  mix covers

@@ -10,5 +10,5 @@ from .capi import (Engine, RbError, lib, lib_path, HIT_DT, NORM_DT, REDUCE_DT, C
                    PAIRS_INFO_DT, PAIRS_ORIENT, PAIRS_FILTER, PAIRS_DECL_PANIC, PAIRS_DECL_KEY, PAIRS_DECL_WRAP, PAIRS_DECL_ZERO_SPAN, pairs_shape, host_pairs_rows,
                    pairs_records_shape, host_pairs_records,
                    ALN_DT, MD_OK, MD_UNUSUAL, ALN_OK, ALN_PANIC_DEL_FIRST, ALN_PANIC_HARDCLIP, ALN_PANIC_NONE, ALN_PANIC_MD_ASSERT, ALN_MD_STATUS, ALN_WARN_M, md_shape,
-                   BAM_OK, BAM_SHORT_BLOCK, BAM_NO_FIT, BAM_BAD_NAME, bam_shape,
+                   BAM_OK, BAM_SHORT_BLOCK, BAM_NO_FIT, BAM_BAD_NAME, bam_shape, bam_reads_shape,
                    NFT_FULL, NFT_SMALL, nucfreq_text_shape)

@@ -166,6 +166,16 @@ def bam_shape():
     return tuple(int(x) for x in out)
 
 
+def bam_reads_shape():
+    """rb_dev_bam_reads' kernels (rb_bam_reads_shape: no device needed): (ops per step of a row of 16 lanes, longest CIGAR a row sums, ops per
+    step of the wavefront, records per workgroup of the scan)"""
+    out = (C.c_uint32 * 4)()
+    f = lib().rb_bam_reads_shape
+    f.restype = None
+    f(out)
+    return tuple(int(x) for x in out)
+
+
 def pairs_shape():
     """(consecutive rows one wavefront of rb_dev_pairs_rows' sum kernel walks, rows per workgroup) (rb_pairs_shape: no device needed)"""
     out = (C.c_uint32 * 2)()
@@ -226,6 +236,12 @@ def _p(a):
 
 def _arr(x, dt):
     return np.ascontiguousarray(x, dtype=dt)
+
+
+class ReadsView(C.Structure):
+    """rb_reads_view"""
+    _fields_ = [("n_reads", C.c_uint64), ("ops", C.c_void_p), ("op_off", C.c_void_p), ("seq", C.c_void_p), ("seq_off", C.c_void_p),
+                ("l_seq", C.c_void_p), ("tid", C.c_void_p), ("pos", C.c_void_p), ("flag", C.c_void_p)]
 
 
 class BatchView(C.Structure):
@@ -566,11 +582,11 @@ class Engine:
         return dict(tid=mk(n, np.int32), pos=mk(n, np.int64), flag=mk(n, np.uint32), l_seq=mk(n, np.uint32), has_md=mk(n, np.uint8), md_off=mk(n, np.uint64),
                     md_end=mk(n, np.uint64), op_off=mk(n + 1, np.uint64), status=mk(n, np.uint8))
 
-    def bam_records(self, data, rec_off, rec_len, ops_cap=None, guard=0, keep=False):
+    def bam_records(self, data, rec_off, rec_len, ops_cap=None, guard=0, keep=False, ops_fill=0xA5A5A5A5):
         """rb_dev_bam_records on host arrays: data (bytes-like; padded here to the slack the call asks for with 0xA5, which is no NUL), the
         records' places -> dict(tid, pos, flag, l_seq, has_md, md_off, md_end, status [n + guard], op_off [n + 1 + guard], ops u32
         [ops_cap + guard]); ops_cap None: (bytes of data) / 4.  The `guard` entries behind every array were filled with 0xA5 before the
-        call, and so was all of ops.  keep: the device buffers stay (dict key "dev": name -> address, "free": call it when done) for
+        call, and all of ops with ops_fill.  keep: the device buffers stay (dict key "dev": name -> address, "free": call it when done) for
         calls that go on with the columns where they lie."""
         data = np.frombuffer(bytes(data), np.uint8)
         n_bytes = len(data)
@@ -579,7 +595,7 @@ class Engine:
         n = len(rec_off)
         cap = n_bytes // 4 if ops_cap is None else int(ops_cap)
         out = self._bam_cols(n, guard, True)
-        out["ops"] = np.full(cap + guard, 0xA5A5A5A5, np.uint32)
+        out["ops"] = np.full(cap + guard, ops_fill, np.uint32)
         names = ("tid", "pos", "flag", "l_seq", "has_md", "md_off", "md_end", "op_off", "ops", "status")
         bufs = []
         try:
@@ -611,6 +627,72 @@ class Engine:
         self._chk(self.L.rb_host_bam_records(self.ctx, _p(data), C.c_uint64(len(data)), _p(rec_off), _p(rec_len), C.c_uint64(n),
                                              *[_p(out[k]) for k in ("tid", "pos", "flag", "l_seq", "has_md", "md_off", "md_end", "op_off", "ops")],
                                              C.c_uint64(cap), _p(out["status"])), "rb_host_bam_records")
+        return out
+
+    # ---- the per-read index of nucfreq (k_bamreads.hip) ----
+    def bam_reads_scratch_bytes(self, n):
+        f = self.L.rb_bam_reads_scratch_bytes
+        f.restype = C.c_size_t
+        return int(f(C.c_uint64(n)))
+
+    def dev_bam_reads(self, data_ptr, rec_off_ptr, rec_len_ptr, n, tid_ptr, pos_ptr, flag_ptr, op_off_ptr, ops_ptr, status_ptr, seq_off_ptr,
+                      start_key_ptr, end_key_pmax_ptr, first_unsorted_ptr, scratch_ptr, check=True):
+        """rb_dev_bam_reads on device addresses; enqueues on the context's stream.  Returns the call's return value (check=False: without
+        raising)."""
+        v = C.c_void_p
+        rc = self.L.rb_dev_bam_reads(self.ctx, v(data_ptr or 0), v(rec_off_ptr or 0), v(rec_len_ptr or 0), C.c_uint64(n), v(tid_ptr or 0), v(pos_ptr or 0),
+                                     v(flag_ptr or 0), v(op_off_ptr or 0), v(ops_ptr or 0), v(status_ptr or 0), v(seq_off_ptr or 0), v(start_key_ptr or 0),
+                                     v(end_key_pmax_ptr or 0), v(first_unsorted_ptr or 0), v(scratch_ptr or 0))
+        if check:
+            self._chk(rc, "rb_dev_bam_reads")
+        return int(rc)
+
+    def bam_reads(self, data, rec_off, rec_len, guard=0, keep=False):
+        """rb_dev_bam_records, then rb_dev_bam_reads on its columns where they lie -> the dict of bam_records() plus seq_off, start_key,
+        end_key_pmax [n + guard] and first_unsorted [1 + guard] (every entry 0xA5 before the call, scratch too; ops was filled with 0xA0A0A0A0, an M of
+        length 0xA0A0A0A: a word behind a record's last op that got into its sum would show).  keep: as bam_records()."""
+        out = self.bam_records(data, rec_off, rec_len, guard=guard, keep=True, ops_fill=0xA0A0A0A0)
+        n = len(out["status"]) - guard
+        d, bufs = out["dev"], []
+        names = ("seq_off", "start_key", "end_key_pmax", "first_unsorted")
+        try:
+            for k in names:
+                out[k] = np.full((1 if k == "first_unsorted" else n) + guard, 0xA5A5A5A5A5A5A5A5, np.uint64)
+                d[k] = self._up(bufs, out[k])
+            d["reads_scratch"] = self._up(bufs, np.full(self.bam_reads_scratch_bytes(n) + 256, 0xA5, np.uint8))
+            scr = (d["reads_scratch"] + 255) & ~255
+            self.dev_bam_reads(d["data"], d["rec_off"], d["rec_len"], n, d["tid"], d["pos"], d["flag"], d["op_off"], d["ops"], d["status"], d["seq_off"],
+                               d["start_key"], d["end_key_pmax"], d["first_unsorted"], scr)
+            for k in names:
+                self._down(out[k], d[k])
+            self.sync()
+            if keep:
+                free0, kept = out["free"], list(bufs)
+                out["free"] = lambda: (free0(), [self.dev_free(b) for b in kept])
+                bufs = []
+            return out
+        finally:
+            self.sync()
+            for b in bufs:
+                self.dev_free(b)
+            if not keep:
+                out["free"]()
+
+    def host_bam_reads(self, data, rec_off, rec_len, ops_cap=None):
+        """rb_host_bam_reads -> the dict of host_bam_records() plus seq_off, start_key, end_key_pmax [n] and first_unsorted [1]"""
+        data = np.frombuffer(bytes(data), np.uint8)
+        rec_off, rec_len = _arr(rec_off, np.uint64), _arr(rec_len, np.uint32)
+        n = len(rec_off)
+        cap = len(data) // 4 if ops_cap is None else int(ops_cap)
+        out = self._bam_cols(n, 0, False)
+        out["ops"] = np.zeros(cap, np.uint32)
+        for k in ("seq_off", "start_key", "end_key_pmax"):
+            out[k] = np.zeros(n, np.uint64)
+        out["first_unsorted"] = np.zeros(1, np.uint64)
+        self._chk(self.L.rb_host_bam_reads(self.ctx, _p(data), C.c_uint64(len(data)), _p(rec_off), _p(rec_len), C.c_uint64(n),
+                                           *[_p(out[k]) for k in ("tid", "pos", "flag", "l_seq", "has_md", "md_off", "md_end", "op_off", "ops")],
+                                           C.c_uint64(cap), _p(out["status"]), _p(out["seq_off"]), _p(out["start_key"]), _p(out["end_key_pmax"]),
+                                           _p(out["first_unsorted"])), "rb_host_bam_reads")
         return out
 
     def rows_to_batch_scratch_bytes(self, n_rows):
@@ -1079,6 +1161,46 @@ class Engine:
                   "rb_host_nucfreq_text")
         return slabs, status[:n], dict(max_depth=int(ctr[0]), n_covered=int(ctr[1]), n_bad=int(ctr[2]), unsorted=int(ctr[3]),
                                        n_dropped=int(ctr[4]), cap_overflow=int(ctr[5]))
+
+    # ---- nucfreq on resident reads (rb_devreads_nucfreq, rb_devreads_nucfreq_text) ----
+    def devreads_nucfreq(self, n_reads, ops, op_off, seq, seq_off, l_seq, tid, pos, flag, rg_tid, rg_st, rg_en):
+        """nucfreq() on reads that are resident: the eight read pointers are device addresses (int; ops and seq the bases of absolute
+        op_off / seq_off, the others may point into their columns).  Returns what nucfreq() returns."""
+        rg_tid, rg_st, rg_en = _arr(rg_tid, np.int32), _arr(rg_st, np.uint64), _arr(rg_en, np.uint64)
+        nr = len(rg_tid)
+        n_pos = int((rg_en.astype(np.int64) - rg_st.astype(np.int64)).sum()) if nr else 0
+        v = ReadsView(n_reads, ops, op_off, seq, seq_off, l_seq, tid, pos, flag)
+        counts = np.zeros((max(n_pos, 1), 4), np.uint32)
+        status = np.zeros(max(n_reads, 1), np.uint32)
+        ctr = np.zeros(6, np.uint64)
+        self._chk(self.L.rb_devreads_nucfreq(self.ctx, C.byref(v), C.c_uint64(nr), _p(rg_tid), _p(rg_st), _p(rg_en), _p(counts), _p(status),
+                                             _p(ctr)), "rb_devreads_nucfreq")
+        return counts[:n_pos], status[:n_reads], dict(max_depth=int(ctr[0]), n_covered=int(ctr[1]), n_bad=int(ctr[2]), unsorted=int(ctr[3]),
+                                                      n_dropped=int(ctr[4]), cap_overflow=int(ctr[5]))
+
+    def devreads_nucfreq_text(self, n_reads, ops, op_off, seq, seq_off, l_seq, tid, pos, flag, rg_tid, rg_st, rg_en, seg_cnt, seg_pos, seg_n,
+                              strings=b"", pre_off=None, pre_len=None, suf_off=None, suf_len=None, mode=NFT_FULL):
+        """nucfreq_text() on reads that are resident (device addresses as in devreads_nucfreq()).  Returns what nucfreq_text() returns."""
+        rg_tid, rg_st, rg_en = _arr(rg_tid, np.int32), _arr(rg_st, np.uint64), _arr(rg_en, np.uint64)
+        seg_cnt, seg_pos, seg_n = _arr(seg_cnt, np.uint64), _arr(seg_pos, np.uint64), _arr(seg_n, np.uint32)
+        fix = [None if a is None else _arr(a, np.uint32) for a in (pre_off, pre_len, suf_off, suf_len)]
+        sb = np.frombuffer(bytes(strings) + b"\0", np.uint8).copy()
+        v = ReadsView(n_reads, ops, op_off, seq, seq_off, l_seq, tid, pos, flag)
+        status = np.zeros(max(n_reads, 1), np.uint32)
+        ctr = np.zeros(6, np.uint64)
+        slabs = []
+        SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8))
+
+        def sink(_user, first_seg, k, off, first, text):
+            o = np.ctypeslib.as_array(off, (k + 1,)).copy()
+            slabs.append((int(first_seg), o, np.ctypeslib.as_array(first, (k,)).copy(), C.string_at(text, int(o[k])) if int(o[k]) else b""))
+        cb = SINK(sink)
+        self._chk(self.L.rb_devreads_nucfreq_text(self.ctx, C.byref(v), C.c_uint64(len(rg_tid)), _p(rg_tid), _p(rg_st), _p(rg_en), C.c_uint64(len(seg_n)),
+                                                  _p(seg_cnt), _p(seg_pos), _p(seg_n), _p(sb), C.c_uint64(len(strings)),
+                                                  *[None if a is None else _p(a) for a in fix], C.c_int(mode), _p(status), _p(ctr), cb, None),
+                  "rb_devreads_nucfreq_text")
+        return slabs, status[:n_reads], dict(max_depth=int(ctr[0]), n_covered=int(ctr[1]), n_bad=int(ctr[2]), unsorted=int(ctr[3]),
+                                             n_dropped=int(ctr[4]), cap_overflow=int(ctr[5]))
 
 
 def synth_n_ops(seed, first_record, n_rec, lo, hi):

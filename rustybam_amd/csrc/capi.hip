@@ -2659,23 +2659,50 @@ extern "C" int rb_dev_bam_records(rb_ctx *ctx, const uint8_t *data, const uint64
     HIPCHK(ctx, rb_launch_bam_copy(&p, ctx->stream));
     return RB_OK;
 }
-extern "C" int rb_host_bam_records(rb_ctx *ctx, const uint8_t *data, uint64_t data_bytes, const uint64_t *rec_off, const uint32_t *rec_len, uint64_t n,
-                                   int32_t *tid, int64_t *pos, uint32_t *flag, uint32_t *l_seq, uint8_t *has_md, uint64_t *md_off, uint64_t *md_end,
-                                   uint64_t *op_off, uint32_t *ops, uint64_t ops_cap, uint8_t *status) {
-    if (!ctx || !op_off || (data_bytes && !data) || (ops_cap && !ops)) return RB_E_INVALID;
+// ---- the per-read index of nucfreq on the columns of rb_dev_bam_records (k_bamreads.hip) ------------------
+// scratch of rb_dev_bam_reads: the maxima of the scan's workgroups, level by level
+extern "C" size_t rb_bam_reads_scratch_bytes(uint64_t n) { return (rb_bam_reads_blk_count(n) * 8 + 255) & ~(size_t)255; }
+extern "C" void rb_bam_reads_shape(uint32_t out[4]) {
+    out[0] = rb_bam_reads_row_step(), out[1] = rb_bam_reads_row_max(), out[2] = rb_bam_reads_wave_step(), out[3] = rb_bam_reads_scan_block();
+}
+extern "C" int rb_dev_bam_reads(rb_ctx *ctx, const uint8_t *data, const uint64_t *rec_off, const uint32_t *rec_len, uint64_t n, const int32_t *tid,
+                                const int64_t *pos, const uint32_t *flag, const uint64_t *op_off, const uint32_t *ops, const uint8_t *status,
+                                uint64_t *seq_off, uint64_t *start_key, uint64_t *end_key_pmax, uint64_t *first_unsorted, void *scratch) {
+    if (!ctx || !first_unsorted) return RB_E_INVALID;
+    if (n && (!data || !rec_off || !rec_len || !tid || !pos || !flag || !op_off || !status || !seq_off || !start_key || !end_key_pmax || !scratch))
+        return RB_E_INVALID;
+    if (((uintptr_t)data | (uintptr_t)ops) & 15u) return fail(ctx, RB_E_INVALID, "rb_dev_bam_reads: data and ops must be 16-byte aligned");
+    if ((uintptr_t)scratch & 255u) return fail(ctx, RB_E_INVALID, "rb_dev_bam_reads: scratch must be 256-byte aligned");
+    rb_bam_reads_params p;
+    p.n = n;
+    p.data = data, p.rec_off = rec_off, p.rec_len = rec_len;
+    p.tid = tid, p.pos = pos, p.flag = flag, p.op_off = op_off, p.ops = ops, p.status = status;
+    p.seq_off = seq_off, p.start_key = start_key, p.end_key_pmax = end_key_pmax;
+    p.first_unsorted = (unsigned long long *)first_unsorted;
+    p.blk = (uint64_t *)scratch;
+    HIPCHK(ctx, rb_fill_async(first_unsorted, 0xFF, 8, ctx->stream));
+    HIPCHK(ctx, rb_launch_bam_reads(&p, ctx->stream));
+    return RB_OK;
+}
+// rb_host_bam_records, and with `reads` rb_host_bam_reads: the two share upload, columns and downloads
+static int bam_host(rb_ctx *ctx, bool reads, const uint8_t *data, uint64_t data_bytes, const uint64_t *rec_off, const uint32_t *rec_len, uint64_t n, int32_t *tid,
+                    int64_t *pos, uint32_t *flag, uint32_t *l_seq, uint8_t *has_md, uint64_t *md_off, uint64_t *md_end, uint64_t *op_off, uint32_t *ops,
+                    uint64_t ops_cap, uint8_t *status, uint64_t *seq_off, uint64_t *start_key, uint64_t *end_key_pmax, uint64_t *first_unsorted) {
+    if (!ctx || !op_off || (data_bytes && !data) || (ops_cap && !ops) || (reads && !first_unsorted)) return RB_E_INVALID;
     if (n && (!rec_off || !rec_len || !tid || !pos || !flag || !l_seq || !has_md || !md_off || !md_end || !status)) return RB_E_INVALID;
+    if (n && reads && (!seq_off || !start_key || !end_key_pmax)) return RB_E_INVALID;
     for (uint64_t r = 0; r < n; r++)
         if (rec_off[r] > data_bytes || rec_len[r] > data_bytes - rec_off[r]) return fail(ctx, RB_E_INVALID, "record %llu: outside the data", (unsigned long long)r);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBatch b(ctx);
-    uint8_t *d_data = nullptr, *d_has = nullptr, *d_status = nullptr, *d_scr = nullptr;
+    uint8_t *d_data = nullptr, *d_has = nullptr, *d_status = nullptr, *d_scr = nullptr, *d_scr2 = nullptr;
     const uint64_t *d_roff = nullptr;
     const uint32_t *d_rlen = nullptr;
     int32_t *d_tid = nullptr;
     int64_t *d_pos = nullptr;
     uint32_t *d_flag = nullptr, *d_lseq = nullptr, *d_ops = nullptr;
-    uint64_t *d_moff = nullptr, *d_mend = nullptr, *d_opoff = nullptr;
-    int rc = b.alloc((size_t)data_bytes + 32, &d_data); // (the slack the device call asks for)
+    uint64_t *d_moff = nullptr, *d_mend = nullptr, *d_opoff = nullptr, *d_sqo = nullptr, *d_sk = nullptr, *d_ek = nullptr, *d_fu = nullptr;
+    int rc = b.alloc((size_t)data_bytes + 32, &d_data); // (the slack the device calls ask for)
     if (!rc && data_bytes) rc = rb_dev_upload(ctx, d_data, data, (size_t)data_bytes);
     if (!rc) rc = b.up(rec_off, (size_t)n, &d_roff);
     if (!rc) rc = b.up(rec_len, (size_t)n, &d_rlen);
@@ -2691,6 +2718,21 @@ extern "C" int rb_host_bam_records(rb_ctx *ctx, const uint8_t *data, uint64_t da
     if (!rc) rc = b.alloc((size_t)n + 1, &d_status);
     if (!rc) rc = b.alloc(rb_bam_scratch_bytes(n), &d_scr);
     if (!rc) rc = rb_dev_bam_records(ctx, d_data, d_roff, d_rlen, n, d_tid, d_pos, d_flag, d_lseq, d_has, d_moff, d_mend, d_opoff, d_ops, ops_cap, d_status, d_scr);
+    if (!rc) rc = rb_dev_download(ctx, op_off, d_opoff, ((size_t)n + 1) * 8); // (rb_dev_download returns with the bytes there: op_off[n] is read below)
+    if (!rc && reads) {
+        if (op_off[n] > ops_cap) return fail(ctx, RB_E_INVALID, "rb_host_bam_reads: %llu ops do not fit ops_cap", (unsigned long long)op_off[n]);
+        rc = b.alloc((size_t)n + 1, &d_sqo);
+        if (!rc) rc = b.alloc((size_t)n + 1, &d_sk);
+        if (!rc) rc = b.alloc((size_t)n + 1, &d_ek);
+        if (!rc) rc = b.alloc(1, &d_fu);
+        if (!rc) rc = b.alloc(rb_bam_reads_scratch_bytes(n) + 256, &d_scr2);
+        d_scr2 = (uint8_t *)(((uintptr_t)d_scr2 + 255) & ~(uintptr_t)255);
+        if (!rc) rc = rb_dev_bam_reads(ctx, d_data, d_roff, d_rlen, n, d_tid, d_pos, d_flag, d_opoff, d_ops, d_status, d_sqo, d_sk, d_ek, d_fu, d_scr2);
+        if (!rc && n) rc = rb_dev_download(ctx, seq_off, d_sqo, (size_t)n * 8);
+        if (!rc && n) rc = rb_dev_download(ctx, start_key, d_sk, (size_t)n * 8);
+        if (!rc && n) rc = rb_dev_download(ctx, end_key_pmax, d_ek, (size_t)n * 8);
+        if (!rc) rc = rb_dev_download(ctx, first_unsorted, d_fu, 8);
+    }
     if (!rc && n) rc = rb_dev_download(ctx, tid, d_tid, (size_t)n * 4);
     if (!rc && n) rc = rb_dev_download(ctx, pos, d_pos, (size_t)n * 8);
     if (!rc && n) rc = rb_dev_download(ctx, flag, d_flag, (size_t)n * 4);
@@ -2699,12 +2741,24 @@ extern "C" int rb_host_bam_records(rb_ctx *ctx, const uint8_t *data, uint64_t da
     if (!rc && n) rc = rb_dev_download(ctx, md_off, d_moff, (size_t)n * 8);
     if (!rc && n) rc = rb_dev_download(ctx, md_end, d_mend, (size_t)n * 8);
     if (!rc && n) rc = rb_dev_download(ctx, status, d_status, (size_t)n);
-    if (!rc) rc = rb_dev_download(ctx, op_off, d_opoff, ((size_t)n + 1) * 8);
     if (!rc) {
         const uint64_t got = op_off[n] < ops_cap ? op_off[n] : ops_cap;
         if (got) rc = rb_dev_download(ctx, ops, d_ops, (size_t)got * 4);
     }
     return rc ? rc : rb_ctx_sync(ctx);
+}
+extern "C" int rb_host_bam_records(rb_ctx *ctx, const uint8_t *data, uint64_t data_bytes, const uint64_t *rec_off, const uint32_t *rec_len, uint64_t n,
+                                   int32_t *tid, int64_t *pos, uint32_t *flag, uint32_t *l_seq, uint8_t *has_md, uint64_t *md_off, uint64_t *md_end,
+                                   uint64_t *op_off, uint32_t *ops, uint64_t ops_cap, uint8_t *status) {
+    return bam_host(ctx, false, data, data_bytes, rec_off, rec_len, n, tid, pos, flag, l_seq, has_md, md_off, md_end, op_off, ops, ops_cap, status, nullptr,
+                    nullptr, nullptr, nullptr);
+}
+extern "C" int rb_host_bam_reads(rb_ctx *ctx, const uint8_t *data, uint64_t data_bytes, const uint64_t *rec_off, const uint32_t *rec_len, uint64_t n,
+                                 int32_t *tid, int64_t *pos, uint32_t *flag, uint32_t *l_seq, uint8_t *has_md, uint64_t *md_off, uint64_t *md_end,
+                                 uint64_t *op_off, uint32_t *ops, uint64_t ops_cap, uint8_t *status, uint64_t *seq_off, uint64_t *start_key,
+                                 uint64_t *end_key_pmax, uint64_t *first_unsorted) {
+    return bam_host(ctx, true, data, data_bytes, rec_off, rec_len, n, tid, pos, flag, l_seq, has_md, md_off, md_end, op_off, ops, ops_cap, status, seq_off,
+                    start_key, end_key_pmax, first_unsorted);
 }
 
 // ---- the hit rows of a clip call as a dense batch (k_rows_batch.hip) ----------------------------------
@@ -3149,14 +3203,17 @@ struct NfDev {
         n_pos = out_off[n_regions];
         return RB_OK;
     }
-    // upload, rb_dev_nucfreq into d_counts, counters and read_status back (layout() first)
-    int run(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st, const uint64_t *rg_en,
-            uint32_t *read_status, rb_nucfreq_counters *counters) {
+    // upload, rb_dev_nucfreq into d_counts, counters and read_status back (layout() first).  resident: *reads is a DEVICE view already
+    // (rb_devreads_nucfreq) and nothing of the reads goes up
+    int run(rb_ctx *ctx, const rb_reads_view *reads, bool resident, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
+            const uint64_t *rg_en, uint32_t *read_status, rb_nucfreq_counters *counters) {
         const uint64_t n = reads->n_reads;
         rb_reads_view d{};
         d.n_reads = n;
         int rc;
-        if (n) {
+        if (resident) {
+            d = *reads;
+        } else if (n) {
             // only the part of ops / seq these reads use goes up, offsets rebased
             const uint64_t op0 = reads->op_off[0], op1 = reads->op_off[n];
             uint64_t s0 = ~0ull, s1 = 0;
@@ -3212,17 +3269,26 @@ int nf_refuse(rb_ctx *ctx, const rb_nucfreq_counters *counters) {
 }
 } // namespace
 
-extern "C" int rb_host_nucfreq(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
-                               const uint64_t *rg_en, uint32_t *counts, uint32_t *read_status, rb_nucfreq_counters *counters) {
+static int nf_counts(rb_ctx *ctx, const rb_reads_view *reads, bool resident, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
+                     const uint64_t *rg_en, uint32_t *counts, uint32_t *read_status, rb_nucfreq_counters *counters) {
     if (!ctx || !reads || !counters || (n_regions && (!rg_tid || !rg_st || !rg_en))) return RB_E_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     NfDev D(ctx);
     int rc;
     if ((rc = D.layout(ctx, n_regions, rg_st, rg_en))) return rc;
     if (D.n_pos && !counts) return RB_E_INVALID;
-    if ((rc = D.run(ctx, reads, n_regions, rg_tid, rg_st, rg_en, read_status, counters))) return rc;
+    if ((rc = D.run(ctx, reads, resident, n_regions, rg_tid, rg_st, rg_en, read_status, counters))) return rc;
     if (D.n_pos && (rc = rb_dev_download(ctx, counts, D.d_counts, (size_t)D.n_pos * 16))) return rc;
     return nf_refuse(ctx, counters);
+}
+extern "C" int rb_host_nucfreq(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
+                               const uint64_t *rg_en, uint32_t *counts, uint32_t *read_status, rb_nucfreq_counters *counters) {
+    return nf_counts(ctx, reads, false, n_regions, rg_tid, rg_st, rg_en, counts, read_status, counters);
+}
+extern "C" int rb_devreads_nucfreq(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
+                                   const uint64_t *rg_en, uint32_t *counts, uint32_t *read_status, rb_nucfreq_counters *counters) {
+    if (ctx && reads && ((uintptr_t)reads->seq & 3u)) return fail(ctx, RB_E_INVALID, "rb_devreads_nucfreq: seq must be 4-byte aligned");
+    return nf_counts(ctx, reads, true, n_regions, rg_tid, rg_st, rg_en, counts, read_status, counters);
 }
 
 // ---- nucfreq: the lines (k_nftext.hip) ------------------------------------------------------------------------------------
@@ -3309,13 +3375,11 @@ extern "C" int rb_dev_nucfreq_text(rb_ctx *ctx, const uint32_t *counts, uint64_t
     return RB_OK;
 }
 
-extern "C" int rb_host_nucfreq_text(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
-                                    const uint64_t *rg_en, uint64_t n_seg, const uint64_t *seg_cnt, const uint64_t *seg_pos, const uint32_t *seg_n,
-                                    const uint8_t *strings, uint64_t strings_bytes, const uint32_t *pre_off, const uint32_t *pre_len,
-                                    const uint32_t *suf_off, const uint32_t *suf_len, int mode, uint32_t *read_status, rb_nucfreq_counters *counters,
-                                    void (*sink)(void *user, uint64_t first_seg, uint64_t n_seg, const uint64_t *seg_text_off,
-                                                 const uint64_t *seg_first, const uint8_t *text),
-                                    void *user) {
+typedef void (*nft_sink)(void *user, uint64_t first_seg, uint64_t n_seg, const uint64_t *seg_text_off, const uint64_t *seg_first, const uint8_t *text);
+static int nf_text(rb_ctx *ctx, const rb_reads_view *reads, bool resident, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
+                   const uint64_t *rg_en, uint64_t n_seg, const uint64_t *seg_cnt, const uint64_t *seg_pos, const uint32_t *seg_n, const uint8_t *strings,
+                   uint64_t strings_bytes, const uint32_t *pre_off, const uint32_t *pre_len, const uint32_t *suf_off, const uint32_t *suf_len, int mode,
+                   uint32_t *read_status, rb_nucfreq_counters *counters, nft_sink sink, void *user) {
     if (!ctx || !reads || !counters || !sink || (n_regions && (!rg_tid || !rg_st || !rg_en))) return RB_E_INVALID;
     if (n_seg && (!seg_cnt || !seg_pos || !seg_n)) return RB_E_INVALID;
     if (mode == RB_NFT_FULL && n_seg && (!pre_off || !pre_len || !suf_off || !suf_len || (strings_bytes && !strings))) return RB_E_INVALID;
@@ -3331,7 +3395,7 @@ extern "C" int rb_host_nucfreq_text(rb_ctx *ctx, const rb_reads_view *reads, uin
         if (mode == RB_NFT_FULL && ((uint64_t)pre_off[s] + pre_len[s] > strings_bytes || (uint64_t)suf_off[s] + suf_len[s] > strings_bytes))
             return fail(ctx, RB_E_INVALID, "nucfreq text: a string of segment %llu lies outside strings", (unsigned long long)s);
     }
-    if ((rc = D.run(ctx, reads, n_regions, rg_tid, rg_st, rg_en, read_status, counters))) return rc;
+    if ((rc = D.run(ctx, reads, resident, n_regions, rg_tid, rg_st, rg_en, read_status, counters))) return rc;
     if ((rc = nf_refuse(ctx, counters))) return rc;
     if (n_seg == 0) return RB_OK;
     // sizes first, then runs of whole segments into a bounded buffer
@@ -3380,4 +3444,25 @@ extern "C" int rb_host_nucfreq_text(rb_ctx *ctx, const rb_reads_view *reads, uin
     }
     free(h_text);
     return RB_OK;
+}
+extern "C" int rb_host_nucfreq_text(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
+                                    const uint64_t *rg_en, uint64_t n_seg, const uint64_t *seg_cnt, const uint64_t *seg_pos, const uint32_t *seg_n,
+                                    const uint8_t *strings, uint64_t strings_bytes, const uint32_t *pre_off, const uint32_t *pre_len,
+                                    const uint32_t *suf_off, const uint32_t *suf_len, int mode, uint32_t *read_status, rb_nucfreq_counters *counters,
+                                    void (*sink)(void *user, uint64_t first_seg, uint64_t n_seg, const uint64_t *seg_text_off,
+                                                 const uint64_t *seg_first, const uint8_t *text),
+                                    void *user) {
+    return nf_text(ctx, reads, false, n_regions, rg_tid, rg_st, rg_en, n_seg, seg_cnt, seg_pos, seg_n, strings, strings_bytes, pre_off, pre_len, suf_off,
+                   suf_len, mode, read_status, counters, sink, user);
+}
+extern "C" int rb_devreads_nucfreq_text(rb_ctx *ctx, const rb_reads_view *reads, uint64_t n_regions, const int32_t *rg_tid, const uint64_t *rg_st,
+                                        const uint64_t *rg_en, uint64_t n_seg, const uint64_t *seg_cnt, const uint64_t *seg_pos, const uint32_t *seg_n,
+                                        const uint8_t *strings, uint64_t strings_bytes, const uint32_t *pre_off, const uint32_t *pre_len,
+                                        const uint32_t *suf_off, const uint32_t *suf_len, int mode, uint32_t *read_status, rb_nucfreq_counters *counters,
+                                        void (*sink)(void *user, uint64_t first_seg, uint64_t n_seg, const uint64_t *seg_text_off,
+                                                     const uint64_t *seg_first, const uint8_t *text),
+                                        void *user) {
+    if (ctx && reads && ((uintptr_t)reads->seq & 3u)) return fail(ctx, RB_E_INVALID, "rb_devreads_nucfreq_text: seq must be 4-byte aligned");
+    return nf_text(ctx, reads, true, n_regions, rg_tid, rg_st, rg_en, n_seg, seg_cnt, seg_pos, seg_n, strings, strings_bytes, pre_off, pre_len, suf_off,
+                   suf_len, mode, read_status, counters, sink, user);
 }

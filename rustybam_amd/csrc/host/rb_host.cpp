@@ -3527,8 +3527,11 @@ static bool bgzf_load_range(int fd, size_t file_size, size_t c, size_t c_last, B
     return ok && f.inflate_members(raw.get(), end - c, c);
 }
 
-// load only what the regions need, through <bam>.bai.  false = no usable index (the caller reads the whole file)
-static bool load_bam_reads_indexed(const std::string &path, const std::vector<Region> &rgns, BamReads &B) {
+// find what the regions need through <bam>.bai: the header into B, then each(f, e) for every merged range in file order -- the
+// inflated members in f (each may move from it), the range's records those that start in [f.pos, e).  false = no usable index (the
+// caller reads the whole file); that can come after each has been called for earlier ranges: the caller discards what it collected
+template <typename Each>
+static bool bam_indexed_ranges(const std::string &path, const std::vector<Region> &rgns, BamReads &B, Each each) {
     if (path == "-" || getenv("RB_NO_BAI")) return false;
     Bai bai;
     if (!bai.load(path + ".bai")) return false;
@@ -3588,11 +3591,146 @@ static bool load_bam_reads_indexed(const std::string &path, const std::vector<Re
         const size_t a = f.upos(lo), e = f.upos(hi);
         if (a == ~(size_t)0 || e == ~(size_t)0 || a > e || e > f.n) return false;
         f.pos = a;
-        bam_read_records(f, e, B);
+        each(f, e);
         i = j;
     }
+    return true;
+}
+// load only what the regions need
+static bool load_bam_reads_indexed(const std::string &path, const std::vector<Region> &rgns, BamReads &B) {
+    if (!bam_indexed_ranges(path, rgns, B, [&](BamStream &f, size_t e) { bam_read_records(f, e, B); })) return false;
     if (B.op_off.empty()) B.op_off.push_back(0);
     bam_finish(B);
+    return true;
+}
+
+// ---- the route that decodes on the device (RB_NUCFREQ_DEV_DECODE=1): the inflated bytes stay where they are, the host only hops from
+// record to record; the stream goes up once and rb_dev_bam_records / rb_dev_bam_reads make the columns nucfreq_bam and the pileup need.
+// The hop of the records that start in [f.pos, stop): bam_next without the copy.  A file that ends inside a record leaves bam_next's
+// panic in `pending` and ends the hop; `base` = where f.buf[0] lies in the uploaded bytes.
+static void bam_hop_records(BamStream &f, size_t stop, uint64_t base, std::vector<uint64_t> &rec_off, std::vector<uint32_t> &rec_len, std::string &pending) {
+    while (f.pos < stop && f.pos != f.n) {
+        if (f.n - f.pos < 4) {
+            pending = "truncated BAM file (inside a block_size field)";
+            return;
+        }
+        const uint32_t bs = le32(f.buf.get() + f.pos);
+        if (bs > f.n - f.pos - 4) {
+            pending = "truncated BAM file (inside a record)";
+            return;
+        }
+        rec_off.push_back(base + f.pos + 4), rec_len.push_back(bs);
+        f.pos += 4 + (size_t)bs;
+    }
+}
+struct BamDevReads {
+    std::vector<uint8_t> status;
+    std::vector<uint64_t> start_key; // (tid, pos and end_key_pmax go into the BamReads the slice search reads)
+    uint64_t first_unsorted = ~0ull;
+    std::string pending;             // the panic of a file that ends inside a record
+    // DEVICE: the stream and the columns, resident until the process ends (nucfreq_bam never frees them: no synchronise-and-free of a
+    // gigabyte on the way out, as with the other text routes' buffers)
+    std::unique_ptr<DevBufs> dev;
+    const uint8_t *d_data = nullptr;
+    const uint32_t *d_ops = nullptr, *d_lseq = nullptr, *d_flag = nullptr;
+    const uint64_t *d_opoff = nullptr, *d_seqoff = nullptr;
+    const int32_t *d_tid = nullptr;
+    const int64_t *d_pos = nullptr;
+};
+// false: a record rb_dev_bam_records refuses -- the caller takes the host decode for the whole file, whose panics are the reference's
+static bool load_bam_reads_dev(Engine &eng, const std::string &path, const std::vector<Region> &rgns, BamReads &B, BamDevReads &R) {
+    static const bool timing = getenv("RB_TIMING") != nullptr;
+    double tl = now_s();
+    rb_ctx *ctx = eng.ctx();
+    // 1. read + inflate: the ranges the index names, or the whole file
+    struct Range {
+        BamStream f;
+        size_t a, e;   // the records that start in [a, e) of f
+        uint64_t base; // where f.buf[a] goes in the device buffer (16-byte aligned)
+    };
+    std::vector<std::unique_ptr<Range>> ranges;
+    B = BamReads();
+    if (!bam_indexed_ranges(path, rgns, B, [&](BamStream &f, size_t e) {
+            const size_t a = f.pos;
+            ranges.emplace_back(new Range{std::move(f), a, e, 0});
+        })) {
+        B = BamReads();
+        ranges.clear();
+        std::unique_ptr<Range> whole(new Range{BamStream(path), 0, ~(size_t)0, 0});
+        bam_read_header(whole->f, path, B);
+        whole->a = whole->f.pos;
+        ranges.push_back(std::move(whole));
+    }
+    lap("read + inflate", tl);
+    // 2. the hop.  A range's bytes end where its last record does (that can be behind e)
+    std::vector<uint64_t> rec_off;
+    std::vector<uint32_t> rec_len;
+    uint64_t bytes = 0;
+    for (auto &rg : ranges) {
+        if (!R.pending.empty()) {
+            rg->e = rg->a; // (the host decode has panicked before it came here)
+            continue;
+        }
+        rg->base = bytes;
+        rg->f.pos = rg->a;
+        bam_hop_records(rg->f, rg->e, rg->base - rg->a, rec_off, rec_len, R.pending);
+        rg->e = rg->f.pos;
+        bytes = (bytes + (rg->e - rg->a) + 15) & ~(uint64_t)15;
+    }
+    const size_t n = rec_off.size();
+    lap("record hop", tl);
+    // 3. the stream, once
+    R.dev.reset(new DevBufs(ctx));
+    DevBufs &d = *R.dev;
+    uint8_t *d_data = d.alloc<uint8_t>(eng, (size_t)bytes + 32);
+    for (auto &rg : ranges)
+        if (rg->e > rg->a) eng.check(rb_dev_upload(ctx, d_data + rg->base, rg->f.buf.get() + rg->a, rg->e - rg->a), "rb_dev_upload");
+    const uint64_t *d_roff = d.up(eng, rec_off);
+    const uint32_t *d_rlen = d.up(eng, rec_len);
+    lap("H2D stream + record places", tl);
+    // 4. the records and the per-read index
+    const uint64_t ops_cap = bytes / 4 + 8;
+    int32_t *d_tid = d.alloc<int32_t>(eng, n);
+    int64_t *d_pos = d.alloc<int64_t>(eng, n);
+    uint32_t *d_flag = d.alloc<uint32_t>(eng, n), *d_lseq = d.alloc<uint32_t>(eng, n);
+    uint8_t *d_st = d.alloc<uint8_t>(eng, n);
+    uint64_t *d_opoff = d.alloc<uint64_t>(eng, n + 2), *d_sqo = d.alloc<uint64_t>(eng, n), *d_sk = d.alloc<uint64_t>(eng, n), *d_ek = d.alloc<uint64_t>(eng, n);
+    uint64_t *d_fu = d.alloc<uint64_t>(eng, 1);
+    uint32_t *d_ops = d.alloc<uint32_t>(eng, (size_t)ops_cap + 32);
+    {
+        DevBufs t(ctx); // what nothing reads afterwards: the MD columns and the scratch of the two calls
+        uint8_t *d_has = t.alloc<uint8_t>(eng, n);
+        uint64_t *d_moff = t.alloc<uint64_t>(eng, n), *d_mend = t.alloc<uint64_t>(eng, n);
+        void *d_scr = t.alloc<uint8_t>(eng, rb_bam_scratch_bytes(n));
+        uint8_t *d_scr2 = t.alloc<uint8_t>(eng, rb_bam_reads_scratch_bytes(n) + 256);
+        d_scr2 = (uint8_t *)(((uintptr_t)d_scr2 + 255) & ~(uintptr_t)255);
+        eng.check(rb_dev_bam_records(ctx, d_data, d_roff, d_rlen, n, d_tid, d_pos, d_flag, d_lseq, d_has, d_moff, d_mend, d_opoff, d_ops, ops_cap, d_st, d_scr),
+                  "rb_dev_bam_records");
+        eng.check(rb_dev_bam_reads(ctx, d_data, d_roff, d_rlen, n, d_tid, d_pos, d_flag, d_opoff, d_ops, d_st, d_sqo, d_sk, d_ek, d_fu, d_scr2), "rb_dev_bam_reads");
+        R.status.resize(n), R.start_key.resize(n);
+        B.tid.resize(n), B.pos.resize(n), B.end_key_pmax.resize(n);
+        if (n) {
+            eng.check(rb_dev_download(ctx, R.status.data(), d_st, n), "rb_dev_download");
+            eng.check(rb_dev_download(ctx, B.tid.data(), d_tid, n * 4), "rb_dev_download");
+            eng.check(rb_dev_download(ctx, B.pos.data(), d_pos, n * 8), "rb_dev_download");
+            eng.check(rb_dev_download(ctx, R.start_key.data(), d_sk, n * 8), "rb_dev_download");
+            eng.check(rb_dev_download(ctx, B.end_key_pmax.data(), d_ek, n * 8), "rb_dev_download");
+        }
+        eng.check(rb_dev_download(ctx, &R.first_unsorted, d_fu, 8), "rb_dev_download");
+    }
+    lap("decode + columns D2H", tl);
+    for (size_t i = 0; i < n; i++)
+        if (R.status[i] != RB_BAM_OK) {
+            R.dev.reset();
+            return false;
+        }
+    if (timing) {
+        size_t n_ranges = 0;
+        for (auto &rg : ranges) n_ranges += rg->e > rg->a;
+        fprintf(stderr, "[rb timing] nucfreq_bam: rb_dev_bam_records, rb_dev_bam_reads\n");
+        fprintf(stderr, "[rb timing]   nucfreq_bam: %zu ranges of the stream back to back, %zu records, %llu bytes\n", n_ranges, n, (unsigned long long)bytes);
+    }
+    R.d_data = d_data, R.d_ops = d_ops, R.d_lseq = d_lseq, R.d_flag = d_flag, R.d_opoff = d_opoff, R.d_seqoff = d_sqo, R.d_tid = d_tid, R.d_pos = d_pos;
     return true;
 }
 
@@ -3650,15 +3788,29 @@ void nucfreq_bam(Engine &eng, const std::string &bam_path, const std::vector<Reg
     static const bool timing = getenv("RB_TIMING") != nullptr;
     bool route_named = false;
     BamReads B;
-    if (!load_bam_reads_indexed(bam_path, rgns, B)) {
+    // the decode on the device (load_bam_reads_dev): opt-in with RB_NUCFREQ_DEV_DECODE=1 -- end to end it is well ahead of the host decode
+    // on long reads, but on short reads without the index it fell behind the parent build by more than that one's run-to-run spread
+    // (profiles/nucfreq_bam_summary.md); RB_GENERAL_PATH=1 and a file with a record the device call refuses keep the host decode for
+    // the whole file
+    BamDevReads &R = *new BamDevReads; // (lives until the process ends, with its device buffers; a decline has freed them)
+    const bool dev_reads = !getenv("RB_GENERAL_PATH") && getenv("RB_NUCFREQ_DEV_DECODE") && load_bam_reads_dev(eng, bam_path, rgns, B, R);
+    if (dev_reads) {
+        tl = now_s();
+        if (!R.pending.empty()) throw Panic(R.pending);
+        if (R.first_unsorted != ~0ull) throw Panic("nucfreq: the BAM file is not coordinate sorted");
+    } else {
         B = BamReads();
-        load_bam_reads(bam_path, B);
+        if (!load_bam_reads_indexed(bam_path, rgns, B)) {
+            B = BamReads();
+            load_bam_reads(bam_path, B);
+        }
+        lap("nucfreq: inflate + decode BAM", tl);
     }
-    lap("nucfreq: inflate + decode BAM", tl);
     const uint64_t n_all = B.tid.size();
-    for (uint64_t i = 1; i < n_all; i++) // the pileup iterator refuses unsorted input ("the input is not sorted"), p.unwrap() panics
+    for (uint64_t i = 1; i < n_all && !dev_reads; i++) // the pileup iterator refuses unsorted input ("the input is not sorted"), p.unwrap() panics
         if (nf_key(B.tid[i], (uint64_t)B.pos[i]) < nf_key(B.tid[i - 1], (uint64_t)B.pos[i - 1]) && B.tid[i] >= 0 && B.pos[i] >= 0)
             throw Panic("nucfreq: the BAM file is not coordinate sorted");
+    auto start_key_at = [&](uint64_t i) { return dev_reads ? R.start_key[i] : nf_key(B.tid[i], (uint64_t)B.pos[i]); };
     const uint64_t MED = 1000000; // main.rs:101: one header per piece of this size
     // the work list: every region cut into chunks of at most 32 pieces; consecutive chunks on one contig share a device call
     struct Chunk {
@@ -3686,15 +3838,20 @@ void nucfreq_bam(Engine &eng, const std::string &bam_path, const std::vector<Reg
             uint64_t lo = i0, hi = n_all;
             while (lo < hi) {
                 const uint64_t mid = (lo + hi) >> 1;
-                if (nf_key(B.tid[mid], (uint64_t)B.pos[mid]) >= k_en) hi = mid; else lo = mid + 1;
+                if (start_key_at(mid) >= k_en) hi = mid; else lo = mid + 1;
             }
             const uint64_t i1 = std::max(lo, i0);
             if (i1 > i0) {
                 rb_nucfreq_counters ctr{};
                 rb_reads_view v{};
                 v.n_reads = i1 - i0;
-                v.ops = B.ops.data(), v.op_off = B.op_off.data() + i0, v.seq = B.seq.data(), v.seq_off = B.seq_off.data() + i0;
-                v.l_seq = B.l_seq.data() + i0, v.tid = B.tid.data() + i0, v.pos = B.pos.data() + i0, v.flag = B.flag.data() + i0;
+                if (dev_reads) { // the slice of the resident columns: ops and the stream by absolute offsets, nothing goes up again
+                    v.ops = R.d_ops, v.op_off = R.d_opoff + i0, v.seq = R.d_data, v.seq_off = R.d_seqoff + i0;
+                    v.l_seq = R.d_lseq + i0, v.tid = R.d_tid + i0, v.pos = R.d_pos + i0, v.flag = R.d_flag + i0;
+                } else {
+                    v.ops = B.ops.data(), v.op_off = B.op_off.data() + i0, v.seq = B.seq.data(), v.seq_off = B.seq_off.data() + i0;
+                    v.l_seq = B.l_seq.data() + i0, v.tid = B.tid.data() + i0, v.pos = B.pos.data() + i0, v.flag = B.flag.data() + i0;
+                }
                 status.assign((size_t)v.n_reads, 0);
                 // the reads the reference dies on: looked for before anything of the batch is printed
                 auto check_reads = [&]() {
@@ -3750,17 +3907,18 @@ void nucfreq_bam(Engine &eng, const std::string &bam_path, const std::vector<Reg
                             K.err = std::current_exception();
                         }
                     };
-                    const int rc = rb_host_nucfreq_text(eng.ctx(), &v, batch.size(), rt.data(), st.data(), en.data(), S.cnt.size(), S.cnt.data(), S.pos.data(),
+                    const int rc = (dev_reads ? rb_devreads_nucfreq_text : rb_host_nucfreq_text)(eng.ctx(), &v, batch.size(), rt.data(), st.data(), en.data(), S.cnt.size(), S.cnt.data(), S.pos.data(),
                                                         S.n.data(), (const uint8_t *)S.strings.data(), S.strings.size(), S.pre_off.data(), S.pre_len.data(),
                                                         S.suf_off.data(), S.suf_len.data(), small ? RB_NFT_SMALL : RB_NFT_FULL, status.data(), &ctr, sink, &sk);
                     if (sk.err) std::rethrow_exception(sk.err);
-                    eng.check(rc, "rb_host_nucfreq_text");
+                    eng.check(rc, dev_reads ? "rb_devreads_nucfreq_text" : "rb_host_nucfreq_text");
                     if (!sk.checked) check_reads();
                     lap("nucfreq: device + lines + write", tl);
                     return;
                 }
                 counts.assign((size_t)off[batch.size()] * 4 + 4, 0), counts_zeroed = true;
-                eng.check(rb_host_nucfreq(eng.ctx(), &v, batch.size(), rt.data(), st.data(), en.data(), counts.data(), status.data(), &ctr), "rb_host_nucfreq");
+                eng.check((dev_reads ? rb_devreads_nucfreq : rb_host_nucfreq)(eng.ctx(), &v, batch.size(), rt.data(), st.data(), en.data(), counts.data(), status.data(), &ctr),
+                          dev_reads ? "rb_devreads_nucfreq" : "rb_host_nucfreq");
                 check_reads();
             }
         }

@@ -44,18 +44,6 @@ extern "C" uint32_t rb_bam_copy_row_step(void) { return RB_BAM_COPY_ROW_STEP; }
 extern "C" uint32_t rb_bam_copy_row_max(void) { return RB_BAM_COPY_ROW_MAX; }
 extern "C" uint32_t rb_bam_copy_wave_step(void) { return RB_BAM_COPY_WAVE_STEP; }
 
-// the k <= 8 bytes data[a .. a + k) as a little-endian number (bytes above the k-th: anything), from the aligned dwords that hold one of them
-__device__ __forceinline__ uint64_t rb_bam_bytes(const uint8_t *data, const uint64_t a, const uint32_t k) {
-    const uint32_t ph = (uint32_t)a & 3u, nb = ph + k;
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(data + (a & ~3ull));
-    uint32_t d0 = 0u, d1 = 0u, d2 = 0u;
-    if (k) d0 = w[0];
-    if (nb > 4u) d1 = w[1];
-    if (nb > 8u) d2 = w[2];
-    const uint64_t lo = ((uint64_t)d1 << 32) | d0;
-    return ph ? (lo >> (8u * ph)) | ((uint64_t)d2 << (64u - 8u * ph)) : lo;
-}
-
 // bit i = byte i of the 16 is zero (exact per byte: no borrow runs from one byte into the next)
 __device__ __forceinline__ uint32_t rb_bam_zero_map(const uint4 v) {
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};

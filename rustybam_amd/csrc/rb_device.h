@@ -208,6 +208,19 @@ __device__ __forceinline__ uint4 rb_load4_unaligned(const uint32_t *p) {
     return make_uint4(t.x, t.y, t.z, t.w);
 }
 
+// ---- a byte stream (k_bam.hip, k_bamreads.hip) ----
+// the k <= 8 bytes data[a .. a + k) as a little-endian number (bytes above the k-th: anything), from the aligned dwords that hold one of them
+__device__ __forceinline__ uint64_t rb_bam_bytes(const uint8_t *data, const uint64_t a, const uint32_t k) {
+    const uint32_t ph = (uint32_t)a & 3u, nb = ph + k;
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(data + (a & ~3ull));
+    uint32_t d0 = 0u, d1 = 0u, d2 = 0u;
+    if (k) d0 = w[0];
+    if (nb > 4u) d1 = w[1];
+    if (nb > 8u) d2 = w[2];
+    const uint64_t lo = ((uint64_t)d1 << 32) | d0;
+    return ph ? (lo >> (8u * ph)) | ((uint64_t)d2 << (64u - 8u * ph)) : lo;
+}
+
 // ---- decimal text (k_text.hip, k_nftext.hip) ----
 // decimal digits of v, at most 9 (an op with a continuation word may have ten: its caller adds the tenth)
 __device__ __forceinline__ uint32_t rb_ndigits(uint32_t v) {

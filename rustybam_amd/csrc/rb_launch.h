@@ -292,6 +292,31 @@ extern "C" uint32_t rb_bam_copy_row_step(void);
 extern "C" uint32_t rb_bam_copy_row_max(void);
 extern "C" uint32_t rb_bam_copy_wave_step(void);
 
+// ---- k_bamreads.hip: the per-read index nucfreq's host code needs, from the columns of rb_dev_bam_records ----
+struct rb_bam_reads_params {
+    uint64_t n;
+    const uint8_t *data;     // the stream rb_dev_bam_records read
+    const uint64_t *rec_off; // [n]
+    const uint32_t *rec_len; // [n]
+    const int32_t *tid;      // [n]
+    const int64_t *pos;      // [n]
+    const uint32_t *flag;    // [n]
+    const uint64_t *op_off;  // [n + 1]
+    const uint32_t *ops;     // 16-byte aligned, readable to the next multiple of 4 words behind the last op
+    const uint8_t *status;   // [n] RB_BAM_*
+    uint64_t *seq_off;       // [n] OUT
+    uint64_t *start_key;     // [n] OUT
+    uint64_t *end_key_pmax;  // [n] OUT the reads' own end keys (0: does not enter), then their inclusive prefix maximum
+    unsigned long long *first_unsorted; // OUT, set to ~0 before the pass
+    uint64_t *blk;           // scratch: the maxima of the scan's workgroups, level by level
+};
+extern "C" hipError_t rb_launch_bam_reads(const rb_bam_reads_params *p, hipStream_t stream);
+extern "C" uint32_t rb_bam_reads_row_step(void);
+extern "C" uint32_t rb_bam_reads_row_max(void);
+extern "C" uint32_t rb_bam_reads_wave_step(void);
+extern "C" uint32_t rb_bam_reads_scan_block(void);
+extern "C" size_t rb_bam_reads_blk_count(uint64_t n);
+
 // ---- k_rows_batch.hip: the hit rows of a clip call as a dense batch ----
 struct rb_rows_batch_params {
     const uint32_t *ops;      // the source batch's packed ops (descriptor rows point into them)
